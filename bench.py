@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- candidate-root lnL evaluations/sec on BASELINE config c2.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one batch of `--batch` full-traversal candidate-root evaluations
 (2n-2 P-matrices + n-1 CLV operations + root reduction each;
@@ -188,6 +188,21 @@ def spawn_ranks(n):
     return failed or next((c for c in codes if c), 0)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, lnl):
+    """--dump-outputs: per-job lnLs as <directory>/lnl.npy (float64).  Past DUMP_LIMIT_BYTES, a
+    fixed, seeded sample of them: the same jobs on every run of the same command."""
+    import numpy as np
+    lnl = np.ascontiguousarray(lnl, dtype=np.float64)
+    keep = (DUMP_LIMIT_BYTES - 4096) // lnl.itemsize      # (room for the .npy header)
+    if lnl.size > keep:
+        lnl = lnl[np.sort(np.random.default_rng(0).choice(lnl.size, keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "lnl.npy"), lnl)
+
+
 def profiled_issue(kernel, batch, config):
     """Issue-slot figures of `kernel` derived by profiles/summarize.py from the
     committed SQ counter passes of the default command (c2, batch 197): VALU
@@ -255,7 +270,13 @@ def main():
                     help="N>1: split candidate roots (no collective, weak scaling; default) or "
                          "split site blocks and all-reduce the per-block lnLs (strong scaling; "
                          "BASELINE config c4 pattern)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the last timed step returned (rank 0's "
+                         "per-job lnLs) as DIR/lnl.npy, float64; the inputs depend on the arguments "
+                         "only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the
@@ -401,6 +422,7 @@ def main():
         sched_stats = [sc.stats() for sc in scheds]
 
     prepared = {}
+    last = {}     # the per-job lnLs of the latest step (what --dump-outputs writes)
 
     def step_jobs(s, params_, count):
         """which candidates step s evaluates and with which parameter draws"""
@@ -472,7 +494,9 @@ def main():
         """one batch: jobs rotate through this rank's candidates; parameters are
         re-drawn around their base values so no step repeats an earlier one."""
         if not use_fused:
-            return sum(evaluate_unfused(s * nb + b) for b in range(nb))
+            vals = [evaluate_unfused(s * nb + b) for b in range(nb)]
+            last["lnl"] = vals
+            return sum(vals)
         a = prepared.get(s) or prepare(s)
         executed["steps"] += a["steps"]
         executed["matvecs"] += a["matvecs"]
@@ -493,7 +517,9 @@ def main():
                 rdist.allreduce_lnl(host, site_group)
                 lnl_dev[:nb].copy_(host)
             return lnl_dev
-        return float(part.evaluate_batch(handles, sub, fr).sum())
+        lnl = part.evaluate_batch(handles, sub, fr)
+        last["lnl"] = lnl
+        return float(lnl.sum())
 
     def barrier():
         if pipeline is not None:
@@ -540,6 +566,10 @@ def main():
     executed_timed = dict(executed)
     if not np.isfinite(check) and not os.environ.get("RDAMD_BENCH_TIMING_ONLY"):   # (ablation runs: profiles/*_ab.sh)
         raise SystemExit("non-finite lnL in the timed region")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's lnLs as its caller received them (site-sharded: the summed row)
+        dump_outputs(args.dump_outputs, lnl_rows[args.steps - 1, :nb].cpu().numpy() if site_sharded
+                     else last["lnl"])
 
     # The K timed steps last tens of milliseconds: too short for the clocks to settle or for a
     # sampling monitor to see the device busy.  `sustained`: the very same step, looped for

@@ -267,6 +267,14 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert out.returncode != 0 and "WORLD_SIZE (1) != --gpus (2)" in out.stderr
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    import subprocess
+    root = os.path.dirname(HERE)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps must be at least 1" in out.stderr
+
+
 @pytest.mark.parametrize("world,victim", [(4, 2), (3, 0)])
 def test_rd_amd_ranks_notice_a_dead_rank(tmp_path, world, victim):
     """a rank that dies mid-search must not leave the others inside a collective.

@@ -190,3 +190,24 @@ def test_rccl_calls_of_the_multi_gpu_path_with_one_rank():
     c = run_bench("--no-cpu-baseline", env=env)          # candidate sharding: barrier + MAX only
     assert c["value"] > 0
     assert c["rccl_ranks"] == 1 and a["rccl_ranks"] == 1   # a real all-reduce over the communicator
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the per-job lnLs of the LAST timed step as DIR/lnl.npy (float64), from
+    inputs that depend on the arguments only -- two runs of one command write the same values,
+    another --steps another step's jobs."""
+    import numpy as np
+    one = run_bench("--no-cpu-baseline", "--sustain-seconds", "0", "--dump-outputs", str(tmp_path / "one"),
+                    steps="1")
+    a = np.load(tmp_path / "one" / "lnl.npy")
+    assert a.dtype == np.float64 and a.shape == (17,) and np.all(np.isfinite(a))
+    assert float(a.sum()) == one["lnl_check"]                # one timed step: its lnLs are the checksum
+    for name in ("b", "c"):
+        run_bench("--no-cpu-baseline", "--sustain-seconds", "0", "--dump-outputs", str(tmp_path / name))
+    b, c = np.load(tmp_path / "b" / "lnl.npy"), np.load(tmp_path / "c" / "lnl.npy")
+    assert b.shape == (17,) and np.allclose(b, c, rtol=1e-12, atol=0)
+    assert not np.allclose(a, b, rtol=1e-6, atol=0)          # step 3 of 3 is not step 1 of 1
+    # the site-sharded path (device-pointer output, one rank) dumps the same jobs' lnLs
+    run_bench("--no-cpu-baseline", "--shard", "sites", "--dump-outputs", str(tmp_path / "s"))
+    s = np.load(tmp_path / "s" / "lnl.npy")
+    assert s.dtype == np.float64 and np.allclose(s, b, rtol=1e-9, atol=0)

@@ -16,6 +16,7 @@ The DIVERGENCE GUARD: a rank whose copy of one sum is off by one ulp (a reducer 
 hand every rank the same bits) must fail the run on every rank at once, naming the round --
 never leave the group in a collective that no longer matches."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -26,6 +27,10 @@ import util
 SRC = os.path.join(util.ROOT, "tests", "cpp", "conductor_check.cpp")
 INC = ["-I", os.path.join(util.ROOT, "root_digger_amd", "csrc"), "-I", os.path.join(util.ROOT, "include"),
        "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__"]
+# GCC 11's ThreadSanitizer runtime aborts ("unexpected memory mapping") on kernels that randomise
+# mmap with more bits than its address layout allows: its programs run with address-space
+# randomisation off for that one process (setarch -R), what later TSan runtimes do by themselves
+TSAN_LAUNCH = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
 
 
 def _build(tmp_path, name, extra):
@@ -40,8 +45,9 @@ def _run_raw(exe, *args, timeout=120):
     return subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
 
 
-def _run(exe, *args, timeout=120):
-    out = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
+def _run(exe, *args, timeout=120, launch=()):
+    out = subprocess.run(list(launch) + [exe] + [str(a) for a in args], capture_output=True, text=True,
+                         timeout=timeout)
     assert out.returncode == 0 and out.stdout.startswith("conductor OK"), out.stdout + out.stderr[-2000:]
     return dict(kv.split("=") for kv in out.stdout.split()[2:]), out.stderr
 
@@ -61,7 +67,7 @@ def test_rounds_do_not_depend_on_thread_timing(tmp_path, ranks, workers, groups,
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_conductor_is_clean_under_thread_sanitizer(tmp_path):
     exe = _build(tmp_path, "conductor_check_tsan", ["-fsanitize=thread"])
-    got, err = _run(exe, 2, 6, 2, 23, 5, timeout=300)
+    got, err = _run(exe, 2, 6, 2, 23, 5, timeout=300, launch=TSAN_LAUNCH)
     assert "ThreadSanitizer" not in err, err[-3000:]
     plain = _run(_build(tmp_path, "conductor_check", []), 2, 6, 2, 23, 5)[0]
     assert got == plain
@@ -84,7 +90,7 @@ def test_device_path_rounds_with_random_second_pass_flags(tmp_path, ranks, worke
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_device_path_is_clean_under_thread_sanitizer(tmp_path):
     exe = _build(tmp_path, "conductor_check_tsan", ["-fsanitize=thread"])
-    got, err = _run(exe, 3, 6, 2, 17, 4, "device", timeout=300)
+    got, err = _run(exe, 3, 6, 2, 17, 4, "device", timeout=300, launch=TSAN_LAUNCH)
     assert "ThreadSanitizer" not in err, err[-3000:]
     assert int(got["redos"]) > 0
 
