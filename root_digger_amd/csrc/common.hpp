@@ -30,6 +30,10 @@ constexpr double kLogScaleThreshold = -177.44567822334599;
 // scratch P-matrix slots behind the caller's (root alpha variants)
 constexpr unsigned kTipcodePad = 256;   // bytes of slack after the tip-code rows
 
+// 20-state data the fused evaluator takes (kernels_fused_k20.hip: a workgroup is one wave per rate
+// category): up to eight categories, at any stack depth.  Beyond eight the traversal kernels serve.
+inline bool fused20_capable(unsigned states, size_t rate_cats) { return states == 20 && rate_cats <= 8; }
+
 void set_error(int code, const char *fmt, ...);
 void clear_error();
 

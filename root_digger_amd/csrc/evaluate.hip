@@ -63,6 +63,8 @@ struct FusedWorkspace {
   FusedJob *d_jobs = nullptr;   // ... and where this batch's pieces sit inside it
   double *d_q = nullptr, *d_rates = nullptr, *d_freqs = nullptr, *d_rw = nullptr;
   double *d_qpow20 = nullptr;   // 20 states: the powers of every job's Q (kernels_fused_k20.hip)
+  char *d_spill20 = nullptr;    // 20 states: the stack levels LDS has no room for (Fused20Args::spill)
+  size_t spill20_bytes = 0;
   double *d_pmat = nullptr, *d_tiptab = nullptr, *d_partials = nullptr, *d_out = nullptr;
   double *d_clade_scratch = nullptr;   // nested clade tables of a launch: [job][step][rate][rows][4]
   size_t clade_scratch_doubles = 0;
@@ -86,7 +88,7 @@ struct FusedWorkspace {
 
 void fused_workspace_free(FusedWorkspace *w) {
   if (!w) return;
-  void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20};
+  void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20, w->d_spill20};
   for (void *d : dev)
     if (d) (void)hipFree(d);
   if (w->h_out) (void)hipHostFree(w->h_out);
@@ -144,7 +146,7 @@ static hipError_t ensure_workspace(rdamd_partition *p, FusedWorkspace *&slot, un
   if (n_jobs <= w->cap_jobs) return hipSuccess;
   hipError_t e = sync_streams(p);
   if (e != hipSuccess) return e;
-  void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20};
+  void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20, w->d_spill20};
   for (void *d : dev)
     if (d) (void)hipFree(d);
   if (w->h_out) (void)hipHostFree(w->h_out);
@@ -205,7 +207,7 @@ static rdamd_schedule_t *schedule_create_impl(rdamd_partition_t *p, const rdamd_
                                               unsigned int n_matrices, bool allow_repeats) {
   // (clade cache, code arenas and the block pool belong to the partition: one thread at a time)
   std::lock_guard<std::mutex> guard(p->launch_mu);
-  const bool k20 = p->states == 20 && p->rate_cats <= 8;
+  const bool k20 = fused20_capable(p->states, p->rate_cats);
   if (p->states != 4 && !k20) {
     set_error(40, "rdamd_schedule_create: the fused evaluator handles 4-state data and 20-state "
                   "data with up to 8 rate categories; use rdamd_update_clvs for %u states, %u "
@@ -573,7 +575,7 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
                              const double *subst, const double *freqs,
                              const double *rates, const double *rate_weights,
                              bool host_out, void *lnl_device, bool export_children, double *mirror) {
-  const bool k20 = p->states == 20 && p->rate_cats <= 8;
+  const bool k20 = fused20_capable(p->states, p->rate_cats);
   if (p->states != 4 && !k20) {
     set_error(40, "rdamd_evaluate_batch: 4-state data, or 20-state data with up to 8 rate categories");
     return RDAMD_FAILURE;
@@ -724,6 +726,19 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     b.freqs = w->d_freqs; b.rate_weights = w->d_rw; b.partials = w->d_partials;
     b.pmat_job_stride = (size_t)p->prob_matrices * R * K * K;
     b.sites = p->sites; b.rate_cats = R; b.tiles = w->blocks_x;
+    b.spill = nullptr; b.spill_levels = 0;
+    if (const size_t spill = fused20_spill_bytes(R, w->blocks_x, n_jobs, max_depth[0])) {
+      // stacks deeper than LDS holds at this R: their lower levels in global memory
+      if (spill > w->spill20_bytes) {
+        RDAMD_HIP_TRY(sync_streams(p), RDAMD_FAILURE);
+        if (w->d_spill20) (void)hipFree(w->d_spill20);
+        w->d_spill20 = nullptr;
+        w->spill20_bytes = 0;
+        RDAMD_HIP_TRY(hipMalloc((void **)&w->d_spill20, spill), RDAMD_FAILURE);
+        w->spill20_bytes = spill;
+      }
+      b.spill = w->d_spill20;
+    }
     if (!pipelined) p->prof_begin(4);
     e = launch_fused20_pmatrix(b, w->d_q, w->d_qpow20, w->d_rates, n_jobs, p->prob_matrices, pre);
     if (!pipelined) p->prof_end();
@@ -1018,7 +1033,7 @@ int rdamd_evaluate_root_children(rdamd_partition_t *p, const rdamd_operation_t *
                                  unsigned int n_matrices, const double *subst, const double *freqs,
                                  const double *rates, const double *rate_weights, double *lnl_out) {
   clear_error();
-  if (!(p->states == 4 && !p->mfma_layout) && !(p->states == 20 && p->rate_cats <= 8 && p->mfma_layout)) {
+  if (!(p->states == 4 && !p->mfma_layout) && !(fused20_capable(p->states, p->rate_cats) && p->mfma_layout)) {
     set_error(50, "rdamd_evaluate_root_children: 4-state (or binary) partitions, and 20-state ones with up to 8 rate categories");
     return RDAMD_FAILURE;
   }

@@ -135,6 +135,11 @@ struct Fused20Args {
   // reference's per-site scalers)
   double   *export_clv[2];
   unsigned *export_cnt[2];
+  // stack levels beyond what LDS holds at this R: fused20_spill_bytes() of global scratch, one
+  // slice per (job, workgroup, wave); null when every program of the launch fits
+  // (spill_levels: set by the launch)
+  char     *spill;
+  unsigned  spill_levels;
 };
 // 4 states: in-memory stack entries of a program whose stack lives in one register slot, one
 // LDS slot and the wave's private segment (kernels_fused.hip, SP; the private segment has a
@@ -149,6 +154,9 @@ constexpr unsigned kFused20TabDoubles = kFused20TabCodes * kFused20TabRow;   // 
 size_t fused20_qpow_doubles();
 hipError_t launch_fused20_pmatrix(const Fused20Args &a, const double *d_q, double *d_qpow, const double *d_rates,
                                   unsigned n_jobs, unsigned n_mat, hipStream_t stream);
+// bytes of Fused20Args::spill a launch of n_jobs programs with stacks up to `depth` levels needs
+// (0 when they fit in LDS)
+size_t fused20_spill_bytes(unsigned R, unsigned tiles, unsigned n_jobs, unsigned depth);
 hipError_t launch_fused20_eval(const Fused20Args &a, unsigned n_jobs, unsigned max_depth,
                                double *d_out, hipStream_t stream);
 // ONE job through the exporting variant: the evaluation, and the root operation's inner children left

@@ -29,6 +29,8 @@
 #include "common.hpp"
 #include "fused.hpp"
 
+#include <algorithm>
+
 namespace rdamd {
 
 namespace {
@@ -325,7 +327,10 @@ fused20_pmatrix_kernel(const double *__restrict__ qpow, const double *__restrict
 // chains), so the per-step traffic through the CU's address unit, the LDS reads
 // and the scalar control flow are shared by NT x 16 sites.
 // Dynamic LDS: [root exchange R x NT x 16 x (8 + 4) B][per wave: one A copy (4 KB) +
-// `depth` stack levels of NT tiles].
+// `lds_levels` stack levels of NT tiles].  A program whose stack is deeper than LDS holds at this R
+// (fused20_lds_levels) keeps the levels from `lds_levels` on in global memory: the wave's own slice
+// of a.spill, a.spill_levels levels in the layout of an LDS level (SPILL: a variant of its own, so that
+// the launches that fit run the all-LDS code of before).
 // EXPORT (rdamd_evaluate_root_children): the steps the host flagged (0x8000 / 0x10000: they compute
 // the root operation's two children) also store the running CLV -- in the partition's operand
 // layout -- and its rescale count: what the root-only steps of the search read afterwards
@@ -333,9 +338,9 @@ fused20_pmatrix_kernel(const double *__restrict__ qpow, const double *__restrict
 // THREADS: 256 for up to four rate categories (the shape every measurement of DESIGN 4.6 is about),
 // 512 for five to eight -- a workgroup is R waves (round 6: `rd --rate-cats N` takes any N,
 // src/main.cpp:256-266; beyond eight the traversal kernels serve).
-template <int NT, bool EXPORT, int THREADS>
+template <int NT, bool EXPORT, int THREADS, bool SPILL>
 __global__ void __launch_bounds__(THREADS)
-fused20_eval_kernel(Fused20Args a, unsigned depth) {
+fused20_eval_kernel(Fused20Args a, unsigned lds_levels) {
   extern __shared__ char lds_raw[];
   const unsigned R = a.rate_cats, S = a.sites;
   const unsigned lane = threadIdx.x & 63, r = uni(threadIdx.x >> 6);
@@ -350,9 +355,11 @@ fused20_eval_kernel(Fused20Args a, unsigned depth) {
 
   double *root_f = reinterpret_cast<double *>(lds_raw);
   int *root_sc = reinterpret_cast<int *>(lds_raw + R * NT * 16 * 8);
-  const unsigned wave_bytes = kCopyLds + depth * NT * kLevelBytes;
+  const unsigned wave_bytes = kCopyLds + lds_levels * NT * kLevelBytes;
   char *a_lds = lds_raw + R * NT * 16 * 12 + r * wave_bytes;   // [4 pieces][64 lanes][16 B]
   char *stack = a_lds + kCopyLds;                               // [level][tile][5][64] doubles + [64] counts
+  // levels lds_levels .. lds_levels + a.spill_levels - 1: [level - lds_levels][tile] ... in global memory
+  char *gstack = a.spill + (((size_t)job * gridDim.x + blockIdx.x) * R + r) * ((size_t)a.spill_levels * NT * kLevelBytes);
 
   const FusedJob jb = a.jobs[job];
   const const_u32_ptr prog = scalar_ptr(jb.prog);   // n_ops + 4 entries (tail padded)
@@ -527,30 +534,40 @@ fused20_eval_kernel(Fused20Args a, unsigned depth) {
           s0sc[q] = sc[q];
         }
       } else {
+        auto push = [&](char *base) {
 #pragma unroll
-        for (int q = 0; q < NT; ++q) {
-          char *level = stack + (sp * NT + q) * kLevelBytes;
-          double *lv = reinterpret_cast<double *>(level) + lane;
+          for (int q = 0; q < NT; ++q) {
+            char *level = base + q * kLevelBytes;
+            double *lv = reinterpret_cast<double *>(level) + lane;
 #pragma unroll
-          for (int s = 0; s < kSteps; ++s) lv[s * 64] = d1[q][s];
-          reinterpret_cast<int *>(level + kSteps * 64 * 8)[lane] = sc[q];
-        }
+            for (int s = 0; s < kSteps; ++s) lv[s * 64] = d1[q][s];
+            reinterpret_cast<int *>(level + kSteps * 64 * 8)[lane] = sc[q];
+          }
+        };
+        if (!SPILL || sp < lds_levels) push(stack + sp * NT * kLevelBytes);
+        else if (sp - lds_levels < a.spill_levels) push(gstack + (size_t)(sp - lds_levels) * NT * kLevelBytes);
         ++sp;
       }
     } else {
       if (kind == kFusedRP && !(cur.flags & 0x400u)) --sp;
+      // ... or on the stack (multiplied by its matrix when parked): LDS or, beyond its levels, global memory
+      auto pop = [&](const char *base, int q) {
+        const char *level = base + q * kLevelBytes;
+        const double *lv = reinterpret_cast<const double *>(level) + lane;
+#pragma unroll
+        for (int s = 0; s < kSteps; ++s) v[q][s] = d1[q][s] * lv[s * 64];
+        sc[q] += reinterpret_cast<const int *>(level + kSteps * 64 * 8)[lane];
+      };
+      const bool pop_lds = !SPILL || sp < lds_levels, pop_global = !pop_lds && sp - lds_levels < a.spill_levels;
 #pragma unroll
       for (int q = 0; q < NT; ++q) {
         if (kind == kFusedRP && (cur.flags & 0x400u)) {   // the sibling waits in the register slot
 #pragma unroll
           for (int s = 0; s < kSteps; ++s) v[q][s] = d1[q][s] * s0[q][s];
           sc[q] += s0sc[q];
-        } else if (kind == kFusedRP) {   // ... or on the LDS stack (multiplied by its matrix when parked)
-          const char *level = stack + (sp * NT + q) * kLevelBytes;
-          const double *lv = reinterpret_cast<const double *>(level) + lane;
-#pragma unroll
-          for (int s = 0; s < kSteps; ++s) v[q][s] = d1[q][s] * lv[s * 64];
-          sc[q] += reinterpret_cast<const int *>(level + kSteps * 64 * 8)[lane];
+        } else if (kind == kFusedRP) {
+          if (pop_lds) pop(stack + sp * NT * kLevelBytes, q);
+          else if (pop_global) pop(gstack + (size_t)(sp - lds_levels) * NT * kLevelBytes, q);
         } else if (kind == kFusedRT) {   // this step's table rows, used in place
           double y[kSteps];
           row_of(t2[q], y);
@@ -705,30 +722,50 @@ hipError_t launch_fused20_pmatrix(const Fused20Args &a, const double *d_q, doubl
 
 constexpr int kFused20Tiles = 1;   // 16-site tiles per wave
 
-size_t fused20_lds_bytes(unsigned R, unsigned depth) {
+constexpr size_t kFused20LdsBudget = 160 * 1024;   // LDS of a CU: the most one workgroup can have
+
+static size_t fused20_lds_bytes(unsigned R, unsigned lds_levels) {
   return (size_t)R * kFused20Tiles * 16 * 12 +
-         (size_t)R * (kCopyLds + (size_t)depth * kFused20Tiles * kLevelBytes);
+         (size_t)R * (kCopyLds + (size_t)lds_levels * kFused20Tiles * kLevelBytes);
+}
+
+// the stack levels a wave keeps in LDS: all `depth` of them where they fit (at most 56 at R = 1,
+// 13 at R = 4, 5 at R = 8), the rest go to global memory
+static unsigned fused20_lds_levels(unsigned R, unsigned depth) {
+  const size_t fixed = fused20_lds_bytes(R, 0), per_level = (size_t)R * kFused20Tiles * kLevelBytes;
+  const size_t fit = fixed >= kFused20LdsBudget ? 0 : (kFused20LdsBudget - fixed) / per_level;
+  return (unsigned)std::min<size_t>(depth, fit);
+}
+
+size_t fused20_spill_bytes(unsigned R, unsigned tiles, unsigned n_jobs, unsigned depth) {
+  const unsigned levels = depth - fused20_lds_levels(R, depth);
+  const size_t groups = (tiles + kFused20Tiles - 1) / kFused20Tiles;
+  return (size_t)n_jobs * groups * R * levels * kFused20Tiles * kLevelBytes;
 }
 
 // one instantiation: its LDS limit raised when a launch needs more than 64 KB (raised, never lowered:
 // partitions launch from their own host threads), then the launch
-template <bool EXPORT, int THREADS>
-static hipError_t launch_fused20_variant(const Fused20Args &a, unsigned n_jobs, unsigned max_depth, hipStream_t stream) {
-  const size_t lds = fused20_lds_bytes(a.rate_cats, max_depth);
-  if (lds > 160u * 1024u) return hipErrorInvalidValue;   // (deep stacks at many rate categories)
+template <bool EXPORT, int THREADS, bool SPILL>
+static hipError_t launch_fused20_variant(const Fused20Args &args, unsigned n_jobs, unsigned max_depth, hipStream_t stream) {
+  Fused20Args a = args;
+  const unsigned lds_levels = fused20_lds_levels(a.rate_cats, max_depth);
+  a.spill_levels = max_depth - lds_levels;
+  // (the caller sized a.spill with fused20_spill_bytes for this launch)
+  if (a.spill_levels && !a.spill) return hipErrorInvalidValue;
+  const size_t lds = fused20_lds_bytes(a.rate_cats, lds_levels);
   {
     static std::mutex lds_mu;
     static size_t lds_allowed = 64 * 1024;
     std::lock_guard<std::mutex> guard(lds_mu);
     if (lds > lds_allowed) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fused20_eval_kernel<kFused20Tiles, EXPORT, THREADS>),
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fused20_eval_kernel<kFused20Tiles, EXPORT, THREADS, SPILL>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return e;
       lds_allowed = lds;
     }
   }
   const unsigned groups = (a.tiles + kFused20Tiles - 1) / kFused20Tiles;
-  fused20_eval_kernel<kFused20Tiles, EXPORT, THREADS><<<dim3(groups, n_jobs), 64 * a.rate_cats, lds, stream>>>(a, max_depth);
+  fused20_eval_kernel<kFused20Tiles, EXPORT, THREADS, SPILL><<<dim3(groups, n_jobs), 64 * a.rate_cats, lds, stream>>>(a, lds_levels);
   return hipGetLastError();
 }
 
@@ -736,8 +773,12 @@ hipError_t launch_fused20_eval(const Fused20Args &a, unsigned n_jobs, unsigned m
                                double *d_out, hipStream_t stream) {
   if (!n_jobs) return hipSuccess;
   if (a.rate_cats > 8) return hipErrorInvalidValue;
-  hipError_t e = a.rate_cats <= 4 ? launch_fused20_variant<false, 256>(a, n_jobs, max_depth, stream)
-                                  : launch_fused20_variant<false, 512>(a, n_jobs, max_depth, stream);
+  const bool spill = fused20_lds_levels(a.rate_cats, max_depth) < max_depth;
+  hipError_t e = a.rate_cats <= 4
+      ? (spill ? launch_fused20_variant<false, 256, true>(a, n_jobs, max_depth, stream)
+               : launch_fused20_variant<false, 256, false>(a, n_jobs, max_depth, stream))
+      : (spill ? launch_fused20_variant<false, 512, true>(a, n_jobs, max_depth, stream)
+               : launch_fused20_variant<false, 512, false>(a, n_jobs, max_depth, stream));
   if (e != hipSuccess) return e;
   fused20_finish_kernel<<<n_jobs, 256, 0, stream>>>(a.partials, a.tiles, d_out);
   return hipGetLastError();
@@ -746,8 +787,12 @@ hipError_t launch_fused20_eval(const Fused20Args &a, unsigned n_jobs, unsigned m
 hipError_t launch_fused20_export(const Fused20Args &a, unsigned max_depth, unsigned *const d_scaler[2],
                                  double *d_out, hipStream_t stream) {
   if (a.rate_cats > 8) return hipErrorInvalidValue;
-  hipError_t e = a.rate_cats <= 4 ? launch_fused20_variant<true, 256>(a, 1, max_depth, stream)
-                                  : launch_fused20_variant<true, 512>(a, 1, max_depth, stream);
+  const bool spill = fused20_lds_levels(a.rate_cats, max_depth) < max_depth;
+  hipError_t e = a.rate_cats <= 4
+      ? (spill ? launch_fused20_variant<true, 256, true>(a, 1, max_depth, stream)
+               : launch_fused20_variant<true, 256, false>(a, 1, max_depth, stream))
+      : (spill ? launch_fused20_variant<true, 512, true>(a, 1, max_depth, stream)
+               : launch_fused20_variant<true, 512, false>(a, 1, max_depth, stream));
   if (e != hipSuccess) return e;
   fused20_finish_kernel<<<1, 256, 0, stream>>>(a.partials, a.tiles, d_out);
   if (a.export_clv[0] || a.export_clv[1]) {

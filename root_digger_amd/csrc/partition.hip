@@ -237,12 +237,12 @@ uint64_t rdamd_partition_footprint(unsigned int tips, unsigned int clv_buffers, 
                                    unsigned int rate_cats, unsigned int scale_buffers) {
   const uint64_t K = states == 2 ? 4 : states, R = rate_cats, S = sites;
   const uint64_t codes = K == 4 ? 16 : 64;
-  const uint64_t Sclv = (K == 20 && R <= 8) ? (S + 15) / 16 * 16 : S;   // operand layout: whole 16-site tiles
+  const uint64_t Sclv = fused20_capable((unsigned)K, R) ? (S + 15) / 16 * 16 : S;   // operand layout: whole 16-site tiles
   // (4 states: the tip codes twice -- as codes and as LDS row offsets for the fused evaluator)
   uint64_t b = (uint64_t)tips * ((S + 3) / 4 * 4) * (K == 4 ? 2 : 1) + (uint64_t)clv_buffers * Sclv * R * K * 8 +
                (uint64_t)scale_buffers * S * 4 + (uint64_t)prob_matrices * R * K * K * 8 +
                (uint64_t)prob_matrices * R * codes * K * 8 + S * 4 + ((uint64_t)6 << 20);
-  if (K == 20 && R <= 8) b += (uint64_t)prob_matrices * R * k20_mfma_copy_doubles() * 8;
+  if (fused20_capable((unsigned)K, R)) b += (uint64_t)prob_matrices * R * k20_mfma_copy_doubles() * 8;
   return b;
 }
 
@@ -305,7 +305,7 @@ rdamd_partition_t *rdamd_partition_create(unsigned int tips, unsigned int clv_bu
   }
   // (the 20-state matrix-core kernel keeps CLVs in its operand layout, whole 16-site tiles:
   // decided here, before the CLV buffers are sized -- common.hpp)
-  p->mfma_layout = K == 20 && R <= 8 &&
+  p->mfma_layout = fused20_capable(K, R) &&
                    (size_t)p->clv_tiles() * 16u * R * K * sizeof(double) < ((size_t)1 << 31) &&
                    (size_t)prob_matrices * R * k20_mfma_copy_doubles() * sizeof(double) < ((size_t)1 << 31);
   p->sparse = (attributes & RDAMD_ATTRIB_SPARSE_CLVS) != 0;
