@@ -592,13 +592,18 @@ void rdamd_model_set_lockstep_groups(rdamd_model_t *m, unsigned int groups);
  * form identical rounds, which is what lets a SITE-SHARDED model search in lock step at all.
  * mode -1 (default): rounds for site-sharded models, arrival order otherwise; 0: arrival order
  * (a site-sharded model refuses); 1: rounds always.  Records are the sequential search's either
- * way.  Rounds take single-partition models. */
+ * way.  A partitioned model's round makes one objective launch per partition that has jobs, each
+ * on that partition's stream, and still ONE collective for all of them. */
 void rdamd_model_set_lockstep_rounds(rdamd_model_t *m, int mode);
 /* the last search in rounds: out[0] rounds closed, [1] collectives queued (rounds that had
  * anything to sum, plus repeats), [2] rounds repeated because a rank's batch needed its second
- * evaluator pass; [3] (any search) collectives THIS model asked its reducer for by itself --
+ * evaluator pass (only the partitions whose batch did launch again); [3] (any search) collectives THIS model asked its reducer for by itself --
  * the sequential site-sharded search's count, one per request */
 void rdamd_model_round_stats(const rdamd_model_t *m, uint64_t out[4]);
+/* ... per objective partition p of the last search in rounds: out[0] objective launches of that
+ * partition (at most one per round), [1] its second-pass launches in repeated rounds -- only the
+ * partitions whose batch raised the flag launch again */
+int rdamd_model_round_partition_stats(const rdamd_model_t *m, unsigned int p, uint64_t out[2]);
 /* ... and where its rounds spent their host time, seconds summed over the rounds: out[0] queueing
  * the objective batch, [1] the root-only launch (it blocks), [2] queueing the sum (a host
  * reducer: waiting for the batch and summing), [3] waiting for the round's event */
@@ -824,6 +829,34 @@ rdamd_model_t *rdamd_model_create_from_file_block(const rdamd_tree_t *tree, cons
                                                   unsigned int block, unsigned int n_blocks,
                                                   unsigned int *n_patterns,
                                                   unsigned int *n_columns);
+/* One rank's block of the partitioned model of src/main.cpp:512-555 (a site-sharded run with a
+ * partition file).  The alignment is read whole and cut into the partition file's column ranges,
+ * as rdamd_model_create_partitioned does; then EACH PARTITION'S OWN columns (its ranges, in file
+ * order) are split into n_blocks contiguous blocks by the rule of rdamd_model_create_from_file_block
+ * (chunking of src/model.cpp:1899-1907), and this model holds block `block` of every partition,
+ * each compressed on its own.  Rate categories come from each line's model string.  A partition
+ * with fewer columns than n_blocks is refused (the error names it).  n_partitions: optional.
+ * patterns / columns (optional): per partition, the block's patterns and the partition's whole
+ * column count -- room for one entry per non-blank line of the partition file.
+ * Summation order of a site group on this model (rdamd_model_set_lnl_reducer): a partition's
+ * objective value is the group's sum of its block lnLs; a root lnL is summed over the partitions
+ * in file order on each rank, then over the group; empirical frequencies are the group's
+ * per-partition sums.  The sequential search and the search in rounds
+ * (rdamd_model_exhaustive_search_lockstep) add the same numbers in that order. */
+rdamd_model_t *rdamd_model_create_partitioned_block(const rdamd_tree_t *tree, const char *msa_filename,
+                                                    const char *partition_filename, unsigned int states,
+                                                    const uint64_t *map, uint64_t seed, int early_stop,
+                                                    unsigned int block, unsigned int n_blocks,
+                                                    unsigned int *n_partitions, unsigned int *patterns,
+                                                    unsigned int *columns);
+/* compute_lh's per-partition terms at rl on THIS model's own columns, not summed over a site
+ * group: out[p] for every partition, in file order.  Diagnostic. */
+int rdamd_model_partition_lnls(rdamd_model_t *m, const rdamd_root_location_t *rl, double *out);
+/* the frequencies partition p of the model evaluates with now (states doubles) */
+int rdamd_model_partition_frequencies(rdamd_model_t *m, unsigned int p, double *out);
+/* rdamd_evaluate_second_passes of the model's own partition p (the objective partition of a
+ * search in rounds): batches that needed the evaluator's second pass so far */
+unsigned long long rdamd_model_partition_second_passes(const rdamd_model_t *m, unsigned int p);
 
 /* RCCL communicator of one site group (librccl is loaded on first use; the
  * library has no link-time dependency on it).  Rank 0 of the group calls

@@ -246,6 +246,7 @@ _sig("rdamd_model_set_lockstep_groups", None, C.c_void_p, _u)
 _sig("rdamd_model_set_lockstep_rounds", None, C.c_void_p, C.c_int)
 _sig("rdamd_model_round_stats", None, C.c_void_p, C.POINTER(C.c_uint64))
 _sig("rdamd_model_round_seconds", None, C.c_void_p, _pd)
+_sig("rdamd_model_round_partition_stats", C.c_int, C.c_void_p, _u, C.POINTER(C.c_uint64))
 _sig("rdamd_model_set_lockstep_priority", None, C.c_void_p, C.c_int)
 _sig("rdamd_model_set_root_children_only", None, C.c_void_p, C.c_int)
 _sig("rdamd_partition_set_stream_priority", C.c_int, _vp, C.c_int)
@@ -265,6 +266,11 @@ LNL_REDUCER = C.CFUNCTYPE(C.c_int, _pd, _u, _vp, _vp)
 _sig("rdamd_model_set_lnl_reducer", C.c_int, _vp, _vp, _vp, C.c_int)
 _sig("rdamd_model_create_from_file_block", _vp, _vp, C.c_char_p, _u, C.c_void_p,
      C.POINTER(RatehetOpts), C.c_uint64, C.c_int, C.c_int, _u, _u, _pu, _pu)
+_sig("rdamd_model_create_partitioned_block", _vp, _vp, C.c_char_p, C.c_char_p, _u, C.c_void_p, C.c_uint64,
+     C.c_int, _u, _u, _pu, _pu, _pu)
+_sig("rdamd_model_partition_lnls", C.c_int, _vp, _prl, _pd)
+_sig("rdamd_model_partition_frequencies", C.c_int, _vp, _u, _pd)
+_sig("rdamd_model_partition_second_passes", C.c_ulonglong, _vp, _u)
 _sig("rdamd_partition_weight_sum", C.c_double, _vp)
 _sig("rdamd_partition_stream", _vp, _vp)
 _sig("rdamd_comm_unique_id", C.c_int, C.c_char * 128)
@@ -1218,6 +1224,46 @@ class Model:
         self.patterns, self.columns = n.value, cols.value
         return self
 
+    @classmethod
+    def from_partition_file_block(cls, tree, msa_path, partition_path, block, n_blocks, states=4, cmap=None,
+                                  seed=1, early_stop=False):
+        """One rank's model of a site-sharded partitioned run: block `block` of `n_blocks` of EVERY
+        partition's own columns (rdamd_model_create_partitioned_block; dist.partition_site_blocks
+        states the split); pair it with set_lnl_reducer.  `patterns` / `columns`: per partition, the
+        block's patterns and the partition's whole column count."""
+        self = cls.__new__(cls)
+        self._tree, self.states = tree, states
+        with open(partition_path) as f:
+            cap = len(f.read().splitlines()) + 1
+        n = C.c_uint(0)
+        pats, cols = (C.c_uint * cap)(), (C.c_uint * cap)()
+        self._h = lib.rdamd_model_create_partitioned_block(
+            tree._h, os.fsencode(msa_path), os.fsencode(partition_path), states,
+            cmap if cmap is not None else MAP_NT, seed, 1 if early_stop else 0, block, n_blocks, C.byref(n),
+            pats, cols)
+        if not self._h:
+            _fail("model_create_partitioned_block")
+        self.partitions = n.value
+        self.patterns = [int(pats[i]) for i in range(n.value)]
+        self.columns = [int(cols[i]) for i in range(n.value)]
+        return self
+
+    def partition_lnls(self, rl):
+        """compute_lh's per-partition terms at rl on this model's own columns (no site-group sum)."""
+        out = np.zeros(self.partition_count(), dtype=np.float64)
+        self._ok(lib.rdamd_model_partition_lnls(self._h, C.byref(rl), _dptr(out)), "partition_lnls")
+        return out
+
+    def partition_frequencies(self, p):
+        """the frequencies partition p evaluates with now"""
+        out = np.zeros(self.states, dtype=np.float64)
+        self._ok(lib.rdamd_model_partition_frequencies(self._h, p, _dptr(out)), "partition_frequencies")
+        return out
+
+    def partition_second_passes(self, p):
+        """batches of the model's own partition p that needed the evaluator's second pass so far"""
+        return int(lib.rdamd_model_partition_second_passes(self._h, p))
+
     def set_lnl_reducer(self, fn, on_device=False, user=None):
         """Site-group reduction hook (rdamd_model_set_lnl_reducer).  `fn` is either a
         Python callable(values: float64 numpy view, n) -> None summing a HOST
@@ -1396,6 +1442,16 @@ class Model:
         d = dict(zip(("rounds", "collectives", "redos", "own_collectives"), (int(v) for v in out)))
         d["seconds"] = dict(zip(("objective_queued", "root_launch", "sum_queued", "waiting"), (float(v) for v in sec)))
         return d
+
+    def round_partition_stats(self):
+        """per objective partition of the last search in rounds: its launches and its second-pass
+        launches in repeated rounds (rdamd_model_round_partition_stats)"""
+        out = []
+        for p in range(self.partition_count()):
+            v = (C.c_uint64 * 2)()
+            self._ok(lib.rdamd_model_round_partition_stats(self._h, p, v), "round_partition_stats")
+            out.append({"launches": int(v[0]), "redo_launches": int(v[1])})
+        return out
 
     def set_root_children_only(self, on):
         """the searches' compute_lh in front of the root-only steps: True (default) = one fused job

@@ -19,11 +19,19 @@
 //   * values it only needs summed (compute_lh's lnL, src/model.cpp:384-413),
 //   * or "my candidate is done, give me the next one" --
 // so its composition is a function of the data, not of thread timing.  The round then is: the
-// objective jobs of all candidates in worker order as ONE launch of the fused evaluator on the
-// shared partition, the root positions of all candidates as ONE root_multi launch beside it,
-// and ONE all-reduce over [objective lnLs | second-pass flag | root lnLs | plain values] queued
-// behind them on the shared partition's stream: one collective per round instead of one per
-// request (13 / 5 / 2-job batches and single Brent steps in the sequential loop).
+// objective jobs of all candidates in worker order as ONE launch of the fused evaluator per
+// objective partition that has any (a candidate is in one partition's L-BFGS-B phase at a time,
+// src/model.cpp:1935-1960; each launch on that partition's own stream), the root positions of all
+// candidates as ONE root_multi launch beside them, and ONE all-reduce over
+//   [partition 0's objective lnLs | its second-pass flag | partition 1's ... | root lnLs | plain values]
+// queued on partition 0's stream, which waits for the other partitions' launches through events:
+// one collective per round for all partitions instead of one per request (13 / 5 / 2-job batches
+// and single Brent steps in the sequential loop).
+//
+// SUMMATION ORDER (the sequential site-sharded search sums the same numbers in the same order, so
+// the two give the same records bit for bit): a partition's objective value is the site group's sum
+// of that partition's block lnLs; a root lnL is summed over the partitions in file order on each
+// rank, then over the site group (what compute_lh_root / compute_all_root_lh_batched do).
 //
 // Two worker groups alternate STRICTLY (A0 B0 A1 B1 ...): while one group's round is on the
 // device and in the collective, the other group's hosts take their optimiser steps; the turn is
@@ -35,7 +43,9 @@
 // fused.hpp) is the one decision a batch used to take on the host.  Here the flag travels
 // through the all-reduce as one more summand (rdamd_evaluate_batch_submit_device): all ranks
 // learn together that some rank needs the pass, all redo the collective, in the same place of
-// the order (the redo waits for the group's turn).
+// the order (the redo waits for the group's turn).  Every objective partition has its own flag:
+// only the partitions whose summed flag is up launch their second pass; the others' slots carry
+// zeros through the repeated collective and keep the sums of the first one.
 //
 // THE ASSUMPTION, AND ITS GUARD.  All of the above rests on one thing: every rank of the group
 // receives the same BITS from the reducer.  The library's RCCL reducer makes that true by
@@ -68,6 +78,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/root_digger_amd.h"
@@ -77,7 +88,12 @@ namespace rdamd {
 class conductor_t {
 public:
   struct config_t {
-    rdamd_partition_t *shared = nullptr;   // the objective partition (the parent model's; not owned)
+    rdamd_partition_t *shared = nullptr;   // the objective partition (the parent model's; not owned) ...
+    std::vector<rdamd_partition_t *> parts;   // ... or one per model partition, in file order (parts[0]'s
+                                              // stream carries the collective); empty: {shared}
+    // how the collective's stream waits for another objective partition's stream (the library hands in
+    // hipStreamWaitEvent); needed with more than one objective partition
+    hipError_t (*stream_wait_event)(hipStream_t, hipEvent_t, unsigned int) = nullptr;
     unsigned n_workers = 1, n_groups = 1;
     size_t n_candidates = 0;
     // the site group's sum (all null: a one-rank "group", nothing to sum)
@@ -94,8 +110,14 @@ public:
   };
 
   explicit conductor_t(const config_t &c) : _c(c) {
+    if (_c.parts.empty() && _c.shared) _c.parts.push_back(_c.shared);
+    _c.shared = _c.parts.empty() ? nullptr : _c.parts[0];
+    for (rdamd_partition_t *p : _c.parts)
+      if (!p) throw std::invalid_argument("conductor: an objective partition is null");
     if (!_c.shared || _c.n_workers < 1 || _c.n_groups < 1 || _c.n_groups > 2)
       throw std::invalid_argument("conductor: a shared partition, >= 1 workers, 1 or 2 groups");
+    if (_c.parts.size() > 1 && !_c.stream_wait_event)
+      throw std::invalid_argument("conductor: several objective partitions need a stream_wait_event");
     _c.n_groups = std::min(_c.n_groups, _c.n_workers);
     for (unsigned w = 0; w < _c.n_workers; ++w) ++_g[w % _c.n_groups].live;
   }
@@ -105,12 +127,15 @@ public:
       if (g.h_in) (void)hipHostFree(g.h_in);
       if (g.h_res) (void)hipHostFree(g.h_res);
       if (g.ev) (void)hipEventDestroy(g.ev);
+      for (hipEvent_t e : g.part_ev)
+        if (e) (void)hipEventDestroy(e);
     }
   }
   conductor_t(const conductor_t &) = delete;
   conductor_t &operator=(const conductor_t &) = delete;
 
-  rdamd_partition_t *shared() const { return _c.shared; }
+  rdamd_partition_t *shared(size_t part = 0) const { return _c.parts.at(part); }
+  size_t n_parts() const { return _c.parts.size(); }
 
   // ---- what a worker (one candidate in flight, on its own model replica) may ask for ---------
   // index of its next candidate, or -1: nothing left, the worker has left its group
@@ -120,14 +145,19 @@ public:
     post(r);
     return r.candidate;
   }
-  // n jobs of one schedule of the shared partition (rdamd_evaluate_batch's blocks); out[j] =
+  // n jobs of one schedule of objective partition `part` (rdamd_evaluate_batch's blocks); out[j] =
   // the lnL of job j summed over the site group
-  void objective(unsigned worker, unsigned n, const rdamd_schedule_t *sched, const double *subst,
+  void objective(unsigned worker, unsigned part, unsigned n, const rdamd_schedule_t *sched, const double *subst,
                  const double *freqs, const double *rates, const double *weights, double *out) {
+    if (part >= _c.parts.size()) throw std::invalid_argument("conductor: objective partition out of range");
     request_t r;
-    r.kind = OBJECTIVE; r.worker = worker; r.n = n; r.sched = sched;
+    r.kind = OBJECTIVE; r.worker = worker; r.part = part; r.n = n; r.sched = sched;
     r.subst = subst; r.freqs = freqs; r.rates = rates; r.weights = weights; r.out = out;
     post(r);
+  }
+  void objective(unsigned worker, unsigned n, const rdamd_schedule_t *sched, const double *subst,
+                 const double *freqs, const double *rates, const double *weights, double *out) {
+    objective(worker, 0, n, sched, subst, freqs, rates, weights, out);
   }
   // n <= 8 positions of root operation `op` on the worker's own partitions; out[a] = the lnL of
   // position a, summed over the partitions (in their order) and then over the site group
@@ -153,12 +183,14 @@ public:
     _cv.notify_all();
   }
 
-  // rounds closed, collectives queued, objective launches / their jobs, root launches / their steps
+  // rounds closed, collectives queued, objective launches (one per partition with jobs per round) /
+  // their jobs, root launches / their steps, repeated collectives / second-pass launches in them
   // seconds[]: host time of the rounds' phases, summed: [0] the objective batch queued, [1] the
   // root-only launch (blocking), [2] the sum queued (host reducer: batch waited for and summed),
   // [3] waiting for the round's event and handing out the results
   struct stats_t {
     uint64_t rounds = 0, collectives = 0, obj_launches = 0, obj_jobs = 0, root_launches = 0, root_steps = 0, redos = 0;
+    std::vector<uint64_t> part_launches, part_redo_launches;   // [objective partition]: launches, second-pass launches
     uint64_t group_size = 0;   // ranks the guard's counting word has seen in the sums (0: no round with a sum yet)
     double seconds[4] = {0, 0, 0, 0};
   };
@@ -172,6 +204,7 @@ private:
   struct request_t {
     kind_t kind = NEXT;
     unsigned worker = 0, n = 0;
+    unsigned part = 0;        // objective: the partition
     // objective
     const rdamd_schedule_t *sched = nullptr;
     const double *subst = nullptr, *freqs = nullptr, *rates = nullptr, *weights = nullptr;
@@ -191,10 +224,12 @@ private:
     unsigned live = 0;
     bool busy = false;
     std::vector<request_t *> posted;
-    // the round's vector: [objective lnLs | flag | root lnLs | plain values]
+    // the round's vector: [partition 0's objective lnLs | its flag | partition 1's ... | root lnLs |
+    // plain values | guard]
     double *d_vec = nullptr, *h_in = nullptr, *h_res = nullptr;
     size_t cap = 0;
     hipEvent_t ev = nullptr;   // behind the round's collective and the copy of its sums
+    std::vector<hipEvent_t> part_ev;   // [p > 0]: behind partition p's batch (its pass) on its stream
     // the divergence guard (header comment): rounds of this group that carried a sum so far, and
     // the hash of the last one's results
     uint64_t seq = 0;
@@ -286,17 +321,38 @@ private:
     RDAMD_ROUND_TRY(hipHostMalloc((void **)&grp.h_res, grp.cap * sizeof(double), hipHostMallocDefault));
   }
 
+  // h_in -> d_vec over the ranges [lo, hi) in ascending order (adjacent ones in one copy), on `stream`
+  void upload(group_t &grp, const std::vector<std::pair<size_t, size_t>> &ranges, hipStream_t stream) {
+    std::vector<std::pair<size_t, size_t>> runs;
+    for (const auto &r : ranges) {
+      if (r.first >= r.second) continue;
+      if (!runs.empty() && runs.back().second == r.first) runs.back().second = r.second;
+      else runs.push_back(r);
+    }
+    for (const auto &r : runs)
+      RDAMD_ROUND_TRY(hipMemcpyAsync(grp.d_vec + r.first, grp.h_in + r.first, (r.second - r.first) * sizeof(double),
+                                     hipMemcpyHostToDevice, stream));
+  }
+
   // `lk` is held on entry and on return
   void run_round(unsigned g, std::vector<request_t *> &round, std::unique_lock<std::mutex> &lk) {
     group_t &grp = _g[g];
-    // (asked for every round: rdamd_partition_set_stream_priority re-creates the stream; a local --
+    const size_t P = _c.parts.size();
+    // (asked for every round: rdamd_partition_set_stream_priority re-creates the streams; locals --
     // the other group's round may be under way)
-    const hipStream_t stream = (hipStream_t)rdamd_partition_stream(_c.shared);
+    std::vector<hipStream_t> streams(P);
+    for (size_t p = 0; p < P; ++p) streams[p] = (hipStream_t)rdamd_partition_stream(_c.parts[p]);
+    const hipStream_t stream = streams[0];   // the collective's
     if (!grp.ev) RDAMD_ROUND_TRY(hipEventCreateWithFlags(&grp.ev, hipEventDisableTiming));
+    if (grp.part_ev.size() < P) grp.part_ev.resize(P, nullptr);
+    for (size_t p = 1; p < P; ++p)
+      if (!grp.part_ev[p]) RDAMD_ROUND_TRY(hipEventCreateWithFlags(&grp.part_ev[p], hipEventDisableTiming));
     std::sort(round.begin(), round.end(), [](const request_t *a, const request_t *b) { return a->worker < b->worker; });
     // ---- candidates, in worker order (under the lock: the counter is shared by the groups,
     // and the turn makes the order of the groups' rounds the same everywhere)
-    std::vector<request_t *> obj, root, red;
+    std::vector<std::vector<request_t *>> obj(P);   // [partition]
+    std::vector<request_t *> root, red;
+    bool any_obj = false;
     uint64_t comp = fnv(fnv(1469598103934665603ull, g), grp.seq);
     for (request_t *r : round) {
       comp = fnv(fnv(fnv(comp, r->worker), (unsigned)r->kind), r->n);
@@ -305,13 +361,17 @@ private:
           if (_next < _c.n_candidates) r->candidate = (long)_next++;
           else { r->candidate = -1; --grp.live; }
           break;
-        case OBJECTIVE: obj.push_back(r); break;
+        case OBJECTIVE:
+          if (P > 1) comp = fnv(comp, r->part);
+          obj[r->part].push_back(r);
+          any_obj = true;
+          break;
         case ROOT: root.push_back(r); break;
         case REDUCE: red.push_back(r); break;
       }
     }
     ++_stats.rounds;
-    if (obj.empty() && root.empty() && red.empty()) {
+    if (!any_obj && root.empty() && red.empty()) {
       pass_turn(g);
       return;
     }
@@ -324,36 +384,48 @@ private:
       t_mark = now;
     };
 
-    // ---- the round's vector
-    size_t m = 0, n_root = 0, n_red = 0;
-    for (request_t *r : obj) m += r->n;
+    // ---- the round's vector: every objective partition has its slice [its jobs' lnLs | its flag]
+    std::vector<size_t> m(P, 0), o_obj(P, 0);
+    size_t n_root = 0, n_red = 0, at_obj = 0;
+    for (size_t p = 0; p < P; ++p) {
+      for (request_t *r : obj[p]) m[p] += r->n;
+      o_obj[p] = at_obj;
+      at_obj += m[p] + 1;
+    }
     for (request_t *r : root) n_root += r->n;
     for (request_t *r : red) n_red += r->n;
-    const size_t o_flag = m, o_root = m + 1, o_red = o_root + n_root, o_guard = o_red + n_red, total = o_guard + GUARD_WORDS;
+    const size_t o_root = at_obj, o_red = o_root + n_root, o_guard = o_red + n_red, total = o_guard + GUARD_WORDS;
     ensure_vec(grp, total, stream);
     const uint64_t round_no = grp.seq++;   // (of this worker group, counting the rounds that carry a sum)
-    // what an objective batch in flight needs when the round fails after it was queued: its slot
-    // released and the partition's batch sequence advanced (parked schedule blocks wait for that)
-    struct batch_in_flight_t {
-      rdamd_partition_t *p; unsigned slot; bool device, armed = false;
-      ~batch_in_flight_t() {
-        if (!armed) return;
-        if (device) (void)rdamd_evaluate_batch_finish_device(p, slot);
-        else { std::vector<double> sink(n); (void)rdamd_evaluate_batch_wait(p, slot, sink.data()); }
+    // what the objective batches in flight need when the round fails after they were queued: their
+    // slots released and their partitions' batch sequences advanced (parked schedule blocks wait for that)
+    struct batches_in_flight_t {
+      unsigned slot = 0;
+      bool device = false;
+      std::vector<rdamd_partition_t *> parts;
+      std::vector<size_t> n;
+      ~batches_in_flight_t() {
+        for (size_t i = 0; i < parts.size(); ++i) {
+          if (device) (void)rdamd_evaluate_batch_finish_device(parts[i], slot);
+          else { std::vector<double> sink(n[i] + 1); (void)rdamd_evaluate_batch_wait(parts[i], slot, sink.data()); }
+        }
       }
-      size_t n = 0;
-    } in_flight{_c.shared, g, false};
+    } in_flight;
+    in_flight.slot = g;
     const bool two_phase = _c.device && _c.queue && _c.wait;
     const bool device_path = !_c.reduce || _c.device;   // (no reducer at all: the device path without a collective)
+    in_flight.device = device_path;
 
-    // ---- the objective jobs: one launch on the shared partition
-    if (m) {
-      const unsigned R = rdamd_partition_rate_cats(_c.shared);
-      const unsigned K = rdamd_partition_states(_c.shared), NP = K * K - K;
+    // ---- the objective jobs: one launch per partition that has any, each on its partition's stream
+    for (size_t p = 0; p < P; ++p) {
+      if (!m[p]) continue;
+      rdamd_partition_t *part = _c.parts[p];
+      const unsigned R = rdamd_partition_rate_cats(part);
+      const unsigned K = rdamd_partition_states(part), NP = K * K - K;
       std::vector<const rdamd_schedule_t *> scheds;
       std::vector<double> subst, freqs, rates, weights;
-      scheds.reserve(m);
-      for (request_t *r : obj) {
+      scheds.reserve(m[p]);
+      for (request_t *r : obj[p]) {
         scheds.insert(scheds.end(), r->n, r->sched);
         subst.insert(subst.end(), r->subst, r->subst + (size_t)r->n * NP);
         freqs.insert(freqs.end(), r->freqs, r->freqs + (size_t)r->n * K);
@@ -361,17 +433,22 @@ private:
         weights.insert(weights.end(), r->weights, r->weights + (size_t)r->n * R);
       }
       const int rc = device_path
-          ? rdamd_evaluate_batch_submit_device(_c.shared, g, (unsigned)m, scheds.data(), subst.data(), freqs.data(),
-                                               rates.data(), weights.data(), grp.d_vec)
-          : rdamd_evaluate_batch_submit(_c.shared, g, (unsigned)m, scheds.data(), subst.data(), freqs.data(),
+          ? rdamd_evaluate_batch_submit_device(part, g, (unsigned)m[p], scheds.data(), subst.data(), freqs.data(),
+                                               rates.data(), weights.data(), grp.d_vec + o_obj[p])
+          : rdamd_evaluate_batch_submit(part, g, (unsigned)m[p], scheds.data(), subst.data(), freqs.data(),
                                         rates.data(), weights.data());
       if (rc != RDAMD_SUCCESS) throw std::runtime_error(std::string("lock-step round: objective batch: ") + rdamd_errmsg());
-      in_flight.device = device_path; in_flight.n = m; in_flight.armed = true;
+      in_flight.parts.push_back(part);
+      in_flight.n.push_back(m[p]);
+      if (device_path && p > 0) {   // (the collective on partition 0's stream comes after this batch)
+        RDAMD_ROUND_TRY(hipEventRecord(grp.part_ev[p], streams[p]));
+        RDAMD_ROUND_TRY(_c.stream_wait_event(stream, grp.part_ev[p], 0));
+      }
     }
     lap(0);
     // ---- the root positions: one launch over the candidates' own partitions, beside it
     if (!root.empty()) {
-      constexpr unsigned P = RDAMD_ROOT_MAX_POSITIONS;
+      constexpr unsigned PP = RDAMD_ROOT_MAX_POSITIONS;
       std::vector<rdamd_partition_t *> parts;
       std::vector<rdamd_operation_t> ops;
       std::vector<const unsigned *> pidx;
@@ -381,10 +458,10 @@ private:
         for (unsigned i = 0; i < r->n_parts; ++i) {
           parts.push_back(r->parts[i]); ops.push_back(r->op); pidx.push_back(r->params_idx[i]);
           npos.push_back(r->n);
-          l1.insert(l1.end(), r->l1, r->l1 + P);
-          l2.insert(l2.end(), r->l2, r->l2 + P);
+          l1.insert(l1.end(), r->l1, r->l1 + PP);
+          l2.insert(l2.end(), r->l2, r->l2 + PP);
         }
-      std::vector<double> v(P * parts.size());
+      std::vector<double> v(PP * parts.size());
       if (rdamd_root_loglikelihood_fused_multi((unsigned)parts.size(), parts.data(), ops.data(), pidx.data(), l1.data(),
                                                l2.data(), npos.data(), v.data()) != RDAMD_SUCCESS)
         throw std::runtime_error(std::string("lock-step round: root step: ") + rdamd_errmsg());
@@ -392,7 +469,7 @@ private:
       for (request_t *r : root) {   // (a candidate's partitions summed in their order, as compute_lh_root does)
         for (unsigned a = 0; a < r->n; ++a) grp.h_in[at + a] = 0.0;
         for (unsigned i = 0; i < r->n_parts; ++i, ++item)
-          for (unsigned a = 0; a < r->n; ++a) grp.h_in[at + a] += v[P * item + a];
+          for (unsigned a = 0; a < r->n; ++a) grp.h_in[at + a] += v[PP * item + a];
         at += r->n;
       }
     }
@@ -426,28 +503,47 @@ private:
       }
       _group_size = (uint64_t)ranks;
     };
+    // releases every slot in flight (device: waits for what was queued), then reports the first failure
+    const auto finish_batches = [&]() {
+      std::vector<rdamd_partition_t *> parts;
+      parts.swap(in_flight.parts);
+      in_flight.n.clear();
+      std::string failed;
+      for (size_t i = 0; i < parts.size(); ++i)
+        if (rdamd_evaluate_batch_finish_device(parts[i], g) != RDAMD_SUCCESS && failed.empty()) failed = rdamd_errmsg();
+      if (!failed.empty()) throw std::runtime_error("lock-step round: objective batch: " + failed);
+    };
 
     lap(1);
     // ---- the sum over the site group
     double *res = grp.h_res;
-    bool need_redo_check = false;
     if (device_path) {
-      if (!m) grp.h_in[o_flag] = 0.0;
-      // (host-made values go up behind the batch; the front of the vector is the batch's)
-      const size_t lo = m ? o_root : 0;
-      if (total > lo)
-        RDAMD_ROUND_TRY(hipMemcpyAsync(grp.d_vec + lo, grp.h_in + lo, (total - lo) * sizeof(double), hipMemcpyHostToDevice, stream));
+      // (host-made values go up behind the batches: the flags of partitions without jobs, and
+      // everything from the root lnLs on)
+      std::vector<std::pair<size_t, size_t>> host_made;
+      for (size_t p = 0; p < P; ++p)
+        if (!m[p]) {
+          grp.h_in[o_obj[p]] = 0.0;
+          host_made.emplace_back(o_obj[p], o_obj[p] + 1);
+        }
+      host_made.emplace_back(o_root, total);
+      upload(grp, host_made, stream);
       queue_sum(grp.d_vec, total, two_phase, stream);
       RDAMD_ROUND_TRY(hipMemcpyAsync(grp.h_res, grp.d_vec, total * sizeof(double), hipMemcpyDeviceToHost, stream));
       RDAMD_ROUND_TRY(hipEventRecord(grp.ev, stream));
-      need_redo_check = m > 0;
     } else {
       // host reducer (ranks that share a device): the batch's own wait runs the second pass where
       // this rank needs it -- its values are final before they are summed
-      in_flight.armed = false;   // (the wait releases the slot whether it succeeds or not)
-      if (m && rdamd_evaluate_batch_wait(_c.shared, g, grp.h_in) != RDAMD_SUCCESS)
-        throw std::runtime_error(std::string("lock-step round: objective batch: ") + rdamd_errmsg());
-      grp.h_in[o_flag] = 0.0;
+      std::vector<rdamd_partition_t *> parts;   // (the wait releases the slot whether it succeeds or not)
+      parts.swap(in_flight.parts);
+      in_flight.n.clear();
+      std::string failed;
+      for (size_t p = 0, i = 0; p < P; ++p) {
+        if (m[p] && rdamd_evaluate_batch_wait(parts[i++], g, grp.h_in + o_obj[p]) != RDAMD_SUCCESS && failed.empty())
+          failed = rdamd_errmsg();
+        grp.h_in[o_obj[p] + m[p]] = 0.0;
+      }
+      if (!failed.empty()) throw std::runtime_error("lock-step round: objective batch: " + failed);
       if (_c.reduce(grp.h_in, (unsigned)total, nullptr, _c.user) != RDAMD_SUCCESS)
         throw std::runtime_error(std::string("lock-step round: site-group reduction failed: ") + rdamd_errmsg());
       res = grp.h_in;
@@ -458,7 +554,10 @@ private:
     // ---- queued: the other group may go
     lk.lock();
     ++_stats.collectives;
-    if (m) { ++_stats.obj_launches; _stats.obj_jobs += m; }
+    _stats.part_launches.resize(P, 0);
+    _stats.part_redo_launches.resize(P, 0);
+    for (size_t p = 0; p < P; ++p)
+      if (m[p]) { ++_stats.obj_launches; _stats.obj_jobs += m[p]; ++_stats.part_launches[p]; }
     if (!root.empty()) { ++_stats.root_launches; _stats.root_steps += root.size(); }
     pass_turn(g);
     _cv.notify_all();
@@ -468,34 +567,56 @@ private:
     if (device_path) {
       wait_round(grp, two_phase);
       check_guard(grp.h_res);
-      if (need_redo_check && grp.h_res[o_flag] != 0.0) {
-        // some rank's batch wants its second pass: every rank repeats the collective -- in the
-        // group's turn, so that it sits at the same place of the stream's order everywhere
+      std::vector<bool> redo(P, false);
+      size_t n_redo = 0;
+      for (size_t p = 0; p < P; ++p)
+        if (m[p] && grp.h_res[o_obj[p] + m[p]] != 0.0) { redo[p] = true; ++n_redo; }
+      if (n_redo) {
+        // some rank's batch of these partitions wants its second pass: every rank repeats the
+        // collective -- in the group's turn, so that it sits at the same place of the stream's order
+        // everywhere -- and only the flagged partitions launch again
         lk.lock();
         while (!my_turn(g) && _error.empty()) _cv.wait(lk);
         if (!_error.empty()) throw std::runtime_error(_error);
         ++_stats.redos; ++_stats.collectives;
+        for (size_t p = 0; p < P; ++p) _stats.part_redo_launches[p] += redo[p] ? 1 : 0;
         lk.unlock();   // (the turn stays here: the other group passes it only when it has it)
-        if (rdamd_evaluate_batch_redo_device(_c.shared, g, grp.d_vec) != RDAMD_SUCCESS)
-          throw std::runtime_error(std::string("lock-step round: second pass: ") + rdamd_errmsg());
-        if (total > o_root)
-          RDAMD_ROUND_TRY(hipMemcpyAsync(grp.d_vec + o_root, grp.h_in + o_root, (total - o_root) * sizeof(double), hipMemcpyHostToDevice, stream));
+        // the other partitions' slices are final: they keep the first sums and carry zeros through the repeat
+        const std::vector<double> first(grp.h_res, grp.h_res + o_root);
+        std::vector<std::pair<size_t, size_t>> host_made;
+        for (size_t p = 0; p < P; ++p) {
+          if (redo[p]) {
+            if (rdamd_evaluate_batch_redo_device(_c.parts[p], g, grp.d_vec + o_obj[p]) != RDAMD_SUCCESS)
+              throw std::runtime_error(std::string("lock-step round: second pass: ") + rdamd_errmsg());
+            if (p > 0) {
+              RDAMD_ROUND_TRY(hipEventRecord(grp.part_ev[p], streams[p]));
+              RDAMD_ROUND_TRY(_c.stream_wait_event(stream, grp.part_ev[p], 0));
+            }
+          } else {
+            std::fill(grp.h_in + o_obj[p], grp.h_in + o_obj[p] + m[p] + 1, 0.0);
+            host_made.emplace_back(o_obj[p], o_obj[p] + m[p] + 1);
+          }
+        }
+        host_made.emplace_back(o_root, total);
+        upload(grp, host_made, stream);
         queue_sum(grp.d_vec, total, two_phase, stream);
         RDAMD_ROUND_TRY(hipMemcpyAsync(grp.h_res, grp.d_vec, total * sizeof(double), hipMemcpyDeviceToHost, stream));
         RDAMD_ROUND_TRY(hipEventRecord(grp.ev, stream));
         wait_round(grp, two_phase);
         check_guard(grp.h_res);
+        for (size_t p = 0; p < P; ++p)
+          if (!redo[p]) std::copy(first.begin() + o_obj[p], first.begin() + o_obj[p] + m[p] + 1, grp.h_res + o_obj[p]);
       }
-      in_flight.armed = false;
-      if (m && rdamd_evaluate_batch_finish_device(_c.shared, g) != RDAMD_SUCCESS)
-        throw std::runtime_error(std::string("lock-step round: objective batch: ") + rdamd_errmsg());
+      finish_batches();
     }
     // (what the NEXT round of this group vouches for: the bits every candidate is about to see)
     grp.prev_word = word40(fnv(1469598103934665603ull, res, o_guard * sizeof(double)));
     {
-      size_t at = 0;
-      for (request_t *r : obj) { std::copy(res + at, res + at + r->n, r->out); at += r->n; }
-      at = o_root;
+      for (size_t p = 0; p < P; ++p) {
+        size_t at = o_obj[p];
+        for (request_t *r : obj[p]) { std::copy(res + at, res + at + r->n, r->out); at += r->n; }
+      }
+      size_t at = o_root;
       for (request_t *r : root) { std::copy(res + at, res + at + r->n, r->out); at += r->n; }
       at = o_red;
       for (request_t *r : red) { std::copy(res + at, res + at + r->n, r->out); at += r->n; }
@@ -506,7 +627,7 @@ private:
     _stats.group_size = _group_size.load();
   }
 
-  // the site group's sum over d[0 .. n), queued on the shared partition's stream
+  // the site group's sum over d[0 .. n), queued on partition 0's stream
   void queue_sum(double *d, size_t n, bool two_phase, hipStream_t stream) {
     if (!_c.reduce && !_c.queue) return;   // a one-rank group
     const int rc = two_phase ? _c.queue(d, (unsigned)n, (void *)stream, _c.async_user)

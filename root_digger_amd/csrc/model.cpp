@@ -353,6 +353,21 @@ double model_t::compute_lh(const root_location_t &root_location) {
   return reduce_value(lh);
 }
 
+// compute_lh's per-partition terms of THIS model's own columns, not summed over a site group
+std::vector<double> model_t::partition_lh(const root_location_t &root_location) {
+  auto sched = _tree.generate_operations(root_location);
+  const auto &ops = std::get<0>(sched);
+  update_pmatrices(std::get<1>(sched), std::get<2>(sched));
+  std::vector<double> out;
+  for (size_t i = 0; i < _partitions.size(); ++i) {
+    rdamd_update_clvs(_partitions[i], ops.data(), (unsigned)ops.size());
+    if (rdamd_errno()) fail("update_clvs");
+    out.push_back(rdamd_compute_root_loglikelihood(_partitions[i], _tree.root_clv_index(), _tree.root_scaler_index(),
+                                                   _param_indicies[i].data(), nullptr));
+  }
+  return out;
+}
+
 // compute_lh for the searches, between optimize_params and the root-only steps: the same
 // value for the caller's convergence test, but only what those steps read is left behind --
 // the CLVs and scalers of the root's two children (rdamd_evaluate_root_children: one job of
@@ -970,8 +985,8 @@ double model_t::bfgs_params(model_params_t &initial, size_t pi, bfgs_target what
       std::copy(_rate_weights[pi].begin(), _rate_weights[pi].end(), weights.begin() + j * R);
     }
     if (_conductor) {   // meets the other candidates' requests in the round's launch; summed over the group
-      _conductor->objective(_worker, (unsigned)m, sched, subst.data(), freqs.data(), rates.data(), weights.data(),
-                            out.data());
+      _conductor->objective(_worker, (unsigned)pi, (unsigned)m, sched, subst.data(), freqs.data(), rates.data(),
+                            weights.data(), out.data());
     } else if (combiner) {   // meets the other candidates' requests in one launch
       combiner->evaluate((unsigned)m, sched, subst.data(), freqs.data(), rates.data(),
                           weights.data(), out.data());
@@ -1077,8 +1092,8 @@ void model_t::optimize_params(std::vector<partition_parameters_t> &params,
   if (!_combiners.empty() && _reduce)
     throw std::runtime_error("optimize_params: the candidates of a site-sharded model meet in rounds "
                              "(lockstep_conductor.hpp), not in batch combiners");
-  if (_conductor && _partitions.size() != 1)
-    throw std::runtime_error("optimize_params: lock step in rounds takes single-partition models");
+  if (_conductor && _conductor->n_parts() != _partitions.size())
+    throw std::runtime_error("optimize_params: lock step in rounds needs one objective partition per model partition");
   for (size_t i = 0; i < _partitions.size(); ++i) {
     // The batched objective runs on the fused evaluators: 4-state and binary data, and 20
     // states with up to eight rate categories (the 381 finite-difference evaluations of a
@@ -1099,7 +1114,7 @@ void model_t::optimize_params(std::vector<partition_parameters_t> &params,
       else rdamd_schedule_destroy(s);
     };
     rdamd_schedule_t *sched =
-        _conductor ? rdamd_schedule_create(_conductor->shared(), std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(),
+        _conductor ? rdamd_schedule_create(_conductor->shared(i), std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(),
                                            std::get<1>(sc).data(), std::get<2>(sc).data(),
                                            (unsigned)std::get<1>(sc).size()) :
         combiner ? combiner->schedule_create(std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(),

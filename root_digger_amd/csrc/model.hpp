@@ -110,6 +110,8 @@ public:
 
   // ---- likelihood facade (hot-path callers) -------------------------------
   double compute_lh(const root_location_t &root_location);      // src/model.cpp:384-413
+  // its per-partition terms on this model's own columns (no site-group sum): out[p], file order
+  std::vector<double> partition_lh(const root_location_t &root_location);
   // the same value; only the root's two children are left materialised (model.cpp)
   double compute_lh_for_root_steps(const root_location_t &root_location);
   void set_root_children_only(bool on) { _children_only = on; }

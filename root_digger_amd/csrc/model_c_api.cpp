@@ -43,6 +43,7 @@ struct rdamd_model {
   unsigned lockstep_groups = 0;   // 0: the library's choice; 1: one group, blocking launches (rdamd_model_set_lockstep_groups)
   uint64_t lockstep_stats[4] = {0, 0, 0, 0};   // of the last lock-stepped search (rdamd_model_lockstep_stats)
   uint64_t round_stats[3] = {0, 0, 0};         // ... in rounds: rounds, collectives, second-pass redos
+  std::vector<uint64_t> round_part_stats;      // ... per objective partition: launches, second-pass launches
   double round_seconds[4] = {0, 0, 0, 0};      // ... and the host time of the rounds' phases
   struct async_reducer_t { rdamd_lnl_reducer_t queue; void *user; };   // rdamd_model_set_lnl_reducer_async
   std::unique_ptr<async_reducer_t> async_reducer;
@@ -249,6 +250,80 @@ rdamd_model_t *rdamd_model_create_partitioned(const rdamd_tree_t *tree, const ch
     if (n_partitions) *n_partitions = (unsigned)(1 + m->more_msas.size());
     return m;
   })
+}
+
+// One rank's block of the partitioned model: every partition's own columns (its ranges, in file
+// order) are cut into n_blocks contiguous blocks by the chunking of src/model.cpp:1899-1907 --
+// the rule rdamd_model_create_from_file_block applies to the whole alignment -- and this rank keeps
+// block `block` of each, compressed on its own.
+rdamd_model_t *rdamd_model_create_partitioned_block(const rdamd_tree_t *tree, const char *msa_filename,
+                                                    const char *partition_filename, unsigned int states,
+                                                    const uint64_t *map, uint64_t seed, int early_stop,
+                                                    unsigned int block, unsigned int n_blocks,
+                                                    unsigned int *n_partitions, unsigned int *patterns,
+                                                    unsigned int *columns) {
+  GUARD(nullptr, {
+    if (n_blocks < 1 || block >= n_blocks) throw std::invalid_argument("site block index out of range");
+    auto *m = new rdamd_model();
+    m->seed = seed; m->early_stop = early_stop != 0;
+    try {
+      const rdamd::msa_t whole = rdamd::msa_t::from_file(msa_filename, map, states, false);
+      const auto infos = rdamd::parse_partition_file(partition_filename);
+      if (infos.empty()) throw std::runtime_error("The partition file holds no partitions");
+      const auto full = rdamd::partition_msa(whole, infos, false);
+      std::vector<rdamd::msa_t> msas;
+      for (size_t p = 0; p < full.size(); ++p) {
+        const size_t len = full[p].length(), size = len / n_blocks, mod = len % n_blocks;
+        if (len < n_blocks)
+          throw std::invalid_argument("Partition '" + infos[p].partition_name + "' has " + std::to_string(len) +
+                                      " columns, fewer than the " + std::to_string(n_blocks) + " site blocks");
+        const size_t lo = size * block + std::min<size_t>(mod, block);
+        const size_t hi = size * (block + 1) + std::min<size_t>(mod, block + 1);
+        msas.push_back(full[p].columns(lo, hi));
+        msas.back().compress();
+        if (columns) columns[p] = (unsigned)len;
+      }
+      for (const auto &pi : infos) {
+        rdamd::ratehet_opts_t rc = pi.model.ratehet_opts;
+        if (rc.rate_cats == 0) rc.rate_cats = 1;
+        m->ratehets.push_back(rc);
+      }
+      for (const auto &x : msas)
+        if (!x.constiency_check(rdamd_tree_cpp(tree).label_set()))
+          throw std::invalid_argument("Taxa on the tree and in the MSA are inconsistient");
+      m->rate_cats = (unsigned)m->ratehets[0].rate_cats;
+      m->msa = msas[0];
+      m->more_msas.assign(msas.begin() + 1, msas.end());
+      m->model = new rdamd::model_t(rdamd_tree_cpp(tree), msas, m->ratehets, false, seed, early_stop != 0);
+      if (patterns)
+        for (size_t p = 0; p < msas.size(); ++p) patterns[p] = (unsigned)msas[p].length();
+    } catch (...) {
+      delete m;
+      throw;
+    }
+    if (n_partitions) *n_partitions = (unsigned)(1 + m->more_msas.size());
+    return m;
+  })
+}
+int rdamd_model_partition_lnls(rdamd_model_t *m, const rdamd_root_location_t *rl, double *out) {
+  GUARD(RDAMD_FAILURE, {
+    const auto v = m->model->partition_lh(to_cpp(rl));
+    std::copy(v.begin(), v.end(), out);
+    return RDAMD_SUCCESS;
+  })
+}
+int rdamd_model_partition_frequencies(rdamd_model_t *m, unsigned int p, double *out) {
+  GUARD(RDAMD_FAILURE, {
+    if (p >= m->model->partition_count()) throw std::invalid_argument("partition index out of range");
+    rdamd_partition_t *part = m->model->partition(p);
+    const double *f = rdamd_partition_frequencies(part, 0);
+    std::copy(f, f + rdamd_partition_states(part), out);
+    return RDAMD_SUCCESS;
+  })
+}
+unsigned long long rdamd_model_partition_second_passes(const rdamd_model_t *m, unsigned int p) {
+  if (p >= m->model->partition_count()) return 0;
+  return rdamd_evaluate_second_passes(m->model->partition(p));
 }
 
 namespace {
@@ -497,13 +572,11 @@ struct shared_priority_t {
 // Lock step in deterministic rounds (lockstep_conductor.hpp): what a site-sharded model's
 // lock-stepped search is -- every rank of the site group runs this with the same candidates and
 // forms the same rounds, one collective each.  Worker w is a host thread with a model replica
-// (sparse: the root's children only); the objective partition is m's own.
+// (sparse: the root's children only); the objective partitions are m's own, one per model partition.
 static int search_in_rounds(rdamd_model_t *m, unsigned int workers, double atol, double pgtol, double brtol,
                             double factor, uint64_t *root_id, double *llh, double *alpha,
                             unsigned int *n_results, rdamd_root_location_t *best_rl, double *best_llh) {
   GUARD(RDAMD_FAILURE, {
-    if (m->model->partition_count() != 1)
-      throw std::runtime_error("lock step in rounds takes single-partition models");
     const std::vector<size_t> todo = m->model->assigned_indicies();
     if (workers < 1) workers = 1;
     workers = (unsigned)std::min<size_t>(workers, std::max<size_t>(todo.size(), 1));
@@ -545,7 +618,8 @@ static int search_in_rounds(rdamd_model_t *m, unsigned int workers, double atol,
     }
     shared_priority_t shared_priority(m, true);
     rdamd::conductor_t::config_t cfg;
-    cfg.shared = m->model->partition(0);
+    for (size_t pi = 0; pi < m->model->partition_count(); ++pi) cfg.parts.push_back(m->model->partition(pi));
+    cfg.stream_wait_event = hipStreamWaitEvent;
     cfg.n_workers = workers;
     // One worker group or two alternating ones (rdamd_model_set_lockstep_groups)?  Two hide the
     // hosts' steps behind the other group's launch; one makes every launch twice as large and
@@ -610,6 +684,11 @@ static int search_in_rounds(rdamd_model_t *m, unsigned int workers, double atol,
     m->lockstep_stats[2] = st.root_launches; m->lockstep_stats[3] = st.root_steps;
     m->round_stats[0] = st.rounds; m->round_stats[1] = st.collectives; m->round_stats[2] = st.redos;
     for (int k = 0; k < 4; ++k) m->round_seconds[k] = st.seconds[k];
+    m->round_part_stats.assign(2 * m->model->partition_count(), 0);
+    for (size_t p = 0; p < st.part_launches.size() && p < m->model->partition_count(); ++p) {
+      m->round_part_stats[2 * p] = st.part_launches[p];
+      m->round_part_stats[2 * p + 1] = st.part_redo_launches[p];
+    }
     if (!first_error.empty()) throw std::runtime_error(first_error);
     std::sort(results.begin(), results.end(),
               [](const rdamd::rd_result_t &a, const rdamd::rd_result_t &b) { return a.root_id < b.root_id; });
@@ -802,6 +881,15 @@ void rdamd_model_round_seconds(const rdamd_model_t *m, double out[4]) {
 void rdamd_model_round_stats(const rdamd_model_t *m, uint64_t out[4]) {
   for (int i = 0; i < 3; ++i) out[i] = m->round_stats[i];
   out[3] = m->model->collectives();
+}
+int rdamd_model_round_partition_stats(const rdamd_model_t *m, unsigned int p, uint64_t out[2]) {
+  out[0] = out[1] = 0;
+  if (p >= m->model->partition_count()) return RDAMD_FAILURE;
+  if (2 * p + 1 < m->round_part_stats.size()) {
+    out[0] = m->round_part_stats[2 * p];
+    out[1] = m->round_part_stats[2 * p + 1];
+  }
+  return RDAMD_SUCCESS;
 }
 void rdamd_model_counters(const rdamd_model_t *m, uint64_t out[6]) {
   const auto c = m->model->counters();

@@ -16,7 +16,9 @@
 // ncclAllGather + a sum in rank order, identical bits on every rank by
 // construction; --site-reduce rccl-allreduce: one ncclAllReduce), or through the
 // host with --site-reduce host (ranks that share one GPU).  G = WORLD_SIZE is BASELINE config c4's layout (site blocks
-// only), 1 < G < WORLD_SIZE config c5's 2-D grid.
+// only), 1 < G < WORLD_SIZE config c5's 2-D grid.  With --partition, each member holds block b of
+// EVERY partition's own columns (rdamd_model_create_partitioned_block); every partition keeps its
+// own parameters, as in the reference's partitioned runs.
 //
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <chrono>
@@ -176,7 +178,6 @@ static int run(int argc, char **argv) {
   const int G = o.site_shards;
   if (G < 1 || world % G) die("--site-shards must divide the number of ranks");
   const int cgroups = world / G, cgroup = rank / G, srank = rank % G;
-  if (G > 1 && !o.partition.empty()) die("--site-shards: partition files are not supported");
   std::unique_ptr<site_group_t> host_group;
   rdamd_comm_t *comm = nullptr;
   if (G > 1 && o.site_reduce_host) {
@@ -251,11 +252,6 @@ static int run(int argc, char **argv) {
       o.root_ratio = h.root_ratio; o.strategy = h.initial_root_strategy; o.early_stop = h.early_stop;
     }
   }
-  // (again, now that a resumed run's saved options are in: a partition file that comes from
-  // the checkpoint would build the whole partitioned model on every member of a site group
-  // while the group's reduction is installed, and every lnL would be counted G times)
-  if (G > 1 && !o.partition.empty())
-    die("--site-shards: the checkpoint belongs to a run with a partition file, which a site group does not support");
   if (o.msa.empty()) { std::puts("No MSA was given, please supply an MSA"); usage(); return 1; }
   if (o.tree.empty()) { std::puts("No tree was given, please supply an tree"); usage(); return 1; }
 
@@ -272,7 +268,26 @@ static int run(int argc, char **argv) {
     o.rate_cats = mi.ratehet.rate_cats ? (unsigned)mi.ratehet.rate_cats : 1u;
   }
   rdamd_model_t *model = nullptr;
-  if (!o.partition.empty()) {
+  // (the partition file may come from a resumed run's checkpoint: it is known only here.  A site
+  // group's member builds its own block of every partition -- the whole partitioned model on every
+  // member would count every lnL G times once the group's reduction is installed)
+  if (!o.partition.empty() && G > 1) {
+    // (room for one entry per line: at least one per partition)
+    size_t lines = 1;
+    {
+      std::ifstream pf(o.partition);
+      for (std::string line; std::getline(pf, line);) ++lines;
+    }
+    unsigned n_parts = 0;
+    std::vector<unsigned> patterns(lines), columns(lines);
+    model = rdamd_model_create_partitioned_block(tree, o.msa.c_str(), o.partition.c_str(), o.states, map, o.seed,
+                                                 early_stop, (unsigned)srank, (unsigned)G, &n_parts, patterns.data(),
+                                                 columns.data());
+    if (model && !o.silent)
+      for (unsigned p = 0; p < n_parts; ++p)
+        std::printf("[rank %d] candidate group %d/%d, partition %u, site block %d/%d: %u patterns of %u columns\n",
+                    rank, cgroup, cgroups, p, srank, G, patterns[p], columns[p]);
+  } else if (!o.partition.empty()) {
     unsigned n_parts = 0;
     model = rdamd_model_create_partitioned(tree, o.msa.c_str(), o.partition.c_str(), o.states, map,
                                            o.seed, early_stop, &n_parts);

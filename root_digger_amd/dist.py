@@ -30,6 +30,33 @@ def site_block(n_sites, rank, num_tasks):
     return chunk(n_sites, rank, num_tasks)
 
 
+def partition_site_blocks(partitions, block, n_blocks):
+    """Column ranges of one rank's block of a partitioned alignment (the split
+    rdamd_model_create_partitioned_block makes).  `partitions`: per partition, its
+    1-based inclusive column ranges as a partition file lists them.  Each
+    partition's OWN columns -- its ranges concatenated in order -- are chunked
+    into `n_blocks` contiguous blocks (site_block); returns, per partition, the
+    1-based inclusive ranges of the original alignment that block `block` holds.
+    A partition with fewer columns than `n_blocks` is refused, by name or index."""
+    if not 0 <= block < n_blocks:
+        raise ValueError("site block index out of range")
+    out = []
+    for i, ranges in enumerate(partitions):
+        cols = [c for lo, hi in ranges for c in range(lo, hi + 1)]
+        if len(cols) < n_blocks:
+            raise ValueError("partition %d has %d columns, fewer than the %d site blocks"
+                             % (i, len(cols), n_blocks))
+        beg, end = site_block(len(cols), block, n_blocks)
+        mine, run = cols[beg:end], []
+        for c in mine:
+            if run and run[-1][1] + 1 == c:
+                run[-1][1] = c
+            else:
+                run.append([c, c])
+        out.append([tuple(r) for r in run])
+    return out
+
+
 def grid_2d(world_size, site_groups):
     """BASELINE config c5: candidate groups x site shards.  Returns
     (candidate_groups, site_groups) with candidate_groups*site_groups == world."""
