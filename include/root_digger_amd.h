@@ -858,6 +858,78 @@ int rdamd_model_partition_frequencies(rdamd_model_t *m, unsigned int p, double *
  * search in rounds): batches that needed the evaluator's second pass so far */
 unsigned long long rdamd_model_partition_second_passes(const rdamd_model_t *m, unsigned int p);
 
+/* ------------------------------------------------------------------------
+ * Site log-likelihoods of candidate roots and their RELL bootstrap
+ * (Kishino, Miyata & Hasegawa 1990; not in the reference, which always passes
+ * persite_lnl = NULL).
+ * ---------------------------------------------------------------------- */
+/* Site patterns of the model, all partitions concatenated in partition order: P_total patterns
+ * standing for N_columns alignment columns.  weights[P_total]: pattern multiplicities;
+ * pattern_of[N_columns]: the pattern every column was compressed into -- per partition in the
+ * partition's own column order (the alignment's for an unpartitioned model, the partition file's
+ * ranges back to back otherwise), partition after partition, as indices into the concatenated
+ * pattern list.  A model made from caller-supplied patterns (rdamd_model_create) has no columns of
+ * its own: pattern p then owns weights[p] consecutive columns.  Any pointer may be NULL.
+ * Refused (error 61) for a model that sums over a site group (rdamd_model_set_lnl_reducer). */
+int rdamd_model_site_patterns(rdamd_model_t *m, unsigned int *P_total, unsigned int *N_columns,
+                              unsigned int *weights, unsigned int *pattern_of);
+/* The same for an alignment FILE, as a model made from it holds it (host only, no device):
+ * n_lines = 0: the whole alignment, compressed; otherwise the partitions the given partition-file
+ * lines describe, each compressed on its own, concatenated.  sequences (optional):
+ * [n_taxa][P_total] characters, the compressed alignment itself, taxa in file order (characters
+ * with the same state set are merged into one, as the compression does).  Call once with the
+ * buffers NULL for the sizes. */
+int rdamd_msa_pattern_probe(const char *msa_filename, const uint64_t *map, unsigned int n_lines,
+                            const char *const *lines, unsigned int *n_taxa, unsigned int *P_total,
+                            unsigned int *N_columns, unsigned int *weights, unsigned int *pattern_of,
+                            char *sequences);
+/* out[n][P_total]: for each of the n root locations (rls[i].brlen_ratio is the root's position on
+ * its branch) the UNWEIGHTED log-likelihood of every site pattern, partitions concatenated in
+ * partition order.  Root i is evaluated with its own parameters, given in the checkpoint's layout
+ * (what rdamd_checkpoint_result_params returns): counts[n][n_partitions][4] = lengths of
+ * subst_rates, freqs, gamma_alpha, gamma_weights, `values` = all those vectors back to back;
+ * applied as the searches apply a candidate's parameters (frequencies are normalised).
+ * counts = values = NULL: the model's current parameters for every root.
+ * One materialising traversal and rdamd_compute_root_loglikelihood(..., persite_lnl) per root
+ * and partition: any state count the model accepts.  The model's parameters, its rooting and the
+ * conditional likelihoods of that rooting are as before when the call returns.
+ * Refused (error 61) for a model that sums over a site group. */
+int rdamd_model_site_lnls(rdamd_model_t *m, unsigned int n, const rdamd_root_location_t *rls,
+                          const uint64_t *counts, const double *values, double *out_patterns);
+
+/* Column that draw d (0 <= d < N) of bootstrap replicate b resamples, N < 2^32 columns.
+ * Stateless and counter-based (all arithmetic mod 2^64):
+ *   sm(x):  x += 0x9E3779B97F4A7C15; z = x;
+ *           z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *           return z ^ (z >> 31)
+ *   key = sm(seed ^ sm(b));  u = sm(key + d);  column = ((u >> 32) * N) >> 32
+ * Replicate b does not depend on the number of replicates, and a process that holds a block of
+ * the columns can draw the same GLOBAL columns.  Plain host code: no device needed. */
+uint32_t rdamd_rell_column(uint64_t seed, uint64_t b, uint64_t d, uint64_t N);
+/* RELL bootstrap of n_rows rows (candidate roots) of site log-likelihoods, on the current device.
+ * site_lnl[n_rows][n_patterns] (host) holds UNWEIGHTED pattern lnLs; pattern p stands for
+ * pattern_weights[p] consecutive columns of the N = sum(pattern_weights) < 2^32 columns, so
+ * col2pat[c] is the pattern whose column range holds c (a pattern of weight 0 is never drawn).
+ *   sums[b][i] = sum over d in [0, N) of site_lnl[i][col2pat[rdamd_rell_column(seed, b, d, N)]]
+ *   bp[i]      = (replicates whose largest sum is row i's; ties go to the LOWEST i) / n_replicates
+ *   elw[i]     = mean over b of exp(sums[b][i] - m_b) / sum_j exp(sums[b][j] - m_b),
+ *                m_b = the replicate's largest sum (expected likelihood weight, Strimmer & Rambaut 2002)
+ * The additions of one (b, i) are made in ONE order that depends on N alone -- not on the row, on
+ * n_rows, on n_replicates or on the launch shape: draw d goes to partial sum d mod 8; each partial
+ * sum adds its draws by increasing d; the eight are combined as ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)).
+ * Equal rows therefore get equal bits, the first B1 replicates of a longer run are the B1-replicate
+ * run's, and a repeated call returns the same bits.
+ * Host pointers in and out: bp[n_rows], elw[n_rows], sums[n_replicates][n_rows] (may be NULL).
+ * The call owns its device memory and leaves no state behind.  Error 62: n_rows, n_patterns or
+ * n_replicates is 0, N is 0 or >= 2^32, or a pointer is missing -- nothing is launched. */
+int rdamd_rell_bootstrap(const double *site_lnl, unsigned int n_rows, unsigned int n_patterns,
+                         const unsigned int *pattern_weights, unsigned int n_replicates,
+                         uint64_t seed, double *bp, double *elw, double *sums);
+/* device time of the resampling kernel alone in this thread's last rdamd_rell_bootstrap call,
+ * milliseconds between two HIP events (0 after a failed call); for measurements */
+double rdamd_rell_last_resample_ms(void);
+
 /* RCCL communicator of one site group (librccl is loaded on first use; the
  * library has no link-time dependency on it).  Rank 0 of the group calls
  * rdamd_comm_unique_id and hands the 128 bytes to the others by any means

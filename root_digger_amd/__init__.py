@@ -41,6 +41,10 @@ from .api import (  # noqa: F401
     rank_order_sum,
     COMM_SUM_GATHER,
     COMM_SUM_ALLREDUCE,
+    msa_pattern_probe,
+    rell_column,
+    rell_bootstrap,
+    rell_last_resample_ms,
 )
 
 __all__ = [
@@ -51,4 +55,5 @@ __all__ = [
     "ATTRIB_SITE_REPEATS", "ATTRIB_NONREV", "ATTRIB_SPARSE_CLVS",
     "device_count", "hip_runtime_path", "mapped_hip_runtimes", "set_device", "device_memory", "msa_probe",
     "rank_order_sum", "COMM_SUM_GATHER", "COMM_SUM_ALLREDUCE",
+    "msa_pattern_probe", "rell_column", "rell_bootstrap", "rell_last_resample_ms",
 ]

@@ -285,6 +285,15 @@ COMM_SUM_GATHER, COMM_SUM_ALLREDUCE = 0, 1
 _sig("rdamd_partition_footprint", C.c_uint64, _u, _u, _u, _u, _u, _u, _u)
 _sig("rdamd_model_max_replicas", _u, _vp, _u, C.POINTER(C.c_uint64))
 
+# site log-likelihoods of candidate roots and their RELL bootstrap
+_sig("rdamd_model_site_patterns", C.c_int, _vp, _pu, _pu, _pu, _pu)
+_sig("rdamd_msa_pattern_probe", C.c_int, C.c_char_p, C.c_void_p, _u, C.POINTER(C.c_char_p), _pu, _pu, _pu,
+     _pu, _pu, C.c_char_p)
+_sig("rdamd_model_site_lnls", C.c_int, _vp, _u, _prl, _pu64, _pd, _pd)
+_sig("rdamd_rell_column", C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64)
+_sig("rdamd_rell_bootstrap", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd)
+_sig("rdamd_rell_last_resample_ms", C.c_double)
+
 _libc = C.CDLL(None)
 _libc.free.argtypes = [_vp]
 _libc.free.restype = None
@@ -966,6 +975,52 @@ def msa_partition_probe(path, lines, cmap=None, compress=True):
     return [(int(a), int(b)) for a, b in zip(n, w)]
 
 
+def msa_pattern_probe(path, lines=(), cmap=None):
+    """The alignment file as a model holds it (host only): the whole alignment compressed, or the
+    partitions the partition-file `lines` describe, each compressed on its own and concatenated.
+    -> (sequences: one compressed string per taxon in file order, weights, pattern_of)."""
+    arr = (C.c_char_p * max(len(lines), 1))(*[l.encode() for l in lines])
+    t, n, c = C.c_uint(0), C.c_uint(0), C.c_uint(0)
+    args = (os.fsencode(path), cmap if cmap is not None else MAP_NT, len(lines), arr)
+    if lib.rdamd_msa_pattern_probe(*args, C.byref(t), C.byref(n), C.byref(c), None, None, None) != 1:
+        _fail("msa_pattern_probe")
+    w = np.zeros(n.value, dtype=np.uint32)
+    po = np.zeros(c.value, dtype=np.uint32)
+    buf = C.create_string_buffer(t.value * n.value + 1)
+    if lib.rdamd_msa_pattern_probe(*args, None, None, None, _uptr(w), _uptr(po), buf) != 1:
+        _fail("msa_pattern_probe")
+    raw = buf.raw
+    return [raw[i * n.value:(i + 1) * n.value].decode() for i in range(t.value)], w, po
+
+
+def rell_column(seed, b, d, n_columns):
+    """column that draw d of bootstrap replicate b resamples (rdamd_rell_column; host only)"""
+    return int(lib.rdamd_rell_column(seed, b, d, n_columns))
+
+
+def rell_bootstrap(site_lnl, pattern_weights, n_replicates, seed=1, return_sums=False):
+    """RELL bootstrap of the rows of site_lnl[rows][patterns] (unweighted pattern lnLs) on the
+    current device (rdamd_rell_bootstrap) -> (bp, elw) or (bp, elw, sums[n_replicates][rows])."""
+    a = np.ascontiguousarray(site_lnl, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("site_lnl is [rows][patterns]")
+    w = np.ascontiguousarray(pattern_weights, dtype=np.uint32)
+    if w.shape != (a.shape[1],):
+        raise ValueError("one weight per pattern is required")
+    rows = a.shape[0]
+    bp, elw = np.zeros(rows, dtype=np.float64), np.zeros(rows, dtype=np.float64)
+    sums = np.zeros((int(n_replicates), rows), dtype=np.float64) if return_sums else None
+    if lib.rdamd_rell_bootstrap(_dptr(a), rows, a.shape[1], _uptr(w), int(n_replicates), int(seed), _dptr(bp),
+                                _dptr(elw), _dptr(sums) if return_sums else None) != 1:
+        _fail("rell_bootstrap")
+    return (bp, elw, sums) if return_sums else (bp, elw)
+
+
+def rell_last_resample_ms():
+    """device time of the resampling kernel in this thread's last rell_bootstrap call (HIP events)"""
+    return float(lib.rdamd_rell_last_resample_ms())
+
+
 class Checkpoint:
     """checkpoint_t of the reference (src/checkpoint.hpp:231-300): the
     `<prefix>.ckp` result log, byte-compatible, shared between processes under
@@ -1258,6 +1313,36 @@ class Model:
         """the frequencies partition p evaluates with now"""
         out = np.zeros(self.states, dtype=np.float64)
         self._ok(lib.rdamd_model_partition_frequencies(self._h, p, _dptr(out)), "partition_frequencies")
+        return out
+
+    def site_patterns(self):
+        """(weights[P_total], pattern_of[N_columns]) of the concatenated partitions
+        (rdamd_model_site_patterns)."""
+        n, c = C.c_uint(0), C.c_uint(0)
+        self._ok(lib.rdamd_model_site_patterns(self._h, C.byref(n), C.byref(c), None, None), "site_patterns")
+        w = np.zeros(n.value, dtype=np.uint32)
+        po = np.zeros(c.value, dtype=np.uint32)
+        self._ok(lib.rdamd_model_site_patterns(self._h, None, None, _uptr(w), _uptr(po)), "site_patterns")
+        return w, po
+
+    def site_lnls(self, rls, params=None):
+        """Unweighted per-pattern lnL of every root in rls -> array [len(rls)][P_total]
+        (rdamd_model_site_lnls).  params: per root the list of per-partition dicts
+        Checkpoint.read_results returns; None: the model's current parameters."""
+        n = len(rls)
+        arr = (RootLocation * max(n, 1))(*rls)
+        pn = C.c_uint(0)
+        self._ok(lib.rdamd_model_site_patterns(self._h, C.byref(pn), None, None, None), "site_patterns")
+        out = np.zeros((n, pn.value), dtype=np.float64)
+        counts = values = None
+        if params is not None:
+            if len(params) != n:
+                raise ValueError("one parameter set per root is required")
+            counts, values = _flatten_params([pp for per_root in params for pp in per_root])
+        self._ok(lib.rdamd_model_site_lnls(self._h, n, arr,
+                                           counts.ctypes.data_as(_pu64) if counts is not None else None,
+                                           _dptr(values) if values is not None else None, _dptr(out)),
+                 "site_lnls")
         return out
 
     def partition_second_passes(self, p):

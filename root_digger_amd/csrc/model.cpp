@@ -369,6 +369,96 @@ std::vector<double> model_t::partition_lh(const root_location_t &root_location) 
   return out;
 }
 
+// ---- site log-likelihoods of a list of roots ------------------------------------------
+size_t model_t::pattern_count() const {
+  size_t n = 0;
+  for (auto p : _partitions) n += rdamd_partition_sites(p);
+  return n;
+}
+
+// The path compute_lh takes, with the root kernel's per-site output switched on.  That output is
+// weight x lnL; the partitions carry unit weights for the duration of the call (exact, and a
+// pattern of weight 0 keeps its lnL), so the rows are unweighted.
+void model_t::site_lnls(const std::vector<root_location_t> &rls,
+                        const std::vector<std::vector<partition_parameters_t>> *params, double *out) {
+  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
+    throw std::invalid_argument("site_lnls: this model sums over a site group and holds one block of the "
+                                "columns; per-site output of a site-sharded model is not supported");
+  if (params && params->size() != rls.size())
+    throw std::invalid_argument("site_lnls: one parameter set per root is required");
+  const size_t P = _partitions.size(), total = pattern_count();
+  struct saved_t {
+    std::vector<double> subst, freqs, rates, rate_weights;
+    std::vector<unsigned> pattern_weights;
+  };
+  std::vector<saved_t> saved(P);
+  const auto saved_rate_rates = _rate_rates;
+  const bool was_rooted = _tree.rooted();
+  const root_location_t saved_rl = _tree.root_location();
+  for (size_t p = 0; p < P; ++p) {
+    const rdamd_partition_t *part = _partitions[p];
+    const unsigned K = rdamd_partition_states(part);
+    const double *s = rdamd_partition_subst_params(part, 0), *f = rdamd_partition_frequencies(part, 0);
+    saved[p].subst.assign(s, s + (size_t)K * K - K);
+    saved[p].freqs.assign(f, f + K);
+    saved[p].rates = part->rates;
+    saved[p].rate_weights = part->rate_weights;
+    saved[p].pattern_weights = part->pattern_weights;
+  }
+  const auto restore = [&] {
+    _rate_rates = saved_rate_rates;
+    for (size_t p = 0; p < P; ++p) {
+      rdamd_set_pattern_weights(_partitions[p], saved[p].pattern_weights.data());
+      rdamd_set_subst_params(_partitions[p], 0, saved[p].subst.data());
+      rdamd_set_frequencies(_partitions[p], 0, saved[p].freqs.data());
+      rdamd_set_category_rates(_partitions[p], saved[p].rates.data());
+      rdamd_set_category_weights(_partitions[p], saved[p].rate_weights.data());
+    }
+  };
+  try {
+    for (size_t p = 0; p < P; ++p) {
+      const std::vector<unsigned> ones(rdamd_partition_sites(_partitions[p]), 1u);
+      if (!ones.empty()) rdamd_set_pattern_weights(_partitions[p], ones.data());
+    }
+    for (size_t i = 0; i < rls.size(); ++i) {
+      if (params) {
+        if ((*params)[i].size() != P)
+          throw std::invalid_argument("site_lnls: a parameter set needs one entry per partition");
+        for (size_t p = 0; p < P; ++p) {
+          const auto &pp = (*params)[i][p];
+          const size_t K = rdamd_partition_states(_partitions[p]);
+          if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
+              (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
+            throw std::invalid_argument("site_lnls: the parameters of root " + std::to_string(i) +
+                                        " do not fit partition " + std::to_string(p));
+        }
+        set_model_params((*params)[i]);
+      }
+      auto sched = _tree.generate_operations(rls[i]);
+      const auto &ops = std::get<0>(sched);
+      update_pmatrices(std::get<1>(sched), std::get<2>(sched));
+      ++_n_full;
+      double *row = out + i * total;
+      for (size_t p = 0; p < P; ++p) {
+        rdamd_update_clvs(_partitions[p], ops.data(), (unsigned)ops.size());
+        if (rdamd_errno()) fail("update_clvs");
+        if (rdamd_partition_sites(_partitions[p]) == 0) continue;
+        rdamd_compute_root_loglikelihood(_partitions[p], _tree.root_clv_index(), _tree.root_scaler_index(),
+                                         _param_indicies[p].data(), row);
+        if (rdamd_errno()) fail("compute_root_loglikelihood");
+        row += rdamd_partition_sites(_partitions[p]);
+      }
+    }
+  } catch (...) {
+    restore();
+    throw;
+  }
+  restore();
+  // the rooting, and the conditional likelihoods the root-only calls read, as they were
+  if (was_rooted) compute_lh(saved_rl);
+  else _tree.unroot();
+}
+
 // compute_lh for the searches, between optimize_params and the root-only steps: the same
 // value for the caller's convergence test, but only what those steps read is left behind --
 // the CLVs and scalers of the root's two children (rdamd_evaluate_root_children: one job of

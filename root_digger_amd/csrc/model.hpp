@@ -69,6 +69,9 @@ struct rd_result_t {   // src/util.hpp:126-130
 struct msa_t {
   std::vector<std::string>  labels, sequences;
   std::vector<unsigned int> weights;        // pattern weights; empty = all 1
+  // compress(): the pattern every column of the uncompressed alignment went into (empty: never
+  // compressed here -- pattern p then stands for weights[p] consecutive columns)
+  std::vector<unsigned int> pattern_of;
   unsigned int              states = 4;
   const uint64_t           *map = rdamd_map_nt;
   // a caller's character map is COPIED (the model -- and the replicas a parallel search makes
@@ -129,6 +132,14 @@ public:
   // so every root costs one root operation.  ratios: alpha per root (nullptr =
   // the stored ones).  One 4-state / binary partition.
   std::vector<double> compute_all_root_lh_directional(const std::vector<double> *ratios = nullptr);
+
+  // Unweighted per-pattern lnL of every root in `rls`, partitions concatenated in file order:
+  // out[rls.size()][pattern_count()].  params (optional): one parameter set per root, applied with
+  // set_model_params.  compute_lh + the root kernel's per-site output under unit pattern weights;
+  // parameters, rooting and the CLVs of that rooting are restored.  Not for site-sharded models.
+  void site_lnls(const std::vector<root_location_t> &rls,
+                 const std::vector<std::vector<partition_parameters_t>> *params, double *out);
+  size_t pattern_count() const;
 
   // batched objective: lnL of (root, parameter set) pairs, all partitions,
   // through rdamd_evaluate_batch (one fused launch per partition)

@@ -285,6 +285,103 @@ unsigned long long rdamd_model_partition_second_passes(const rdamd_model_t *m, u
   return rdamd_evaluate_second_passes(m->model->partition(p));
 }
 
+// ---- site patterns and site log-likelihoods (include/root_digger_amd.h) ----------------
+// a model that sums over a site group holds one block of the columns: error 61, not the generic 50
+static bool refuse_site_sharded(const rdamd_model_t *m, const char *what) {
+  if (!m->model->site_sharded()) return false;
+  rdamd::set_error(61, "%s: this model sums over a site group (rdamd_model_set_lnl_reducer) and holds one block of "
+                       "the columns; site-sharded models are not supported here", what);
+  return true;
+}
+// weights and column -> pattern map of the partitions' alignments, one behind the other
+static void concat_patterns(const std::vector<rdamd::msa_t> &msas, unsigned int *P_total, unsigned int *N_columns,
+                            unsigned int *weights, unsigned int *pattern_of) {
+  uint64_t patterns = 0, columns = 0;
+  for (const auto &msa : msas) {
+    const size_t len = msa.length();
+    for (size_t s = 0; s < len; ++s) {
+      const unsigned w = msa.weights.empty() ? 1u : msa.weights[s];
+      if (weights) weights[patterns + s] = w;
+      if (!msa.pattern_of.empty()) continue;
+      // (never compressed here: pattern s stands for w consecutive columns)
+      if (pattern_of)
+        for (unsigned k = 0; k < w; ++k) pattern_of[columns + k] = (unsigned)(patterns + s);
+      columns += w;
+    }
+    if (pattern_of)
+      for (size_t c = 0; c < msa.pattern_of.size(); ++c) pattern_of[columns + c] = (unsigned)(patterns + msa.pattern_of[c]);
+    columns += msa.pattern_of.size();
+    patterns += len;
+  }
+  if ((columns >> 32) || (patterns >> 32)) throw std::overflow_error("2^32 alignment columns or more");
+  if (P_total) *P_total = (unsigned)patterns;
+  if (N_columns) *N_columns = (unsigned)columns;
+}
+int rdamd_model_site_patterns(rdamd_model_t *m, unsigned int *P_total, unsigned int *N_columns,
+                              unsigned int *weights, unsigned int *pattern_of) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_site_patterns")) return RDAMD_FAILURE;
+    concat_patterns(m->msas, P_total, N_columns, weights, pattern_of);
+    return RDAMD_SUCCESS;
+  })
+}
+int rdamd_msa_pattern_probe(const char *msa_filename, const uint64_t *map, unsigned int n_lines,
+                            const char *const *lines, unsigned int *n_taxa, unsigned int *P_total,
+                            unsigned int *N_columns, unsigned int *weights, unsigned int *pattern_of,
+                            char *sequences) {
+  GUARD(RDAMD_FAILURE, {
+    std::vector<rdamd::msa_t> msas;
+    if (n_lines == 0) {
+      msas.push_back(rdamd::msa_t::from_file(msa_filename, map, 4, true));
+    } else {
+      const rdamd::msa_t whole = rdamd::msa_t::from_file(msa_filename, map, 4, false);
+      rdamd::msa_partitions_t infos;
+      for (unsigned i = 0; i < n_lines; ++i) infos.push_back(rdamd::parse_partition_info(lines[i]));
+      msas = rdamd::partition_msa(whole, infos, true);
+    }
+    unsigned total = 0;
+    concat_patterns(msas, &total, N_columns, weights, pattern_of);
+    if (P_total) *P_total = total;
+    if (n_taxa) *n_taxa = (unsigned)msas[0].count();
+    if (sequences) {
+      size_t at = 0;
+      for (const auto &msa : msas) {
+        for (int t = 0; t < msa.count(); ++t)
+          std::memcpy(sequences + (size_t)t * total + at, msa.sequences[t].data(), msa.length());
+        at += msa.length();
+      }
+    }
+    return RDAMD_SUCCESS;
+  })
+}
+int rdamd_model_site_lnls(rdamd_model_t *m, unsigned int n, const rdamd_root_location_t *rls,
+                          const uint64_t *counts, const double *values, double *out_patterns) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_site_lnls")) return RDAMD_FAILURE;
+    if ((counts == nullptr) != (values == nullptr))
+      throw std::invalid_argument("rdamd_model_site_lnls: counts and values come together");
+    if (n && (!rls || !out_patterns)) throw std::invalid_argument("rdamd_model_site_lnls: null argument");
+    std::vector<root_location_t> roots;
+    for (unsigned i = 0; i < n; ++i) roots.push_back(to_cpp(&rls[i]));
+    std::vector<std::vector<rdamd::partition_parameters_t>> params;
+    if (counts) {
+      const size_t P = m->model->partition_count();
+      for (unsigned i = 0; i < n; ++i) {
+        params.emplace_back(P);
+        for (size_t p = 0; p < P; ++p) {
+          rdamd::partition_parameters_t &pp = params.back()[p];
+          for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
+            v->assign(values, values + *counts);
+            values += *counts++;
+          }
+        }
+      }
+    }
+    m->model->site_lnls(roots, counts ? &params : nullptr, out_patterns);
+    return RDAMD_SUCCESS;
+  })
+}
+
 namespace {
 void fill_model(const rdamd::model_info_t &mi, rdamd_partition_info_t *out) {
   std::snprintf(out->subst_str, sizeof out->subst_str, "%s", mi.subst_str.c_str());

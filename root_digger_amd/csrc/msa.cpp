@@ -142,7 +142,7 @@ void msa_t::compress() {
   const std::vector<unsigned int> old_w = weights.size() == len ? weights : std::vector<unsigned int>(len, 1u);
   std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return cols[a] < cols[b]; });
   std::vector<std::string> out(n);
-  std::vector<unsigned int> w;
+  std::vector<unsigned int> w, into(len);
   for (size_t k = 0; k < len; ++k) {
     const size_t s = order[k];
     if (k && cols[s] == cols[order[k - 1]]) {
@@ -151,7 +151,11 @@ void msa_t::compress() {
       for (size_t i = 0; i < n; ++i) out[i].push_back(cols[s][i]);
       w.push_back(old_w[s]);
     }
+    into[s] = (unsigned int)w.size() - 1;
   }
+  // column -> pattern (an alignment compressed before keeps its own columns: compose)
+  if (pattern_of.empty()) pattern_of = into;
+  else for (auto &p : pattern_of) p = into[p];
   sequences = out;
   weights = w;
 }
@@ -168,7 +172,7 @@ msa_t msa_t::columns(size_t lo, size_t hi) const {
   out.map_store = map_store;
   for (const auto &s : sequences) out.sequences.push_back(s.substr(lo, hi - lo));
   if (!weights.empty()) out.weights.assign(hi - lo, 1u);
-  return out;
+  return out;   // (pattern_of stays empty: the block's own compress() fills it)
 }
 
 bool msa_t::constiency_check(const std::unordered_set<std::string> &tree_labels) const {

@@ -20,7 +20,14 @@
 // EVERY partition's own columns (rdamd_model_create_partitioned_block); every partition keeps its
 // own parameters, as in the reference's partitioned runs.
 //
+// --rell B [--rell-seed N] / --site-lh (new here, with --exhaustive): after the search rank 0 reads
+// every candidate's parameters back from the checkpoint, evaluates their site log-likelihoods
+// (rdamd_model_site_lnls) and writes <prefix>.sitelh (Tree-Puzzle / CONSEL layout) and, from a RELL
+// bootstrap of B replicates on the device (rdamd_rell_bootstrap), <prefix>.support.tsv and the BP /
+// ELW annotations of <prefix>.lwr.tree.
+//
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -52,6 +59,10 @@ struct options_t {
   int strategy = 2;     // random, midpoint, modified-mad
   bool exhaustive = false, silent = false, clean = false, echo = false, no_checkpoint = false,
        invariant_sites = false;
+  // RELL bootstrap of the candidates' site lnLs (--rell B, 0: off) and the .sitelh file
+  long rell = 0;
+  bool rell_given = false, rell_seed_given = false, site_lh = false;
+  uint64_t rell_seed = 0;
 };
 
 [[noreturn]] void die(const std::string &what) {
@@ -70,7 +81,8 @@ void usage() {
       "  --atol <X>  --brtol <X>  --bfgstol <X>  --factor <X>  --early-stop  --no-early-stop\n"
       "  --initial-root-strategy {random,midpoint,modified-mad}  --threads <N>  --lockstep <N>\n"
       "  --site-shards <G>  --site-reduce {rccl,rccl-allreduce,host}  --lockstep-rounds {0,1}  --lockstep-groups {1,2}  --stats\n"
-      "  --lbfgsb <LIB>  --device <N>  --silent  --echo  --clean  --no-checkpoint  --version");
+      "  --lbfgsb <LIB>  --device <N>  --silent  --echo  --clean  --no-checkpoint  --version\n"
+      "  --rell <B>  --rell-seed <N>  --site-lh   (with --exhaustive: RELL support and site lnLs of every root)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -94,6 +106,8 @@ options_t parse(int argc, char **argv) {
       {"no-checkpoint", no_argument, 0, 0},      {"site-shards", required_argument, 0, 0},
       {"site-reduce", required_argument, 0, 0},  {"lockstep-rounds", required_argument, 0, 0},
       {"stats", no_argument, 0, 0},              {"lockstep-groups", required_argument, 0, 0},
+      {"rell", required_argument, 0, 0},         {"rell-seed", required_argument, 0, 0},
+      {"site-lh", no_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -137,6 +151,9 @@ options_t parse(int argc, char **argv) {
     else if (name == "lockstep-rounds") o.lockstep_rounds = std::atoi(v);
     else if (name == "lockstep-groups") o.lockstep_groups = std::atoi(v);
     else if (name == "stats") o.stats = true;
+    else if (name == "rell") { o.rell = std::atol(v); o.rell_given = true; }
+    else if (name == "rell-seed") { o.rell_seed = std::strtoull(v, nullptr, 10); o.rell_seed_given = true; }
+    else if (name == "site-lh") o.site_lh = true;
     else if (name == "site-reduce") {
       const std::string s = v;
       if (s != "rccl" && s != "rccl-allreduce" && s != "host") die("--site-reduce takes rccl, rccl-allreduce or host");
@@ -172,6 +189,16 @@ static int run(int argc, char **argv) {
   const int rank = env_int("RANK", 0), world = env_int("WORLD_SIZE", 1);
   if (o.prefix.empty()) o.prefix = o.msa;
   if (world > 1 && o.no_checkpoint) die("--no-checkpoint: the ranks of a run meet in the checkpoint file");
+  // the candidates' records and parameters are read back from the checkpoint; a site group's
+  // member holds one block of the columns
+  const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : nullptr;
+  if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
+  if (support_opt) {
+    const std::string opt = support_opt;
+    if (o.rell_given && (o.rell < 1 || o.rell > 0x7fffffffl)) die("--rell: the number of replicates must be at least 1");
+    if (o.no_checkpoint) die(opt + ": the candidates' parameters are read from the checkpoint; not with --no-checkpoint");
+    if (o.site_shards > 1) die(opt + ": not supported with --site-shards > 1 (each rank holds one block of the columns)");
+  }
   need(rdamd_set_device(o.device >= 0 ? o.device : env_int("LOCAL_RANK", 0)), "set_device");
   rendezvous_t ranks(rank, world);
   // candidate groups x site shards (see the header comment): rank = cgroup * G + srank
@@ -252,6 +279,9 @@ static int run(int argc, char **argv) {
       o.root_ratio = h.root_ratio; o.strategy = h.initial_root_strategy; o.early_stop = h.early_stop;
     }
   }
+  if (support_opt && !o.exhaustive)
+    die(std::string(support_opt) + ": needs --exhaustive (the heuristic search evaluates one root)");
+  if (!o.rell_seed_given) o.rell_seed = o.seed;
   if (o.msa.empty()) { std::puts("No MSA was given, please supply an MSA"); usage(); return 1; }
   if (o.tree.empty()) { std::puts("No tree was given, please supply an tree"); usage(); return 1; }
 
@@ -416,6 +446,7 @@ static int run(int argc, char **argv) {
                  (unsigned long long)(ls[0] ? ls[0] : ct[0]), (unsigned long long)(ls[1] ? ls[1] : ct[1]),
                  (unsigned long long)ls[2], (unsigned long long)ls[3], rsec[0], rsec[1], rsec[2], rsec[3], took.count());
   }
+  const std::chrono::duration<double> search_took = std::chrono::steady_clock::now() - start;
   ranks.barrier();
   if (rank != 0) {
     rdamd_model_destroy(model);
@@ -444,6 +475,80 @@ static int run(int argc, char **argv) {
     }
   }
   if (n_results == 0) die("no candidate root was evaluated");
+
+  // ---- site lnLs of every candidate at its own parameters, .sitelh, RELL support
+  std::vector<double> bp, elw;
+  double site_seconds = 0.0, rell_seconds = 0.0;
+  if (support_opt) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<rdamd_root_location_t> rls(n_results);
+    std::vector<uint64_t> counts;
+    std::vector<double> values;
+    for (unsigned i = 0; i < n_results; ++i) {
+      uint64_t id = 0, nv = 0;
+      double l = 0, a = 0;
+      unsigned np = 0;
+      need(rdamd_checkpoint_result(ckp, i, &id, &l, &a, &np, &nv), "checkpoint result");
+      const size_t c0 = counts.size(), v0 = values.size();
+      counts.resize(c0 + 4 * (size_t)np);
+      values.resize(v0 + nv + 1);
+      need(rdamd_checkpoint_result_params(ckp, i, counts.data() + c0, values.data() + v0), "checkpoint result_params");
+      values.resize(v0 + nv);
+      need(rdamd_tree_root_location(tree, (unsigned)ids[i], &rls[i]), "root_location");
+      rls[i].brlen_ratio = alpha[i];
+    }
+    values.push_back(0.0);   // (never empty)
+    unsigned P = 0, columns = 0;
+    need(rdamd_model_site_patterns(model, &P, &columns, nullptr, nullptr), "site_patterns");
+    std::vector<unsigned> weights(P), pattern_of(columns);
+    need(rdamd_model_site_patterns(model, nullptr, nullptr, weights.data(), pattern_of.data()), "site_patterns");
+    std::vector<double> lnls((size_t)n_results * P);
+    need(rdamd_model_site_lnls(model, n_results, rls.data(), counts.data(), values.data(), lnls.data()), "site_lnls");
+    // the log keeps a candidate's BEST lnL but its LAST parameters: say when they are not one iterate's
+    unsigned off = 0;
+    for (unsigned i = 0; i < n_results; ++i) {
+      double total = 0.0;
+      for (unsigned p = 0; p < P; ++p) total += weights[p] * lnls[(size_t)i * P + p];
+      if (!(std::fabs(total - llh[i]) <= o.atol)) ++off;
+    }
+    if (off)
+      std::cerr << off << " of " << n_results << " candidates: the lnL re-evaluated from the recorded parameters "
+                << "differs from the recorded lnL by more than --atol (the record keeps the best iterate's lnL and "
+                << "the last iterate's parameters)\n";
+    site_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (o.site_lh) {
+      std::FILE *f = std::fopen((o.prefix + ".sitelh").c_str(), "w");
+      if (!f) die("could not write " + o.prefix + ".sitelh");
+      std::fprintf(f, "%u %u\n", n_results, columns);
+      for (unsigned i = 0; i < n_results; ++i) {
+        std::fprintf(f, "root%llu", (unsigned long long)ids[i]);
+        for (unsigned c = 0; c < columns; ++c) std::fprintf(f, " %.17g", lnls[(size_t)i * P + pattern_of[c]]);
+        std::fputc('\n', f);
+      }
+      std::fclose(f);
+    }
+    if (o.rell_given) {
+      const auto t1 = std::chrono::steady_clock::now();
+      bp.assign(n_results, 0.0);
+      elw.assign(n_results, 0.0);
+      need(rdamd_rell_bootstrap(lnls.data(), n_results, P, weights.data(), (unsigned)o.rell, o.rell_seed, bp.data(),
+                                elw.data(), nullptr), "rell_bootstrap");
+      rell_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+      double mx = -INFINITY, total = 0.0;
+      for (unsigned i = 0; i < n_results; ++i) mx = std::max(mx, llh[i]);
+      for (unsigned i = 0; i < n_results; ++i) total += std::exp(llh[i] - mx);
+      std::vector<unsigned> by_id(n_results);
+      for (unsigned i = 0; i < n_results; ++i) by_id[i] = i;
+      std::stable_sort(by_id.begin(), by_id.end(), [&](unsigned a, unsigned b) { return ids[a] < ids[b]; });
+      std::FILE *f = std::fopen((o.prefix + ".support.tsv").c_str(), "w");
+      if (!f) die("could not write " + o.prefix + ".support.tsv");
+      std::fprintf(f, "root_id\tllh\tlwr\tbp\telw\n");
+      for (unsigned i : by_id)
+        std::fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\n", (unsigned long long)ids[i], llh[i],
+                     std::exp(llh[i] - mx) / total, bp[i], elw[i]);
+      std::fclose(f);
+    }
+  }
   rdamd_tree_t *out = rdamd_tree_from_file(o.tree.c_str());
   std::string final_tree;
   if (o.exhaustive) {
@@ -455,6 +560,10 @@ static int run(int argc, char **argv) {
       need(rdamd_tree_root_location(out, (unsigned)ids[i], &rl), "root_location");
       rl.brlen_ratio = alpha[i];
       rdamd_tree_annotate_branch(out, &rl, "LWR", std::to_string(std::exp(llh[i] - mx) / total).c_str());
+      if (!bp.empty()) {
+        rdamd_tree_annotate_branch(out, &rl, "BP", std::to_string(bp[i]).c_str());
+        rdamd_tree_annotate_branch(out, &rl, "ELW", std::to_string(elw[i]).c_str());
+      }
       rdamd_tree_annotate_branch(out, &rl, "LLH", std::to_string(llh[i]).c_str());
       rdamd_tree_annotate_branch_lr(out, &rl, "alpha", std::to_string(alpha[i]).c_str(),
                                     std::to_string(1 - alpha[i]).c_str());
@@ -480,6 +589,11 @@ static int run(int argc, char **argv) {
   }
   if (!o.silent) std::printf("Final LogLH: %.5f\n", best_llh);
   std::cout << final_tree << std::endl;
+  if (!o.silent && support_opt) {
+    std::cout << "Search took: " << search_took.count() << "s" << std::endl;
+    std::cout << "Site lnLs took: " << site_seconds << "s" << std::endl;
+    if (o.rell_given) std::cout << "RELL bootstrap took: " << rell_seconds << "s" << std::endl;
+  }
   if (!o.silent) {
     const std::chrono::duration<double> took = std::chrono::steady_clock::now() - start;
     std::cout << "Inference took: " << took.count() << "s" << std::endl;
