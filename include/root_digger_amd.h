@@ -930,6 +930,58 @@ int rdamd_rell_bootstrap(const double *site_lnl, unsigned int n_rows, unsigned i
  * milliseconds between two HIP events (0 after a failed call); for measurements */
 double rdamd_rell_last_resample_ms(void);
 
+/* KH, SH and weighted-SH tests of the rows (candidate roots), made on the device from the
+ * resampled sums of rdamd_rell_bootstrap (Kishino & Hasegawa 1989; Shimodaira & Hasegawa 1999).
+ * The inputs are those of rdamd_rell_bootstrap. sums[b][i] is exactly that function's: same
+ * draws, same order of additions, same bits. With B replicates and n rows:
+ *
+ * - Observed lnL. lnl[i] = sum_p pattern_weights[p] * site_lnl[i][p].
+ *   - It is summed on the device in one fixed order that depends on the pattern count alone.
+ *   - m is the lowest i with the largest lnl[i].
+ * - Centred sums. mean[i] = (1/B) sum_b sums[b][i], the replicates added in one fixed order that
+ *   depends on B alone. c[b][i] = sums[b][i] - mean[i].
+ * - KH. p_kh[i] = #{b : c[b][m] - c[b][i] >= lnl[m] - lnl[i]} / B.
+ * - SH. p_sh[i] = #{b : max_j c[b][j] - c[b][i] >= lnl[m] - lnl[i]} / B.
+ * - Pair spread. s[i][j] = sqrt( sum_b (c[b][i] - c[b][j])^2 / (B - 1) ).
+ *   - It is computed from the differences themselves, not from a Gram matrix.
+ *   - Rows whose sums are bit-identical therefore have s = 0 exactly.
+ * - WSH. The statistic is t(x)_i = max( 0, max over j != i with s[i][j] > 0 of (x_j - x_i) / s[i][j] ).
+ *   - p_wsh[i] = #{b : t(c[b])_i >= t(lnl)_i} / B.
+ *   - The zero term is the j = i term. Pairs with s = 0 differ by nothing and are left out.
+ *
+ * All comparisons are >=. For row m both sides of KH and SH are exactly 0, and x - x is exactly 0
+ * in floating point. So p_kh[m] = p_sh[m] = 1 by arithmetic, not by a special case. A row whose
+ * WSH statistic is 0 is equally robust.
+ *
+ * Every p is an integer count divided by B. With n = 1 all three are 1. The call needs B >= 2.
+ *
+ * How the device computes it (csrc/kernels_rell_tests.hip):
+ *   the sums over patterns (lnl) and over replicates (mean): entry k goes to chunk k / 512, in it
+ *   to slice (k % 512) / 128, in that to partial sum k % 4; a partial sum adds its entries by
+ *   increasing k (lnl: one fused multiply-add per pattern; a pattern of weight 0 is left out, so it
+ *   may hold anything), a slice is (p0 + p1) + (p2 + p3), a chunk (s0 + s1) + (s2 + s3), and the
+ *   chunks are added by increasing index; mean = that sum / B;
+ *   a pair's squares are added by increasing b, one fused multiply-add each, so s is symmetric to
+ *   the bit; a statistic divides by multiplying with 1 / s[i][j], rounded once per pair;
+ *   counts are integers added with integer atomics.  No result depends on a launch shape; a
+ *   repeated call returns the same bits; a row's lnl, mean, p_kh do not depend on the other rows
+ *   beyond lnl[m] and c[.][m].
+ * Host pointers: lnl[n_rows] (may be NULL), bp, elw, sums as in rdamd_rell_bootstrap and
+ * bit-identical to its results for the same arguments, p_kh[n_rows], p_sh[n_rows], p_wsh[n_rows]
+ * (may be NULL: the O(n_rows^2 B) part is then not run), spread[n_rows][n_rows] (may be NULL):
+ * the pair spreads s, for checks.
+ * Error 62: as rdamd_rell_bootstrap; also n_replicates < 2, p_kh or p_sh missing, and p_wsh or
+ * spread given with more than 8192 rows (the table of n_rows^2 doubles is 512 MB there) --
+ * nothing is launched. */
+int rdamd_rell_tests(const double *site_lnl, unsigned int n_rows, unsigned int n_patterns,
+                     const unsigned int *pattern_weights, unsigned int n_replicates, uint64_t seed,
+                     double *lnl, double *bp, double *elw, double *p_kh, double *p_sh, double *p_wsh,
+                     double *sums, double *spread);
+/* device time of everything this thread's last rdamd_rell_tests call launched after the
+ * resampling kernel (BP / ELW included), milliseconds between two HIP events (0 after a failed
+ * call); rdamd_rell_last_resample_ms holds the resampling kernel's own time of that call */
+double rdamd_rell_last_tests_ms(void);
+
 /* RCCL communicator of one site group (librccl is loaded on first use; the
  * library has no link-time dependency on it).  Rank 0 of the group calls
  * rdamd_comm_unique_id and hands the 128 bytes to the others by any means

@@ -45,6 +45,9 @@ from .api import (  # noqa: F401
     rell_column,
     rell_bootstrap,
     rell_last_resample_ms,
+    rell_tests,
+    rell_last_tests_ms,
+    elw_confidence_set,
 )
 
 __all__ = [
@@ -56,4 +59,5 @@ __all__ = [
     "device_count", "hip_runtime_path", "mapped_hip_runtimes", "set_device", "device_memory", "msa_probe",
     "rank_order_sum", "COMM_SUM_GATHER", "COMM_SUM_ALLREDUCE",
     "msa_pattern_probe", "rell_column", "rell_bootstrap", "rell_last_resample_ms",
+    "rell_tests", "rell_last_tests_ms", "elw_confidence_set",
 ]

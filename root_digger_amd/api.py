@@ -293,6 +293,8 @@ _sig("rdamd_model_site_lnls", C.c_int, _vp, _u, _prl, _pu64, _pd, _pd)
 _sig("rdamd_rell_column", C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64)
 _sig("rdamd_rell_bootstrap", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd)
 _sig("rdamd_rell_last_resample_ms", C.c_double)
+_sig("rdamd_rell_tests", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd)
+_sig("rdamd_rell_last_tests_ms", C.c_double)
 
 _libc = C.CDLL(None)
 _libc.free.argtypes = [_vp]
@@ -1019,6 +1021,53 @@ def rell_bootstrap(site_lnl, pattern_weights, n_replicates, seed=1, return_sums=
 def rell_last_resample_ms():
     """device time of the resampling kernel in this thread's last rell_bootstrap call (HIP events)"""
     return float(lib.rdamd_rell_last_resample_ms())
+
+
+def rell_tests(site_lnl, pattern_weights, n_replicates, seed=1, return_sums=False, return_spread=False):
+    """KH, SH and weighted-SH tests of the rows of site_lnl[rows][patterns] from a RELL bootstrap on
+    the current device (rdamd_rell_tests) -> dict of arrays lnl, bp, elw, p_kh, p_sh, p_wsh
+    [, sums[n_replicates][rows]][, spread[rows][rows]]; bp, elw and sums are rell_bootstrap's."""
+    a = np.ascontiguousarray(site_lnl, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("site_lnl is [rows][patterns]")
+    w = np.ascontiguousarray(pattern_weights, dtype=np.uint32)
+    if w.shape != (a.shape[1],):
+        raise ValueError("one weight per pattern is required")
+    rows = a.shape[0]
+    out = {k: np.zeros(rows, dtype=np.float64) for k in ("lnl", "bp", "elw", "p_kh", "p_sh", "p_wsh")}
+    if return_sums:
+        out["sums"] = np.zeros((int(n_replicates), rows), dtype=np.float64)
+    if return_spread:
+        out["spread"] = np.zeros((rows, rows), dtype=np.float64)
+    if lib.rdamd_rell_tests(_dptr(a), rows, a.shape[1], _uptr(w), int(n_replicates), int(seed), _dptr(out["lnl"]),
+                            _dptr(out["bp"]), _dptr(out["elw"]), _dptr(out["p_kh"]), _dptr(out["p_sh"]),
+                            _dptr(out["p_wsh"]), _dptr(out["sums"]) if return_sums else None,
+                            _dptr(out["spread"]) if return_spread else None) != 1:
+        _fail("rell_tests")
+    return out
+
+
+def rell_last_tests_ms():
+    """device time of everything this thread's last rell_tests call launched after the resampling
+    kernel (HIP events)"""
+    return float(lib.rdamd_rell_last_tests_ms())
+
+
+def elw_confidence_set(elw, level=0.95):
+    """boolean mask of the rows in the ELW confidence set (Strimmer & Rambaut 2002): rows by
+    decreasing elw, equal values by lower index, taken until the running sum reaches `level`
+    (host only)"""
+    e = np.asarray(elw, dtype=np.float64)
+    if e.ndim != 1:
+        raise ValueError("elw is one value per row")
+    mask = np.zeros(e.shape[0], dtype=bool)
+    total = 0.0
+    for i in np.argsort(-e, kind="stable"):
+        mask[i] = True
+        total += e[i]
+        if total >= level:
+            break
+    return mask
 
 
 class Checkpoint:

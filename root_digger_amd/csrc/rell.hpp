@@ -43,4 +43,38 @@ hipError_t launch_rell_support(const double *d_sums, unsigned n_rows, unsigned n
                                double *d_weights, unsigned *d_winner, double *d_bp, double *d_elw,
                                hipStream_t stream);
 
+// ---- KH / SH / weighted-SH tests of the rows (rdamd_rell_tests; kernels_rell_tests.hip).
+// c[b][i] = d_sums[b][i] - d_mean[i] is never stored: every kernel subtracts as it loads.
+// All counts are unsigned integers (integer atomics only); no result depends on a launch shape.
+
+// Sums over the leading axis are made in chunks of RELL_CHUNK entries: d_partial holds
+// rell_chunks(K) * n_rows doubles for a sum over K entries.
+constexpr unsigned RELL_CHUNK = 512;
+inline unsigned rell_chunks(unsigned K) { return (K + RELL_CHUNK - 1) / RELL_CHUNK; }
+// at most this many rows with a pair table (n^2 doubles: 512 MB here)
+constexpr unsigned RELL_MAX_PAIR_ROWS = 8192;
+
+// d_lnl[i] = sum_p weights[p] * table[p][i] (patterns of weight 0 are left out), d_best[0] = the
+// lowest row with the largest d_lnl
+hipError_t launch_rell_totals(const double *d_table, unsigned padded, const unsigned *d_pattern_weights,
+                              unsigned n_patterns, unsigned n_rows, double *d_partial, double *d_lnl,
+                              unsigned *d_best, hipStream_t stream);
+// d_mean[i] = (sum_b d_sums[b][i]) / n_replicates
+hipError_t launch_rell_means(const double *d_sums, unsigned n_rows, unsigned n_replicates, double *d_partial,
+                             double *d_mean, hipStream_t stream);
+// d_cmax[b] = max_j c[b][j], d_cbest[b] = c[b][best]; then d_kh[i] / d_sh[i] = replicates with
+// d_cbest[b] - c[b][i] / d_cmax[b] - c[b][i] >= d_lnl[best] - d_lnl[i]
+hipError_t launch_rell_kh_sh(const double *d_sums, const double *d_mean, const double *d_lnl,
+                             const unsigned *d_best, unsigned n_rows, unsigned n_replicates, double *d_cmax,
+                             double *d_cbest, unsigned *d_kh, unsigned *d_sh, hipStream_t stream);
+// s[i][j] = sqrt(sum_b (c[b][i] - c[b][j])^2 / (n_replicates - 1)), replicates added in order:
+// d_rinv[i][j] = s > 0 ? 1 / s : 0 and, unless NULL, d_spread[i][j] = s; both symmetric to the bit
+hipError_t launch_rell_spreads(const double *d_sums, const double *d_mean, unsigned n_rows,
+                               unsigned n_replicates, double *d_rinv, double *d_spread, hipStream_t stream);
+// t(x)_i = max(0, max_j (x_j - x_i) * d_rinv[i][j]); d_tobs[i] = t(d_lnl)_i,
+// d_wsh[i] = replicates with t(c[b])_i >= d_tobs[i]
+hipError_t launch_rell_wsh(const double *d_sums, const double *d_mean, const double *d_lnl,
+                           const double *d_rinv, unsigned n_rows, unsigned n_replicates, double *d_tobs,
+                           unsigned *d_wsh, hipStream_t stream);
+
 }  // namespace rdamd

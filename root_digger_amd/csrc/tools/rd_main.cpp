@@ -24,7 +24,9 @@
 // every candidate's parameters back from the checkpoint, evaluates their site log-likelihoods
 // (rdamd_model_site_lnls) and writes <prefix>.sitelh (Tree-Puzzle / CONSEL layout) and, from a RELL
 // bootstrap of B replicates on the device (rdamd_rell_bootstrap), <prefix>.support.tsv and the BP /
-// ELW annotations of <prefix>.lwr.tree.
+// ELW annotations of <prefix>.lwr.tree.  --root-tests (with --rell): the KH, SH and weighted-SH tests of
+// every candidate from the same replicates (rdamd_rell_tests instead of rdamd_rell_bootstrap):
+// <prefix>.roottests.tsv, and pKH / pSH / pWSH next to BP / ELW on <prefix>.lwr.tree.
 //
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
@@ -61,7 +63,7 @@ struct options_t {
        invariant_sites = false;
   // RELL bootstrap of the candidates' site lnLs (--rell B, 0: off) and the .sitelh file
   long rell = 0;
-  bool rell_given = false, rell_seed_given = false, site_lh = false;
+  bool rell_given = false, rell_seed_given = false, site_lh = false, root_tests = false;
   uint64_t rell_seed = 0;
 };
 
@@ -82,7 +84,8 @@ void usage() {
       "  --initial-root-strategy {random,midpoint,modified-mad}  --threads <N>  --lockstep <N>\n"
       "  --site-shards <G>  --site-reduce {rccl,rccl-allreduce,host}  --lockstep-rounds {0,1}  --lockstep-groups {1,2}  --stats\n"
       "  --lbfgsb <LIB>  --device <N>  --silent  --echo  --clean  --no-checkpoint  --version\n"
-      "  --rell <B>  --rell-seed <N>  --site-lh   (with --exhaustive: RELL support and site lnLs of every root)");
+      "  --rell <B>  --rell-seed <N>  --site-lh   (with --exhaustive: RELL support and site lnLs of every root)\n"
+      "  --root-tests   (with --rell: KH, SH and weighted-SH p-values of every root, <prefix>.roottests.tsv)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -107,7 +110,7 @@ options_t parse(int argc, char **argv) {
       {"site-reduce", required_argument, 0, 0},  {"lockstep-rounds", required_argument, 0, 0},
       {"stats", no_argument, 0, 0},              {"lockstep-groups", required_argument, 0, 0},
       {"rell", required_argument, 0, 0},         {"rell-seed", required_argument, 0, 0},
-      {"site-lh", no_argument, 0, 0},
+      {"site-lh", no_argument, 0, 0},            {"root-tests", no_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -154,6 +157,7 @@ options_t parse(int argc, char **argv) {
     else if (name == "rell") { o.rell = std::atol(v); o.rell_given = true; }
     else if (name == "rell-seed") { o.rell_seed = std::strtoull(v, nullptr, 10); o.rell_seed_given = true; }
     else if (name == "site-lh") o.site_lh = true;
+    else if (name == "root-tests") o.root_tests = true;
     else if (name == "site-reduce") {
       const std::string s = v;
       if (s != "rccl" && s != "rccl-allreduce" && s != "host") die("--site-reduce takes rccl, rccl-allreduce or host");
@@ -193,6 +197,8 @@ static int run(int argc, char **argv) {
   // member holds one block of the columns
   const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : nullptr;
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
+  if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
+  if (o.root_tests && o.rell < 2) die("--root-tests: --rell must give at least 2 replicates");
   if (support_opt) {
     const std::string opt = support_opt;
     if (o.rell_given && (o.rell < 1 || o.rell > 0x7fffffffl)) die("--rell: the number of replicates must be at least 1");
@@ -477,7 +483,7 @@ static int run(int argc, char **argv) {
   if (n_results == 0) die("no candidate root was evaluated");
 
   // ---- site lnLs of every candidate at its own parameters, .sitelh, RELL support
-  std::vector<double> bp, elw;
+  std::vector<double> bp, elw, p_kh, p_sh, p_wsh;
   double site_seconds = 0.0, rell_seconds = 0.0;
   if (support_opt) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -531,8 +537,17 @@ static int run(int argc, char **argv) {
       const auto t1 = std::chrono::steady_clock::now();
       bp.assign(n_results, 0.0);
       elw.assign(n_results, 0.0);
-      need(rdamd_rell_bootstrap(lnls.data(), n_results, P, weights.data(), (unsigned)o.rell, o.rell_seed, bp.data(),
-                                elw.data(), nullptr), "rell_bootstrap");
+      if (o.root_tests) {
+        p_kh.assign(n_results, 0.0);
+        p_sh.assign(n_results, 0.0);
+        p_wsh.assign(n_results, 0.0);
+        need(rdamd_rell_tests(lnls.data(), n_results, P, weights.data(), (unsigned)o.rell, o.rell_seed, nullptr,
+                              bp.data(), elw.data(), p_kh.data(), p_sh.data(), p_wsh.data(), nullptr, nullptr),
+             "rell_tests");
+      } else {
+        need(rdamd_rell_bootstrap(lnls.data(), n_results, P, weights.data(), (unsigned)o.rell, o.rell_seed, bp.data(),
+                                  elw.data(), nullptr), "rell_bootstrap");
+      }
       rell_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
       double mx = -INFINITY, total = 0.0;
       for (unsigned i = 0; i < n_results; ++i) mx = std::max(mx, llh[i]);
@@ -547,6 +562,37 @@ static int run(int argc, char **argv) {
         std::fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\n", (unsigned long long)ids[i], llh[i],
                      std::exp(llh[i] - mx) / total, bp[i], elw[i]);
       std::fclose(f);
+      if (o.root_tests) {
+        // the 95 % ELW set: rows by decreasing elw, equal values by lower index, until the sum reaches 0.95
+        std::vector<unsigned> by_elw(n_results);
+        for (unsigned i = 0; i < n_results; ++i) by_elw[i] = i;
+        std::stable_sort(by_elw.begin(), by_elw.end(), [&](unsigned a, unsigned b) { return elw[a] > elw[b]; });
+        std::vector<int> in_set(n_results, 0);
+        double running = 0.0;
+        for (unsigned i : by_elw) {
+          in_set[i] = 1;
+          running += elw[i];
+          if (running >= 0.95) break;
+        }
+        f = std::fopen((o.prefix + ".roottests.tsv").c_str(), "w");
+        if (!f) die("could not write " + o.prefix + ".roottests.tsv");
+        std::fprintf(f, "root_id\tllh\tlwr\tbp\telw\tp_kh\tp_sh\tp_wsh\tin_elw95\n");
+        for (unsigned i : by_id)
+          std::fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%d\n", (unsigned long long)ids[i],
+                       llh[i], std::exp(llh[i] - mx) / total, bp[i], elw[i], p_kh[i], p_sh[i], p_wsh[i], in_set[i]);
+        std::fclose(f);
+        if (!o.silent) {
+          unsigned kh = 0, sh = 0, wsh = 0, in95 = 0;
+          for (unsigned i = 0; i < n_results; ++i) {
+            kh += p_kh[i] >= 0.05;
+            sh += p_sh[i] >= 0.05;
+            wsh += p_wsh[i] >= 0.05;
+            in95 += in_set[i];
+          }
+          std::cout << "Root tests: of " << n_results << " roots, not rejected at 0.05 by KH " << kh << ", SH " << sh
+                    << ", WSH " << wsh << "; 95% ELW set " << in95 << std::endl;
+        }
+      }
     }
   }
   rdamd_tree_t *out = rdamd_tree_from_file(o.tree.c_str());
@@ -563,6 +609,11 @@ static int run(int argc, char **argv) {
       if (!bp.empty()) {
         rdamd_tree_annotate_branch(out, &rl, "BP", std::to_string(bp[i]).c_str());
         rdamd_tree_annotate_branch(out, &rl, "ELW", std::to_string(elw[i]).c_str());
+        if (!p_kh.empty()) {
+          rdamd_tree_annotate_branch(out, &rl, "pKH", std::to_string(p_kh[i]).c_str());
+          rdamd_tree_annotate_branch(out, &rl, "pSH", std::to_string(p_sh[i]).c_str());
+          rdamd_tree_annotate_branch(out, &rl, "pWSH", std::to_string(p_wsh[i]).c_str());
+        }
       }
       rdamd_tree_annotate_branch(out, &rl, "LLH", std::to_string(llh[i]).c_str());
       rdamd_tree_annotate_branch_lr(out, &rl, "alpha", std::to_string(alpha[i]).c_str(),
