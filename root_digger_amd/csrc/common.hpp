@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/root_digger_amd.h"
+#include "level_op.hpp"
 
 namespace rdamd {
 
@@ -33,6 +34,11 @@ constexpr unsigned kTipcodePad = 256;   // bytes of slack after the tip-code row
 // 20-state data the fused evaluator takes (kernels_fused_k20.hip: a workgroup is one wave per rate
 // category): up to eight categories, at any stack depth.  Beyond eight the traversal kernels serve.
 inline bool fused20_capable(unsigned states, size_t rate_cats) { return states == 20 && rate_cats <= 8; }
+// Does a fused evaluator take partitions of this shape at all?  4-state data -- the C ABI's 2-state
+// partitions count as such, they run embedded in the 4-state machinery -- and the 20-state shapes above.
+inline bool fused_capable(unsigned states, size_t rate_cats) {
+  return states == 4 || states == 2 || fused20_capable(states, rate_cats);
+}
 
 void set_error(int code, const char *fmt, ...);
 void clear_error();
@@ -246,42 +252,14 @@ hipError_t launch_pmatrix(rdamd_partition *p, const unsigned *d_params_indices,
 hipError_t launch_tiptab_all(rdamd_partition *p);
 
 // kernels_clv.hip
-struct LevelOp {   // device-side op descriptor
-  unsigned parent_clv, child1_clv, child2_clv;     // absolute clv indices
-  unsigned child1_mat, child2_mat;
-  int parent_sc, child1_sc, child2_sc;
-  // where each child comes from: 0 tip, 1 memory, 2 register (= parent of the
-  // previous op), 3+s = LDS parking slot s (4-state kernel only)
-  unsigned src1, src2;
-  // 4-state kernel: park = 1+s: also park the parent in LDS slot s (0: do not); noop = padding
-  // entry (lists are padded to whole chunks).  20-state kernel (which has neither): the tip
-  // indices of the NEXT operation's children (0 where a child is no tip, or there is no
-  // next operation) -- it fetches tip codes through the scalar cache two operations ahead,
-  // and taking the address from the operation in front means no scalar load has to wait
-  // for another one.
-  union { unsigned park; unsigned ahead1; };
-  union { unsigned noop; unsigned ahead2; };
-  // 4-state kernel only: byte offsets worked out on the host, so the kernel's
-  // scalar unit does no 64-bit index arithmetic.  *_off of a child: its row in
-  // the tip codes (tip) or its CLV (memory); kNoOffset where there is none.
-  uint64_t parent_off, parent_sc_off;
-  uint64_t child1_off, child1_sc_off;
-  uint64_t child2_off, child2_sc_off;
-};
-static_assert(sizeof(LevelOp) == 96, "LevelOp: 12 words + 6 offsets");
-constexpr uint64_t kNoOffset = ~0ull;
+// (LevelOp, kNoOffset: level_op.hpp)
 // LDS parking slots per lane the 4-state traversal kernel will have for this
 // partition (0 for the other kernels): an older sibling waits there instead of
 // being read back from HBM.
 unsigned clv_traversal_slots(const rdamd_partition *p);
 // the 4-state kernel wants its list padded with no-ops to a multiple of this (else 1)
 unsigned clv_traversal_chunk(const rdamd_partition *p);
-// independent pieces of one operation list, run side by side (grid.y): [start, start + len) each
-constexpr unsigned kMaxListPieces = 32;
-struct ListPieces {
-  unsigned n = 0;
-  unsigned start[kMaxListPieces] = {0}, len[kMaxListPieces] = {0};
-};
+// (ListPieces, kMaxListPieces: level_op.hpp)
 // most pieces per launch a list of `count` operations of this partition is worth cutting into
 // (0: run the list as it is)
 unsigned clv_traversal_pieces(const rdamd_partition *p, unsigned count);

@@ -63,7 +63,7 @@ model_t::model_t(rooted_tree_t tree, const std::vector<msa_t> &msas,
     unsigned int attributes = RDAMD_ATTRIB_NONREV;
     if (msa.states == 4) attributes |= RDAMD_ATTRIB_SITE_REPEATS;
     // (the shapes rdamd_evaluate_root_children takes: what compute_lh_for_root_steps runs on)
-    if (_sparse && (msa.states == 4 || msa.states == 2 || rdamd::fused20_capable(msa.states, _rate_rates[p].size())))
+    if (_sparse && rdamd::fused_capable(msa.states, _rate_rates[p].size()))
       attributes |= RDAMD_ATTRIB_SPARSE_CLVS;
     rdamd_partition_t *part = rdamd_partition_create(
         _tree.tip_count(), _tree.branch_count(), msa.states, (unsigned)msa.length(), 1,
@@ -475,8 +475,7 @@ double model_t::compute_lh_for_root_steps(const root_location_t &root_location) 
   double lh = 0.0;
   for (size_t i = 0; i < _partitions.size(); ++i) {
     rdamd_partition_t *part = _partitions[i];
-    const unsigned st = rdamd_partition_states(part);
-    if (st == 4 || st == 2 || rdamd::fused20_capable(st, rdamd_partition_rate_cats(part))) {
+    if (rdamd::fused_capable(rdamd_partition_states(part), rdamd_partition_rate_cats(part))) {
       double v = 0.0;
       // (a replica's sparse partition: the children of the LAST root, and whatever else an earlier
       // call named, give their memory back -- nothing reads them after this call)
@@ -597,32 +596,23 @@ std::vector<dlh_t> model_t::compute_dlh_many(const std::vector<root_location_t> 
 // src/model.cpp:481-519: one-sided difference with EPSILON = 1e-8 (backward
 // when alpha + eps would reach 1); both positions go to the device in one call.
 dlh_t model_t::compute_dlh(const root_location_t &root) {
-  constexpr double EPSILON = 1e-8;
-  root_location_t root_prime{root};
-  root_prime.brlen_ratio += EPSILON;
-  double sign = 1.0;
-  if (root_prime.brlen_ratio >= 1.0) {
-    root_prime.brlen_ratio = root.brlen_ratio - EPSILON;
-    sign = -1.0;
-  }
+  double pos[2], sign;
+  dlh_positions(root, pos, &sign);
   auto res = _tree.generate_derivative_operations(root);
   const rdamd_operation_t &op = std::get<0>(res);
   // evaluate alpha' first and alpha last: the partition is left at `root`,
   // where generate_derivative_operations put the tree
-  const double l1[2] = {root_prime.brlen(), root.brlen()};
-  const double l2[2] = {root_prime.brlen_compliment(), root.brlen_compliment()};
+  double l1[2], l2[2];
+  root_location_t at{root};
+  for (int k = 0; k < 2; ++k) {
+    at.brlen_ratio = pos[k];
+    l1[k] = at.brlen();
+    l2[k] = at.brlen_compliment();
+  }
   _n_root_positions += 2;
   double both[2] = {0.0, 0.0};
   root_positions(op, l1, l2, 2, both);
-  const double fxh = both[0], fx = both[1];
-  if (std::isnan(fx))
-    throw std::runtime_error("fx is not finite when computing derivative: " +
-                             std::to_string(root.saved_brlen));
-  if (std::isnan(fxh))
-    throw std::runtime_error("fxh is not finite when computing derivative: " +
-                             std::to_string(root.saved_brlen));
-  if (std::isinf(fxh) && std::isinf(fx)) return {fx, 0};
-  return {fx, (fxh - fx) / EPSILON * sign};
+  return dlh_from(both[1], both[0], sign, root);
 }
 
 void model_t::move_root(const root_location_t &new_root) {
@@ -650,42 +640,51 @@ std::vector<double> model_t::compute_all_root_lh() {
   return out;
 }
 
+// lnL of `roots` on partition p as ONE batch of the fused evaluator: a schedule per root, compiled
+// on `tree` (whose rooting moves) and destroyed on every way out; fill(j, subst, freqs, rates,
+// weights) writes job j's parameters
+std::vector<double> model_t::batch_roots(size_t p, rooted_tree_t &tree, const std::vector<root_location_t> &roots,
+                                         const std::function<void(size_t, double *, double *, double *, double *)> &fill) {
+  rdamd_partition_t *part = _partitions[p];
+  const size_t n = roots.size();
+  const unsigned R = rdamd_partition_rate_cats(part), K = rdamd_partition_states(part), NP = K * K - K;
+  struct owned_t {
+    std::vector<const rdamd_schedule_t *> s;
+    ~owned_t() { for (auto o : s) rdamd_schedule_destroy(const_cast<rdamd_schedule_t *>(o)); }
+  } scheds;
+  std::vector<double> subst(n * NP), freqs(n * K), rates(n * R), weights(n * R), out(n);
+  for (size_t j = 0; j < n; ++j) {
+    auto sc = tree.generate_operations(roots[j]);
+    rdamd_schedule_t *s = rdamd_schedule_create(part, std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(),
+                                                std::get<1>(sc).data(), std::get<2>(sc).data(),
+                                                (unsigned)std::get<1>(sc).size());
+    if (!s) fail("schedule_create");
+    scheds.s.push_back(s);
+    fill(j, &subst[j * NP], &freqs[j * K], &rates[j * R], &weights[j * R]);
+  }
+  if (rdamd_evaluate_batch(part, (unsigned)n, scheds.s.data(), subst.data(), freqs.data(), rates.data(),
+                           weights.data(), out.data()) != RDAMD_SUCCESS)
+    fail("evaluate_batch");
+  return out;
+}
+
 std::vector<double> model_t::compute_all_root_lh_batched() {
   const auto &roots = _tree.roots();
-  const size_t n = roots.size();
-  std::vector<double> total(n, 0.0);
+  std::vector<double> total(roots.size(), 0.0);
   rooted_tree_t scratch(_tree);   // schedules are generated on a copy: _tree keeps its rooting
   for (size_t p = 0; p < _partitions.size(); ++p) {
     rdamd_partition_t *part = _partitions[p];
     const unsigned K = rdamd_partition_states(part), NP = K * K - K;
     if (K != 4 && K != 2 && K != 20)
       throw std::runtime_error("compute_all_root_lh_batched: 4-state, binary or 20-state data only");
-    const unsigned R = rdamd_partition_rate_cats(part);
     const double *cs = rdamd_partition_subst_params(part, 0), *cf = rdamd_partition_frequencies(part, 0);
-    std::vector<rdamd_schedule_t *> owned;
-    std::vector<const rdamd_schedule_t *> scheds(n);
-    std::vector<double> subst(n * NP), freqs(n * K), rates(n * R), weights(n * R), out(n);
-    for (size_t j = 0; j < n; ++j) {
-      auto sc = scratch.generate_operations(roots[j]);
-      rdamd_schedule_t *s = rdamd_schedule_create(
-          part, std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(), std::get<1>(sc).data(),
-          std::get<2>(sc).data(), (unsigned)std::get<1>(sc).size());
-      if (!s) {
-        for (auto o : owned) rdamd_schedule_destroy(o);
-        fail("schedule_create");
-      }
-      owned.push_back(s);
-      scheds[j] = s;
-      std::copy(cs, cs + NP, subst.begin() + j * NP);
-      std::copy(cf, cf + K, freqs.begin() + j * K);
-      std::copy(_rate_rates[p].begin(), _rate_rates[p].end(), rates.begin() + j * R);
-      std::copy(_rate_weights[p].begin(), _rate_weights[p].end(), weights.begin() + j * R);
-    }
-    int ok = rdamd_evaluate_batch(part, (unsigned)n, scheds.data(), subst.data(), freqs.data(),
-                                  rates.data(), weights.data(), out.data());
-    for (auto o : owned) rdamd_schedule_destroy(o);
-    if (ok != RDAMD_SUCCESS) fail("evaluate_batch");
-    for (size_t j = 0; j < n; ++j) total[j] += out[j];
+    const auto out = batch_roots(p, scratch, roots, [&](size_t, double *subst, double *freqs, double *rates, double *weights) {
+      std::copy(cs, cs + NP, subst);
+      std::copy(cf, cf + K, freqs);
+      std::copy(_rate_rates[p].begin(), _rate_rates[p].end(), rates);
+      std::copy(_rate_weights[p].begin(), _rate_weights[p].end(), weights);
+    });
+    for (size_t j = 0; j < out.size(); ++j) total[j] += out[j];
   }
   reduce_values(total.data(), total.size());
   return total;
@@ -739,40 +738,18 @@ std::vector<double> model_t::compute_lh_batch(
   std::vector<double> total(n, 0.0);
   // schedules are per (partition, distinct root): compile once per root
   for (size_t p = 0; p < _partitions.size(); ++p) {
-    const unsigned R = rdamd_partition_rate_cats(_partitions[p]);
-    const unsigned K = rdamd_partition_states(_partitions[p]), NP = K * K - K;
-    std::vector<rdamd_schedule_t *> owned;
-    std::vector<const rdamd_schedule_t *> scheds(n);
-    std::vector<double> subst(n * NP), freqs(n * K), rates(n * R), weights(n * R), out(n);
-    for (size_t j = 0; j < n; ++j) {
-      auto sc = _tree.generate_operations(roots[j]);
-      rdamd_schedule_t *s = rdamd_schedule_create(
-          _partitions[p], std::get<0>(sc).data(), (unsigned)std::get<0>(sc).size(),
-          std::get<1>(sc).data(), std::get<2>(sc).data(), (unsigned)std::get<1>(sc).size());
-      if (!s) {
-        for (auto o : owned) rdamd_schedule_destroy(o);
-        fail("schedule_create");
-      }
-      owned.push_back(s);
-      scheds[j] = s;
+    const unsigned R = rdamd_partition_rate_cats(_partitions[p]), K = rdamd_partition_states(_partitions[p]);
+    const auto out = batch_roots(p, _tree, roots, [&](size_t j, double *subst, double *freqs, double *rates, double *weights) {
       const partition_parameters_t &pp = params[j][p];
-      std::copy(pp.subst_rates.begin(), pp.subst_rates.end(), subst.begin() + j * NP);
+      std::copy(pp.subst_rates.begin(), pp.subst_rates.end(), subst);
       double fs = 0.0;
       for (auto f : pp.freqs) fs += f;
-      for (size_t k = 0; k < K; ++k) freqs[j * K + k] = pp.freqs[k] / fs;
-      std::vector<double> r(R, 1.0);
+      for (size_t k = 0; k < K; ++k) freqs[k] = pp.freqs[k] / fs;
+      std::fill(rates, rates + R, 1.0);
       if (_rate_category_types[p] != rate_category::FREE)
-        rdamd_compute_gamma_cats(pp.gamma_alpha.empty() ? 1.0 : pp.gamma_alpha[0], R, r.data(),
-                                 RDAMD_GAMMA_RATES_MEDIAN);
-      for (unsigned k = 0; k < R; ++k) {
-        rates[j * R + k] = r[k];
-        weights[j * R + k] = _rate_weights[p][k];
-      }
-    }
-    int ok = rdamd_evaluate_batch(_partitions[p], (unsigned)n, scheds.data(), subst.data(),
-                                  freqs.data(), rates.data(), weights.data(), out.data());
-    for (auto o : owned) rdamd_schedule_destroy(o);
-    if (ok != RDAMD_SUCCESS) fail("evaluate_batch");
+        rdamd_compute_gamma_cats(pp.gamma_alpha.empty() ? 1.0 : pp.gamma_alpha[0], R, rates, RDAMD_GAMMA_RATES_MEDIAN);
+      std::copy(_rate_weights[p].begin(), _rate_weights[p].begin() + R, weights);
+    });
     for (size_t j = 0; j < n; ++j) total[j] += out[j];
   }
   reduce_values(total.data(), total.size());
@@ -1174,8 +1151,7 @@ void model_t::optimize_params(std::vector<partition_parameters_t> &params,
     // The batched objective runs on the fused evaluators: 4-state and binary data, and 20
     // states with up to eight rate categories (the 381 finite-difference evaluations of a
     // 20-state rate matrix are one launch of fused20_eval_kernel, src/model.cpp:1490-1502).
-    const unsigned st = rdamd_partition_states(_partitions[i]);
-    if (st != 4 && st != 2 && !rdamd::fused20_capable(st, rdamd_partition_rate_cats(_partitions[i])))
+    if (!rdamd::fused_capable(rdamd_partition_states(_partitions[i]), rdamd_partition_rate_cats(_partitions[i])))
       throw std::runtime_error("optimize_params: the batched objective handles 4-state and binary data, and "
                                "20-state data with up to 8 rate categories");
     // (lock step: this candidate is inside partition i's objective phase from here on)

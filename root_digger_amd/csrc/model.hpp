@@ -346,6 +346,9 @@ private:
   // over the site group: one launch (or one request to the meeting point where it meets the other
   // candidates' steps)
   void root_positions(const rdamd_operation_t &op, const double *l1, const double *l2, unsigned n, double *total);
+  // lnL of `roots` on partition p in one batch of the fused evaluator (model.cpp)
+  std::vector<double> batch_roots(size_t p, rooted_tree_t &tree, const std::vector<root_location_t> &roots,
+                                  const std::function<void(size_t, double *, double *, double *, double *)> &fill);
   double bfgs_params(model_params_t &initial, size_t partition, bfgs_target what,
                      rdamd_schedule_t *sched, double p_min, double p_max,
                      double epsilon, double pgtol, double factor);

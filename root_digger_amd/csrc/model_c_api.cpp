@@ -584,8 +584,7 @@ unsigned int rdamd_model_max_replicas(const rdamd_model_t *m, unsigned int reque
     // all 2n - 3 buffers (RDAMD_ATTRIB_SPARSE_CLVS; their pools start at four slots) -- plus the
     // evaluator's workspace for the one job that writes them
     const unsigned R = (unsigned)ratehets[i].rate_cats;
-    const bool sparse = replicas_are_sparse(m) &&
-                        (msas[i].states == 4 || msas[i].states == 2 || rdamd::fused20_capable(msas[i].states, R));
+    const bool sparse = replicas_are_sparse(m) && rdamd::fused_capable(msas[i].states, R);
     per_replica += rdamd_partition_footprint(tips, sparse ? 4u : branches, msas[i].states, (unsigned)msas[i].length(),
                                              branches, R, sparse ? 4u : branches);
     if (sparse) {

@@ -11,7 +11,7 @@
 #include <dlfcn.h>
 
 #include "clades.hpp"
-#include "k20_split.hpp"
+#include "clv_plan.hpp"
 #include "common.hpp"
 
 namespace rdamd {
@@ -190,6 +190,219 @@ hipError_t op_phys(rdamd_partition *p, const rdamd_operation_t &o, rdamd_operati
   if (e == hipSuccess) e = scaler_phys(p, o.child2_scaler_index, &out->child2_scaler_index);
   return e;
 }
+
+// ---- what several entry points check or do in the same way -----------------------------------
+static bool op_in_range(const rdamd_partition *p, const rdamd_operation_t &o) {
+  return operation_in_range(o, p->tips, p->clv_buffers, p->prob_matrices, p->scale_buffers);
+}
+// the first of the per-rate-category indices (rate matrix / frequency set) that names no rate
+// matrix of the partition, or null
+static const unsigned *bad_rate_index(const rdamd_partition *p, const unsigned *indices) {
+  for (unsigned r = 0; r < p->rate_cats; ++r)
+    if (indices[r] >= p->rate_matrices) return indices + r;
+  return nullptr;
+}
+static bool length_ok(double l) { return l >= 0.0 && std::isfinite(l); }
+// tip tables made for an older set of state codes are rebuilt before a kernel reads them
+static hipError_t flush_tiptab(rdamd_partition *p) {
+  if (!p->tiptab_stale) return hipSuccess;
+  p->stream_dirty = true;
+  const hipError_t e = launch_tiptab_all(p);
+  if (e == hipSuccess) p->tiptab_stale = false;
+  return e;
+}
+// shapes the single-launch root kernels take (root_single_dna_kernel, root_multi_dna_kernel)
+static bool fast_root_shape(const rdamd_partition *p, const rdamd_operation_t &root_op) {
+  const unsigned R = p->rate_cats;
+  return p->states == 4 && p->ncodes_cap == 16 && (R == 1 || R == 2 || R == 4 || R == 8) &&
+         root_op.parent_scaler_index >= 0;
+}
+
+#ifdef RDAMD_ABLATION
+// RDAMD_CLV_DEBUG: what choose_slots (clv_plan.hpp) saw for every launch of several pieces
+static void print_clv_pieces(const ClvPlanInput &in, const ClvPlan &plan, const rdamd_operation_t *ops, unsigned count) {
+  if (in.k20) return;
+  const std::vector<unsigned> &seg = plan.cut.seg;
+  for (size_t l = 0; l + 1 < plan.levels.size(); ++l) {
+    const unsigned s0 = plan.levels[l], s1 = plan.levels[l + 1];
+    if (s1 - s0 < 2) continue;
+    fprintf(stderr, "[clv pieces] launch %zu: %u operations in %u pieces (longest %u); read-backs by slots:", l,
+            seg[s1] - seg[s0], s1 - s0, seg[s0 + 1] - seg[s0]);
+    for (unsigned sl = 0; sl <= in.slots_whole; ++sl) fprintf(stderr, " %u:%u", sl, clv_plan_readbacks(in, plan, ops, count, l, sl));
+    fprintf(stderr, "; chosen %u\n", plan.seg_slots[s0]);
+  }
+  if (plan.levels.size() > 2)
+    fprintf(stderr, "[clv pieces] last launch: %u operations\n", count - seg[plan.levels[plan.levels.size() - 2]]);
+}
+#endif
+
+// what the planner (clv_plan.hpp) needs to know of the partition and its kernels
+static ClvPlanInput clv_plan_input(const rdamd_partition *p, unsigned count) {
+  ClvPlanInput in;
+  in.tips = p->tips; in.clv_buffers = p->clv_buffers; in.prob_matrices = p->prob_matrices;
+  in.scale_buffers = p->scale_buffers; in.sites = p->sites; in.tip_stride = p->tip_stride();
+  in.clv_bytes = (uint64_t)p->clv_doubles() * sizeof(double);
+  in.k20 = p->mfma_layout;   // fixed at creation, with the CLV layout
+  if (in.k20) clv_k20_traversal_cut(p, count, &in.rows, &in.small, &in.min_count);
+  else in.rows = clv_traversal_pieces(p, count);
+  in.slots_whole = clv_traversal_slots(p);
+  in.chunk = clv_traversal_chunk(p);
+#ifdef RDAMD_ABLATION
+  if (getenv("RDAMD_CLV_PIECE_OPS")) in.small = (unsigned)atoi(getenv("RDAMD_CLV_PIECE_OPS"));
+  if (getenv("RDAMD_CLV_MIN_SPLIT")) in.min_count = (unsigned)atoi(getenv("RDAMD_CLV_MIN_SPLIT"));
+  if (getenv("RDAMD_CLV_READBACK_PCT")) in.readback_tolerance_pct = (unsigned)atoi(getenv("RDAMD_CLV_READBACK_PCT"));
+  if (getenv("RDAMD_CLV_PIECE_SLOTS")) in.forced_slots = (int)std::min<unsigned>((unsigned)atoi(getenv("RDAMD_CLV_PIECE_SLOTS")), 6u);
+#endif
+  return in;
+}
+
+// rdamd_root_loglikelihood_fused_multi: room for n_items rows (and their results) in the leader's blocks
+static bool reserve_root_items(rdamd_partition *lead, unsigned n_items) {
+  if (lead->root_items_cap >= n_items) return true;
+  if (lead->d_root_items) (void)hipFree(lead->d_root_items);
+  if (lead->h_root_items) (void)hipHostFree(lead->h_root_items);
+  lead->d_root_items = lead->h_root_items = nullptr;
+  lead->root_items_cap = std::max(64u, n_items * 2);
+  const size_t bytes = (size_t)lead->root_items_cap * (sizeof(RootItem) + kRootMaxPositions * sizeof(double));
+  RDAMD_HIP_TRY(hipMalloc(&lead->d_root_items, bytes), false);
+  RDAMD_HIP_TRY(hipHostMalloc(&lead->h_root_items, bytes, hipHostMallocDefault), false);
+  return true;
+}
+
+// ... and row i: partition p checked and brought up to date, everything root_multi_dna_kernel reads of it
+// (lengths: n_positions of them per child; result: where its kRootMaxPositions values land)
+static bool fill_root_item(rdamd_partition *p, rdamd_partition *lead, unsigned i, const rdamd_operation_t &op,
+                           const unsigned *params_indices, const double *len1, const double *len2,
+                           unsigned n_positions, RootItem &it, double *result) {
+  if (!op_in_range(p, op)) {
+    set_error(10, "rdamd_root_loglikelihood_fused_multi: item %u: index out of range", i);
+    return false;
+  }
+  rdamd_operation_t o;
+  RDAMD_HIP_TRY(op_phys(p, op, &o), false);
+  memset(&it, 0, sizeof it);
+  for (unsigned a = 0; a < kRootMaxPositions; ++a) {   // (unused positions repeat the last one: same state left behind)
+    const unsigned src = std::min(a, n_positions - 1);
+    it.ra.len1[a] = len1[src];
+    it.ra.len2[a] = len2[src];
+    if (!length_ok(it.ra.len1[a]) || !length_ok(it.ra.len2[a])) {
+      set_error(9, "rdamd_root_loglikelihood_fused_multi: item %u: invalid branch length", i);
+      return false;
+    }
+  }
+  if (bad_rate_index(p, params_indices)) {
+    set_error(7, "rdamd_root_loglikelihood_fused_multi: item %u: params index out of range", i);
+    return false;
+  }
+  for (unsigned r = 0; r < 8; ++r) it.ra.params_idx[r] = r < p->rate_cats ? params_indices[r] : 0u;
+  RDAMD_HIP_TRY(flush_q(p), false);
+  RDAMD_HIP_TRY(flush_tiptab(p), false);
+  // whatever this partition's own stream still has queued (parameter uploads just now) must
+  // be done before the leader's stream reads it
+  if (p != lead && (p->stream_dirty || p->stream_external)) RDAMD_HIP_TRY(sync_main(p), false);
+  it.v = p->view();
+  level_op_fields(o, it.op);
+  it.q = p->d_q; it.rates = p->d_rates; it.freqs = p->d_freqs; it.rate_w = p->d_rate_weights;
+  it.pw = p->d_pattern_weights; it.codemask = p->d_codemask;
+  it.partials = p->d_partials; it.counter = p->d_counter;
+  it.result = result;   // (pinned host memory: the folding wave writes it there, no copy launch)
+  it.blocks = root_single_blocks(p);
+  it.ra.n_positions = n_positions;
+  return true;
+}
+
+// rdamd_partition_create: CLV layout, stream, device buffers and pinned blocks of a partition whose sizes are set
+// (false: an error is set; the caller destroys what exists)
+#define TRY(expr) RDAMD_HIP_TRY(expr, false)
+static bool allocate_device_state(rdamd_partition *p) {
+  const unsigned K = p->states, R = p->rate_cats, tips = p->tips, clv_buffers = p->clv_buffers,
+                 scale_buffers = p->scale_buffers, prob_matrices = p->prob_matrices, rate_matrices = p->rate_matrices;
+  const size_t S = p->sites;
+  TRY(hipGetDevice(&p->device));
+  TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  // + kTipcodePad: the traversal kernel reads tip codes with dword-wide scalar
+  // loads that may run a few bytes past the last row
+  TRY(hipMalloc(&p->d_tipcodes, (size_t)tips * p->tip_stride() + kTipcodePad));
+  if (K == 4) {
+    TRY(hipMalloc(&p->d_tipcodes16, (size_t)tips * p->tip_stride() + kTipcodePad));
+    p->code_rows = p->code_rows_cap = tips;
+  }
+  // (the 20-state matrix-core kernel keeps CLVs in its operand layout, whole 16-site tiles:
+  // decided here, before the CLV buffers are sized -- common.hpp)
+  p->mfma_layout = fused20_capable(K, R) &&
+                   (size_t)p->clv_tiles() * 16u * R * K * sizeof(double) < ((size_t)1 << 31) &&
+                   (size_t)prob_matrices * R * k20_mfma_copy_doubles() * sizeof(double) < ((size_t)1 << 31);
+  p->sparse = (p->attributes & RDAMD_ATTRIB_SPARSE_CLVS) != 0;
+  if (p->sparse) {   // a small pool to start with (common.hpp); it grows when more buffers are live at once
+    p->clv_slot.assign(clv_buffers, -1);
+    p->sc_slot.assign(scale_buffers, -1);
+    p->clv_slots_cap = std::min(clv_buffers, 4u);
+    p->sc_slots_cap = std::min(scale_buffers, 4u);
+  }
+  const size_t clv_alloc = p->sparse ? p->clv_slots_cap : clv_buffers, sc_alloc = p->sparse ? p->sc_slots_cap : scale_buffers;
+  TRY(hipMalloc(&p->d_clv, std::max<size_t>(8, clv_alloc * p->clv_doubles() * sizeof(double))));
+  TRY(hipMalloc(&p->d_scaler, std::max<size_t>(4, sc_alloc * S * sizeof(unsigned))));
+  TRY(hipMalloc(&p->d_pmat, (size_t)prob_matrices * R * K * K * sizeof(double)));
+  TRY(hipMalloc(&p->d_tiptab, (size_t)prob_matrices * R * p->ncodes_cap * K * sizeof(double)));
+  if (p->mfma_layout)
+    TRY(hipMalloc(&p->d_pmat_mfma, (size_t)prob_matrices * R * k20_mfma_copy_doubles() * sizeof(double)));
+  TRY(hipMalloc(&p->d_codemask, 256 * sizeof(uint64_t)));
+  TRY(hipMalloc(&p->d_q, (size_t)rate_matrices * K * K * sizeof(double)));
+  TRY(hipMalloc(&p->d_freqs, (size_t)rate_matrices * K * sizeof(double)));
+  TRY(hipMalloc(&p->d_rates, R * sizeof(double)));
+  TRY(hipMalloc(&p->d_rate_weights, R * sizeof(double)));
+  TRY(hipMalloc(&p->d_pattern_weights, std::max<size_t>(4, S * sizeof(unsigned))));
+  TRY(hipMalloc(&p->d_partials, 32768 * sizeof(double)));   // (8 root positions x 1024 blocks x 4 waves)
+  TRY(hipMalloc(&p->d_counter, sizeof(unsigned)));
+  TRY(hipMemsetAsync(p->d_counter, 0, sizeof(unsigned), p->stream));
+  TRY(hipMalloc(&p->d_result, 64 * sizeof(double)));
+  p->stage_bytes = (size_t)4 << 20;
+  TRY(hipHostMalloc(&p->h_stage, p->stage_bytes, hipHostMallocDefault));
+  TRY(hipHostMalloc(&p->h_result, 64 * sizeof(double), hipHostMallocDefault));
+  TRY(ensure_scratch(p, (size_t)1 << 20));
+  TRY(hipMemsetAsync(p->d_scaler, 0, std::max<size_t>(4, sc_alloc * S * sizeof(unsigned)), p->stream));
+  TRY(hipMemsetAsync(p->d_tipcodes, 0, (size_t)tips * p->tip_stride() + kTipcodePad, p->stream));
+  if (K == 4) TRY(hipMemsetAsync(p->d_tipcodes16, 0, (size_t)tips * p->tip_stride() + kTipcodePad, p->stream));
+  return true;
+}
+
+// ... and the host mirrors, with the defaults uploaded
+static bool set_defaults(rdamd_partition *p) {
+  const unsigned K = p->states, R = p->rate_cats, tips = p->tips, rate_matrices = p->rate_matrices;
+  const size_t S = p->sites;
+  // defaults as corax_partition_create leaves them: weights 1, rates 1, 1/R
+  p->subst.assign(rate_matrices, std::vector<double>((size_t)K * K - K, 1.0));
+  p->freqs.assign(rate_matrices, std::vector<double>(K, 1.0 / K));
+  if (p->embedded()) {   // defaults of a 2-state partition, through the embedding setters
+    p->api_subst.assign(rate_matrices, std::vector<double>(2, 1.0));
+    p->api_freqs.assign(rate_matrices, std::vector<double>(2, 0.5));
+    for (unsigned i = 0; i < rate_matrices; ++i) {
+      p->subst[i].assign(12, 0.0);
+      p->subst[i][0] = p->subst[i][3] = 1.0;
+      p->freqs[i] = {0.5, 0.5, 0.0, 0.0};
+    }
+  }
+  p->rates.assign(R, 1.0);
+  p->rate_weights.assign(R, 1.0 / R);
+  p->prop_invar.assign(rate_matrices, 0.0);
+  p->pattern_weights.assign(S, 1u);
+  p->tipcodes.assign((size_t)tips * S, 0);
+  p->q_dirty.assign(rate_matrices, 1);
+  p->codemask.assign(256, 0);
+  if (K == 4) {
+    for (unsigned c = 0; c < 16; ++c) p->codemask[c] = c;
+    p->ncodes = 16;
+  } else {
+    p->ncodes = 0;
+  }
+  TRY(upload(p, p->d_codemask, p->codemask.data(), 256 * sizeof(uint64_t)));
+  TRY(upload(p, p->d_rates, p->rates.data(), R * sizeof(double)));
+  TRY(upload(p, p->d_rate_weights, p->rate_weights.data(), R * sizeof(double)));
+  if (S) TRY(upload(p, p->d_pattern_weights, p->pattern_weights.data(), S * sizeof(unsigned)));
+  TRY(hipStreamSynchronize(p->stream));
+  return true;
+}
+#undef TRY
 }  // namespace rdamd
 
 extern "C" {
@@ -290,87 +503,10 @@ rdamd_partition_t *rdamd_partition_create(unsigned int tips, unsigned int clv_bu
     p->rescale_speculation = mode <= 0 ? 0 : 1;
   }
   p->ncodes_cap = states == 4 ? 16 : 64;
-  const unsigned K = states, R = rate_cats;
-  const size_t S = sites;
-
-#define TRY(expr) RDAMD_HIP_TRY(expr, (rdamd_partition_destroy(p), nullptr))
-  TRY(hipGetDevice(&p->device));
-  TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  // + kTipcodePad: the traversal kernel reads tip codes with dword-wide scalar
-  // loads that may run a few bytes past the last row
-  TRY(hipMalloc(&p->d_tipcodes, (size_t)tips * p->tip_stride() + kTipcodePad));
-  if (K == 4) {
-    TRY(hipMalloc(&p->d_tipcodes16, (size_t)tips * p->tip_stride() + kTipcodePad));
-    p->code_rows = p->code_rows_cap = tips;
+  if (!allocate_device_state(p) || !set_defaults(p)) {
+    rdamd_partition_destroy(p);
+    return nullptr;
   }
-  // (the 20-state matrix-core kernel keeps CLVs in its operand layout, whole 16-site tiles:
-  // decided here, before the CLV buffers are sized -- common.hpp)
-  p->mfma_layout = fused20_capable(K, R) &&
-                   (size_t)p->clv_tiles() * 16u * R * K * sizeof(double) < ((size_t)1 << 31) &&
-                   (size_t)prob_matrices * R * k20_mfma_copy_doubles() * sizeof(double) < ((size_t)1 << 31);
-  p->sparse = (attributes & RDAMD_ATTRIB_SPARSE_CLVS) != 0;
-  if (p->sparse) {   // a small pool to start with (common.hpp); it grows when more buffers are live at once
-    p->clv_slot.assign(clv_buffers, -1);
-    p->sc_slot.assign(scale_buffers, -1);
-    p->clv_slots_cap = std::min(clv_buffers, 4u);
-    p->sc_slots_cap = std::min(scale_buffers, 4u);
-  }
-  const size_t clv_alloc = p->sparse ? p->clv_slots_cap : clv_buffers, sc_alloc = p->sparse ? p->sc_slots_cap : scale_buffers;
-  TRY(hipMalloc(&p->d_clv, std::max<size_t>(8, clv_alloc * p->clv_doubles() * sizeof(double))));
-  TRY(hipMalloc(&p->d_scaler, std::max<size_t>(4, sc_alloc * S * sizeof(unsigned))));
-  TRY(hipMalloc(&p->d_pmat, (size_t)prob_matrices * R * K * K * sizeof(double)));
-  TRY(hipMalloc(&p->d_tiptab, (size_t)prob_matrices * R * p->ncodes_cap * K * sizeof(double)));
-  if (p->mfma_layout)
-    TRY(hipMalloc(&p->d_pmat_mfma, (size_t)prob_matrices * R * k20_mfma_copy_doubles() * sizeof(double)));
-  TRY(hipMalloc(&p->d_codemask, 256 * sizeof(uint64_t)));
-  TRY(hipMalloc(&p->d_q, (size_t)rate_matrices * K * K * sizeof(double)));
-  TRY(hipMalloc(&p->d_freqs, (size_t)rate_matrices * K * sizeof(double)));
-  TRY(hipMalloc(&p->d_rates, R * sizeof(double)));
-  TRY(hipMalloc(&p->d_rate_weights, R * sizeof(double)));
-  TRY(hipMalloc(&p->d_pattern_weights, std::max<size_t>(4, S * sizeof(unsigned))));
-  TRY(hipMalloc(&p->d_partials, 32768 * sizeof(double)));   // (8 root positions x 1024 blocks x 4 waves)
-  TRY(hipMalloc(&p->d_counter, sizeof(unsigned)));
-  TRY(hipMemsetAsync(p->d_counter, 0, sizeof(unsigned), p->stream));
-  TRY(hipMalloc(&p->d_result, 64 * sizeof(double)));
-  p->stage_bytes = (size_t)4 << 20;
-  TRY(hipHostMalloc(&p->h_stage, p->stage_bytes, hipHostMallocDefault));
-  TRY(hipHostMalloc(&p->h_result, 64 * sizeof(double), hipHostMallocDefault));
-  TRY(ensure_scratch(p, (size_t)1 << 20));
-  TRY(hipMemsetAsync(p->d_scaler, 0, std::max<size_t>(4, sc_alloc * S * sizeof(unsigned)), p->stream));
-  TRY(hipMemsetAsync(p->d_tipcodes, 0, (size_t)tips * p->tip_stride() + kTipcodePad, p->stream));
-  if (K == 4) TRY(hipMemsetAsync(p->d_tipcodes16, 0, (size_t)tips * p->tip_stride() + kTipcodePad, p->stream));
-
-  // defaults as corax_partition_create leaves them: weights 1, rates 1, 1/R
-  p->subst.assign(rate_matrices, std::vector<double>((size_t)K * K - K, 1.0));
-  p->freqs.assign(rate_matrices, std::vector<double>(K, 1.0 / K));
-  if (p->embedded()) {   // defaults of a 2-state partition, through the embedding setters
-    p->api_subst.assign(rate_matrices, std::vector<double>(2, 1.0));
-    p->api_freqs.assign(rate_matrices, std::vector<double>(2, 0.5));
-    for (unsigned i = 0; i < rate_matrices; ++i) {
-      p->subst[i].assign(12, 0.0);
-      p->subst[i][0] = p->subst[i][3] = 1.0;
-      p->freqs[i] = {0.5, 0.5, 0.0, 0.0};
-    }
-  }
-  p->rates.assign(R, 1.0);
-  p->rate_weights.assign(R, 1.0 / R);
-  p->prop_invar.assign(rate_matrices, 0.0);
-  p->pattern_weights.assign(S, 1u);
-  p->tipcodes.assign((size_t)tips * S, 0);
-  p->q_dirty.assign(rate_matrices, 1);
-  p->codemask.assign(256, 0);
-  if (K == 4) {
-    for (unsigned c = 0; c < 16; ++c) p->codemask[c] = c;
-    p->ncodes = 16;
-  } else {
-    p->ncodes = 0;
-  }
-  TRY(upload(p, p->d_codemask, p->codemask.data(), 256 * sizeof(uint64_t)));
-  TRY(upload(p, p->d_rates, p->rates.data(), R * sizeof(double)));
-  TRY(upload(p, p->d_rate_weights, p->rate_weights.data(), R * sizeof(double)));
-  if (S) TRY(upload(p, p->d_pattern_weights, p->pattern_weights.data(), S * sizeof(unsigned)));
-  TRY(hipStreamSynchronize(p->stream));
-#undef TRY
   return p;
 }
 
@@ -598,19 +734,17 @@ int rdamd_update_prob_matrices(rdamd_partition_t *p, const unsigned int *params_
   clear_error();
   if (count == 0) return RDAMD_SUCCESS;
   const unsigned R = p->rate_cats;
-  for (unsigned r = 0; r < R; ++r)
-    if (params_indices[r] >= p->rate_matrices) {
-      set_error(7, "rdamd_update_prob_matrices: params index %u out of range",
-                params_indices[r]);
-      return RDAMD_FAILURE;
-    }
+  if (const unsigned *bad = bad_rate_index(p, params_indices)) {
+    set_error(7, "rdamd_update_prob_matrices: params index %u out of range", *bad);
+    return RDAMD_FAILURE;
+  }
   for (unsigned m = 0; m < count; ++m) {
     if (matrix_indices[m] >= p->prob_matrices) {
       set_error(8, "rdamd_update_prob_matrices: matrix index %u out of range",
                 matrix_indices[m]);
       return RDAMD_FAILURE;
     }
-    if (!(branch_lengths[m] >= 0.0) || !std::isfinite(branch_lengths[m])) {
+    if (!length_ok(branch_lengths[m])) {
       set_error(9, "rdamd_update_prob_matrices: invalid branch length %g for matrix %u",
                 branch_lengths[m], matrix_indices[m]);
       return RDAMD_FAILURE;
@@ -646,7 +780,6 @@ void rdamd_update_clvs(rdamd_partition_t *p, const rdamd_operation_t *ops,
                        unsigned int count) {
   clear_error();
   if (count == 0) return;
-  const unsigned nclv = p->tips + p->clv_buffers;
   std::vector<rdamd_operation_t> phys_ops;
   if (p->sparse) {   // from here on the list names pool slots (common.hpp)
     phys_ops.resize(count);
@@ -660,255 +793,28 @@ void rdamd_update_clvs(rdamd_partition_t *p, const rdamd_operation_t *ops,
     }
     ops = phys_ops.data();
   }
-  // Independent subtrees side by side, level by level (k20_split.hpp, list_levels): the 20-state
-  // kernel always (kernels_clv_mfma.hip), the 4-state one where one row of blocks leaves the device's
-  // wave slots empty (kernels_clv.hip).
-  ListLevels lv;
-  {
-    unsigned rows = 0, small = 8, min_count = 16;
-    if (p->mfma_layout) clv_k20_traversal_cut(p, count, &rows, &small, &min_count);
-    else rows = clv_traversal_pieces(p, count);
-#ifdef RDAMD_ABLATION
-    if (getenv("RDAMD_CLV_PIECE_OPS")) small = (unsigned)atoi(getenv("RDAMD_CLV_PIECE_OPS"));
-    if (getenv("RDAMD_CLV_MIN_SPLIT")) min_count = (unsigned)atoi(getenv("RDAMD_CLV_MIN_SPLIT"));
-#endif
-    if (rows >= 2) list_levels(p->tips, p->clv_buffers, ops, count, rows, small, min_count, lv, p->mfma_layout);
-  }
-  if (!lv.order.empty()) ops = lv.order.data();
-  std::vector<LevelOp> lops(count);
-  for (unsigned i = 0; i < count; ++i) {
-    const rdamd_operation_t &o = ops[i];
-    if (o.parent_clv_index < p->tips || o.parent_clv_index >= nclv ||
-        o.child1_clv_index >= nclv || o.child2_clv_index >= nclv ||
-        o.child1_matrix_index >= p->prob_matrices ||
-        o.child2_matrix_index >= p->prob_matrices ||
-        o.parent_scaler_index >= (int)p->scale_buffers ||
-        o.child1_scaler_index >= (int)p->scale_buffers ||
-        o.child2_scaler_index >= (int)p->scale_buffers) {
-      set_error(10, "rdamd_update_clvs: operation %u has an index out of range", i);
-      return;
-    }
-    LevelOp &d = lops[i];
-    d.parent_clv = o.parent_clv_index; d.child1_clv = o.child1_clv_index;
-    d.child2_clv = o.child2_clv_index; d.child1_mat = o.child1_matrix_index;
-    d.child2_mat = o.child2_matrix_index; d.parent_sc = o.parent_scaler_index;
-    d.child1_sc = o.child1_scaler_index; d.child2_sc = o.child2_scaler_index;
-    d.src1 = o.child1_clv_index < p->tips ? 0u : 1u;
-    d.src2 = o.child2_clv_index < p->tips ? 0u : 1u;
-    d.park = d.noop = 0;
-    const uint64_t clv_bytes = (uint64_t)p->clv_doubles() * sizeof(double);
-    auto sc_off = [&](int scb) {
-      return scb >= 0 ? (uint64_t)scb * p->sites * sizeof(unsigned) : kNoOffset;
-    };
-    auto child_off = [&](unsigned clv) {
-      return clv < p->tips ? (uint64_t)clv * p->tip_stride() : (uint64_t)(clv - p->tips) * clv_bytes;
-    };
-    d.parent_off = (uint64_t)(d.parent_clv - p->tips) * clv_bytes;
-    d.parent_sc_off = sc_off(d.parent_sc);
-    d.child1_off = child_off(d.child1_clv); d.child1_sc_off = sc_off(d.child1_sc);
-    d.child2_off = child_off(d.child2_clv); d.child2_sc_off = sc_off(d.child2_sc);
-  }
-  // Where does each inner child come from?  The parent of the operation just
-  // before stays in the lane's registers; an older sibling waits in one of the
-  // kernel's LDS parking slots when one is free (shortest wait wins: when the
-  // slots are full the value needed furthest in the future gives its slot up
-  // and is read back from HBM instead -- every CLV is written there anyway).
-  // A child is forwarded only when its scaler index is the producer's.
-  // (`cuts` splits a list into segments, each analysed on its own: the pieces of a split list, which
-  // run side by side with the slots their row count leaves them, then the operations that join them;
-  // the 4-state kernel needs no other cut -- memory children are read at use, after every earlier
-  // store of the lane.)
-  const unsigned slots_whole = clv_traversal_slots(p);
-  // segment boundaries, and the first segment of every launch (segments [levels[l], levels[l + 1])
-  // run side by side)
-  std::vector<unsigned> cuts{0u}, levels{0u};
-  if (!lv.order.empty()) {
-    cuts.assign(lv.seg.begin(), lv.seg.end() - 1);
-    levels.assign(lv.level.begin(), lv.level.end() - 1);
-  }
-  // The 20-state kernel requests the operands of operation i+1 a whole
-  // operation ahead and stores the result of operation i one operation late:
-  // operation i may not read from memory what i-1 or i-2 wrote.  Their parents
-  // are forwarded in registers (sources 2 and 3 below) -- except where the
-  // value cannot be forwarded (same CLV under another scaler index, or the
-  // other way round, or both earlier operations wrote it): there the list is
-  // cut into two launches.
-  // (No piece of a cut list has such a place -- list_levels has checked --; the list that is left
-  // over, or the whole list, may.)
-  const bool use_k20 = p->mfma_layout;   // fixed at creation, with the CLV layout
-  if (use_k20)
-    for (unsigned i = cuts.back() + 1; i < count; ++i)
-      if (k20_hazard(p->tips, ops, i, cuts.back())) {
-        cuts.push_back(i);
-        levels.push_back((unsigned)cuts.size() - 1);
-      }
-  cuts.push_back(count);
-  levels.push_back((unsigned)cuts.size() - 1);
-  std::vector<int> producer(nclv, -1), consumer(count), which(count);
-  // one segment with `nslots` parking slots; returns the number of children it reads back from memory
-  // (producer: clv -> op of this segment that wrote it; all -1 between calls)
-  auto analyse = [&](unsigned lo, unsigned hi, unsigned nslots) {
-    for (unsigned i = lo; i < hi; ++i) {
-      consumer[i] = -1;   // op -> first later op reading its parent
-      lops[i].src1 = ops[i].child1_clv_index < p->tips ? 0u : 1u;
-      lops[i].src2 = ops[i].child2_clv_index < p->tips ? 0u : 1u;
-      if (!use_k20) lops[i].park = 0;
-    }
-    for (unsigned i = lo; i < hi; ++i) {
-      const rdamd_operation_t &o = ops[i];
-      const unsigned ch[2] = {o.child1_clv_index, o.child2_clv_index};
-      const int chsc[2] = {o.child1_scaler_index, o.child2_scaler_index};
-      for (int c = 0; c < 2; ++c) {
-        if (ch[c] < p->tips || (!use_k20 && c == 1 && ch[1] == ch[0])) continue;
-        const int j = producer[ch[c]];
-        if (use_k20) {
-          // the 20-state kernel keeps the results of the last TWO operations in
-          // registers and forwards them to every reader (source 2: the operation
-          // just before, 3: the one before that)
-          if (j >= 0 && (int)i - j <= 2 && ops[j].parent_scaler_index == chsc[c])
-            (c ? lops[i].src2 : lops[i].src1) = (int)i - j == 1 ? 2u : 3u;
-          continue;
-        }
-        if (j >= 0 && consumer[j] < 0 && ops[j].parent_scaler_index == chsc[c]) {
-          consumer[j] = (int)i;
-          which[j] = c;
-        }
-      }
-      producer[o.parent_clv_index] = (int)i;
-    }
-    std::vector<int> slot_owner(nslots, -1);
-    auto set_src = [&](int j, unsigned kind) {
-      LevelOp &c = lops[consumer[j]];
-      (which[j] ? c.src2 : c.src1) = kind;
-    };
-    for (unsigned i = lo; i < hi; ++i) {
-      for (unsigned sl = 0; sl < nslots; ++sl)      // slots whose value is consumed now
-        if (slot_owner[sl] >= 0 && consumer[slot_owner[sl]] == (int)i) slot_owner[sl] = -1;
-      const int c = consumer[i];
-      if (c < 0) continue;
-      // (consumer[i] was taken from producer[] at the time the consumer was
-      // scanned, i.e. op i is the LAST writer of that CLV before it: nothing
-      // in between can have overwritten the value)
-      if (c == (int)i + 1) {
-        set_src((int)i, 2u);
-        // the same CLV as both children: both come from the registers
-        if (ops[c].child1_clv_index == ops[c].child2_clv_index &&
-            ops[c].child1_scaler_index == ops[c].child2_scaler_index)
-          lops[c].src1 = lops[c].src2 = 2u;
-        continue;
-      }
-      if (nslots == 0) continue;
-      int take = -1, far = -1;
-      for (unsigned sl = 0; sl < nslots; ++sl) {
-        if (slot_owner[sl] < 0) { take = (int)sl; far = -1; break; }
-        if (far < 0 || consumer[slot_owner[sl]] > consumer[slot_owner[far]]) far = (int)sl;
-      }
-      if (take < 0 && far >= 0 && consumer[slot_owner[far]] > c) {
-        const int ev = slot_owner[far];             // give the slot to the shorter wait
-        set_src(ev, 1u);
-        lops[ev].park = 0;
-        take = far;
-      }
-      if (take >= 0) {
-        slot_owner[take] = (int)i;
-        lops[i].park = 1u + (unsigned)take;
-        set_src((int)i, 3u + (unsigned)take);
-      }
-    }
-    unsigned readbacks = 0;
-    for (unsigned i = lo; i < hi; ++i) {
-      if (consumer[i] >= 0 && (which[i] ? lops[consumer[i]].src2 : lops[consumer[i]].src1) == 1u) ++readbacks;
-      producer[ops[i].parent_clv_index] = -1;
-    }
-    return readbacks;
-  };
-  // The pieces of a launch share one slot count: the fewest slots that leave no more read-backs than
-  // the whole-list count would, plus 6 in 100 operations (every slot less is LDS for another resident
-  // block, a read-back is one exposed round trip of one piece; measured, profiles/r5_clv_pieces_ab.txt:
-  // c2 in 8 pieces 162 / 172 / 189 us with 1 / 2 / 3 slots and 2 / 0 / 0 read-backs; c5's shard in
-  // 32 pieces 1.67 / 1.60 / 1.73 ms with 74 / 31 / 13).
-  std::vector<unsigned> seg_slots(cuts.size() - 1, slots_whole);
-  for (size_t l = 0; !use_k20 && l + 1 < levels.size(); ++l) {
-    const unsigned s0 = levels[l], s1 = levels[l + 1];
-    if (s1 - s0 < 2) continue;
-    auto level_readbacks = [&](unsigned nslots) {
-      unsigned n = 0;
-      for (unsigned seg = s0; seg < s1; ++seg) n += analyse(cuts[seg], cuts[seg + 1], nslots);
-      return n;
-    };
-    unsigned tolerance = 6;
-#ifdef RDAMD_ABLATION
-    if (getenv("RDAMD_CLV_READBACK_PCT")) tolerance = (unsigned)atoi(getenv("RDAMD_CLV_READBACK_PCT"));
-#endif
-    const unsigned allowed = level_readbacks(slots_whole) + (cuts[s1] - cuts[s0]) * tolerance / 100;
-    unsigned chosen = slots_whole;
-    while (chosen > 0 && level_readbacks(chosen - 1) <= allowed) --chosen;
-#ifdef RDAMD_ABLATION
-    if (getenv("RDAMD_CLV_PIECE_SLOTS")) chosen = std::min<unsigned>((unsigned)atoi(getenv("RDAMD_CLV_PIECE_SLOTS")), 6u);
-    if (getenv("RDAMD_CLV_DEBUG")) {
-      fprintf(stderr, "[clv pieces] launch %zu: %u operations in %u pieces (longest %u); read-backs by slots:", l,
-              cuts[s1] - cuts[s0], s1 - s0, cuts[s0 + 1] - cuts[s0]);
-      for (unsigned sl = 0; sl <= slots_whole; ++sl) fprintf(stderr, " %u:%u", sl, level_readbacks(sl));
-      fprintf(stderr, "; chosen %u\n", chosen);
-    }
-#endif
-    for (unsigned seg = s0; seg < s1; ++seg) seg_slots[seg] = chosen;
+  const ClvPlanInput in = clv_plan_input(p, count);
+  const ClvPlan plan = plan_clv_traversal(in, ops, count);
+  if (plan.bad_op >= 0) {
+    set_error(10, "rdamd_update_clvs: operation %u has an index out of range", (unsigned)plan.bad_op);
+    return;
   }
 #ifdef RDAMD_ABLATION
-  if (getenv("RDAMD_CLV_DEBUG") && !use_k20 && levels.size() > 2)
-    fprintf(stderr, "[clv pieces] last launch: %u operations\n", count - cuts[levels[levels.size() - 2]]);
+  if (getenv("RDAMD_CLV_DEBUG")) print_clv_pieces(in, plan, ops, count);
 #endif
-  for (size_t seg = 0; seg + 1 < cuts.size(); ++seg) analyse(cuts[seg], cuts[seg + 1], seg_slots[seg]);
-  // Each segment (normally the whole list) runs as one launch in the caller's
-  // order: every dependency is site-local, so the kernel needs no level
-  // structure (kernels_clv.hip).
-  if (!use_k20) {   // every segment padded to whole chunks with no-ops (a copy of its last op, stores off)
-    const unsigned chunk = clv_traversal_chunk(p);
-    std::vector<LevelOp> padded_ops;
-    std::vector<unsigned> padded_cuts{0u};
-    padded_ops.reserve(count + cuts.size() * chunk + 1);
-    LevelOp pad{};
-    for (size_t seg = 0; seg + 1 < cuts.size(); ++seg) {
-      padded_ops.insert(padded_ops.end(), lops.begin() + cuts[seg], lops.begin() + cuts[seg + 1]);
-      pad = lops[cuts[seg + 1] - 1];
-      pad.src1 = pad.src2 = 2u;
-      pad.park = 0;
-      pad.noop = 1;
-      while ((padded_ops.size() - padded_cuts.back()) % chunk) padded_ops.push_back(pad);
-      padded_cuts.push_back((unsigned)padded_ops.size());
-    }
-    padded_ops.push_back(pad);   // terminator: the kernel looks one operation ahead (a segment's last
-                                 // operation looks at the next segment's first: tip codes it never uses)
-    lops.swap(padded_ops);
-    cuts.swap(padded_cuts);
-  }
-  if (use_k20)   // tip-code look-ahead of the 20-state kernel (LevelOp::ahead*)
-    for (unsigned i = 0; i < count; ++i) {
-      const bool more = i + 1 < count;
-      lops[i].ahead1 = more && lops[i + 1].src1 == 0u ? lops[i + 1].child1_clv : 0u;
-      lops[i].ahead2 = more && lops[i + 1].src2 == 0u ? lops[i + 1].child2_clv : 0u;
-    }
-  const size_t padded = lops.size();
-  hipError_t e = ensure_scratch(p, sizeof(LevelOp) * padded + 256);
-  if (e == hipSuccess && p->tiptab_stale) {
-    e = (p->stream_dirty = true, launch_tiptab_all(p));
-    p->tiptab_stale = false;
-  }
+  const size_t bytes = sizeof(LevelOp) * plan.lops.size();
+  hipError_t e = ensure_scratch(p, bytes + 256);
+  if (e == hipSuccess) e = flush_tiptab(p);
   Scratch sc{p};
   if (e == hipSuccess) {
-    LevelOp *d_ops = (LevelOp *)sc.take(sizeof(LevelOp) * padded);
-    e = upload(p, d_ops, lops.data(), sizeof(LevelOp) * padded);
+    LevelOp *d_ops = (LevelOp *)sc.take(bytes);
+    e = upload(p, d_ops, plan.lops.data(), bytes);
     p->prof_begin(0);
     // one launch per level of the cut: its pieces side by side
-    for (size_t l = 0; e == hipSuccess && l + 1 < levels.size(); ++l) {
-      ListPieces pc;
-      for (unsigned seg = levels[l]; seg < levels[l + 1]; ++seg) {
-        pc.start[pc.n] = cuts[seg];
-        pc.len[pc.n++] = cuts[seg + 1] - cuts[seg];
-      }
-      e = use_k20 ? launch_clv_k20_traversal(p, d_ops, pc) : launch_clv_traversal(p, d_ops, pc, seg_slots[levels[l]]);
-    }
-    p->last_clv_launches = (unsigned)levels.size() - 1;
+    for (size_t l = 0; e == hipSuccess && l < plan.launches(); ++l)
+      e = in.k20 ? launch_clv_k20_traversal(p, d_ops, plan.pieces(l))
+                 : launch_clv_traversal(p, d_ops, plan.pieces(l), plan.seg_slots[plan.levels[l]]);
+    p->last_clv_launches = plan.launches();
     p->prof_end();
   }
   if (e != hipSuccess)
@@ -927,11 +833,10 @@ double rdamd_compute_root_loglikelihood(rdamd_partition_t *p, unsigned int clv_i
               clv_index, scaler_index);
     return nan;
   }
-  for (unsigned r = 0; r < p->rate_cats; ++r)
-    if (freqs_indices[r] >= p->rate_matrices) {
-      set_error(7, "rdamd_compute_root_loglikelihood: freqs index out of range");
-      return nan;
-    }
+  if (bad_rate_index(p, freqs_indices)) {
+    set_error(7, "rdamd_compute_root_loglikelihood: freqs index out of range");
+    return nan;
+  }
   if (p->sites == 0) return 0.0;   // an empty alignment has likelihood 1
   RDAMD_HIP_TRY(clv_phys(p, clv_index, &clv_index), nan);
   RDAMD_HIP_TRY(scaler_phys(p, scaler_index, &scaler_index), nan);
@@ -980,11 +885,10 @@ int rdamd_compute_root_loglikelihoods(rdamd_partition_t *p, unsigned int count,
     }
     scaler_indices = phys_sc.data();
   }
-  for (unsigned r = 0; r < p->rate_cats; ++r)
-    if (freqs_indices[r] >= p->rate_matrices) {
-      set_error(7, "rdamd_compute_root_loglikelihoods: freqs index out of range");
-      return RDAMD_FAILURE;
-    }
+  if (bad_rate_index(p, freqs_indices)) {
+    set_error(7, "rdamd_compute_root_loglikelihoods: freqs index out of range");
+    return RDAMD_FAILURE;
+  }
   if (p->sites == 0) {
     std::fill(lnl_out, lnl_out + count, 0.0);
     return RDAMD_SUCCESS;
@@ -1019,15 +923,11 @@ int rdamd_root_loglikelihood_fused(rdamd_partition_t *p, const rdamd_operation_t
                                    unsigned int n_alpha, double *lnl_out) {
   clear_error();
   if (n_alpha == 0) return RDAMD_SUCCESS;
-  const unsigned R = p->rate_cats, K = p->states;
   if (p->sites == 0) {
     std::fill(lnl_out, lnl_out + n_alpha, 0.0);
     return RDAMD_SUCCESS;
   }
-  const bool fast = K == 4 && p->ncodes_cap == 16 &&
-                    (R == 1 || R == 2 || R == 4 || R == 8) &&
-                    root_op->parent_scaler_index >= 0;
-  if (!fast) {
+  if (!fast_root_shape(p, *root_op)) {
     // generic shapes: the three calls queued back to back on the partition stream
     for (unsigned a = 0; a < n_alpha; ++a) {
       unsigned mi[2] = {root_op->child1_matrix_index, root_op->child2_matrix_index};
@@ -1042,30 +942,19 @@ int rdamd_root_loglikelihood_fused(rdamd_partition_t *p, const rdamd_operation_t
     }
     return RDAMD_SUCCESS;
   }
-  const unsigned nclv = p->tips + p->clv_buffers;
-  if (root_op->parent_clv_index < p->tips || root_op->parent_clv_index >= nclv ||
-      root_op->child1_clv_index >= nclv || root_op->child2_clv_index >= nclv ||
-      root_op->child1_matrix_index >= p->prob_matrices ||
-      root_op->child2_matrix_index >= p->prob_matrices ||
-      root_op->parent_scaler_index >= (int)p->scale_buffers ||
-      root_op->child1_scaler_index >= (int)p->scale_buffers ||
-      root_op->child2_scaler_index >= (int)p->scale_buffers) {
+  if (!op_in_range(p, *root_op)) {
     set_error(10, "rdamd_root_loglikelihood_fused: index out of range");
     return RDAMD_FAILURE;
   }
-  for (unsigned r = 0; r < R; ++r)
-    if (params_indices[r] >= p->rate_matrices) {
-      set_error(7, "rdamd_root_loglikelihood_fused: params index out of range");
-      return RDAMD_FAILURE;
-    }
+  if (bad_rate_index(p, params_indices)) {
+    set_error(7, "rdamd_root_loglikelihood_fused: params index out of range");
+    return RDAMD_FAILURE;
+  }
   rdamd_operation_t phys_root;
   RDAMD_HIP_TRY(op_phys(p, *root_op, &phys_root), RDAMD_FAILURE);
   root_op = &phys_root;
   RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
-  if (p->tiptab_stale) {
-    RDAMD_HIP_TRY((p->stream_dirty = true, launch_tiptab_all(p)), RDAMD_FAILURE);
-    p->tiptab_stale = false;
-  }
+  RDAMD_HIP_TRY(flush_tiptab(p), RDAMD_FAILURE);
   // One launch per chunk of up to eight positions (four at 8 rate categories;
   // root_single_dna_kernel): branch
   // lengths and parameter indices travel as kernel arguments, the P-matrices are
@@ -1073,18 +962,14 @@ int rdamd_root_loglikelihood_fused(rdamd_partition_t *p, const rdamd_operation_t
   // The LAST position of the call leaves its matrices, root CLV and scaler in the
   // partition, exactly as the unfused call sequence would.
   LevelOp op;
-  op.parent_clv = root_op->parent_clv_index; op.child1_clv = root_op->child1_clv_index;
-  op.child2_clv = root_op->child2_clv_index; op.child1_mat = root_op->child1_matrix_index;
-  op.child2_mat = root_op->child2_matrix_index; op.parent_sc = root_op->parent_scaler_index;
-  op.child1_sc = root_op->child1_scaler_index; op.child2_sc = root_op->child2_scaler_index;
+  level_op_fields(*root_op, op);
   op.src1 = op.src2 = 0;
   for (unsigned a = 0; a < n_alpha; ++a)
-    if (!(lengths1[a] >= 0.0) || !(lengths2[a] >= 0.0) || !std::isfinite(lengths1[a]) ||
-        !std::isfinite(lengths2[a])) {
+    if (!length_ok(lengths1[a]) || !length_ok(lengths2[a])) {
       set_error(9, "rdamd_root_loglikelihood_fused: invalid branch length");
       return RDAMD_FAILURE;
     }
-  const unsigned chunk = root_single_max_positions(R);
+  const unsigned chunk = root_single_max_positions(p->rate_cats);
   for (unsigned base = 0; base < n_alpha; base += chunk) {
     const unsigned n = std::min(chunk, n_alpha - base);
     p->prof_begin(2);
@@ -1113,13 +998,11 @@ int rdamd_root_loglikelihood_fused_multi(unsigned int n_items, rdamd_partition_t
   clear_error();
   if (n_items == 0) return RDAMD_SUCCESS;
   bool fast = true;
-  unsigned max_pos = 0, max_blocks = 0;
   for (unsigned i = 0; i < n_items; ++i) {
     const rdamd_partition *p = parts[i];
-    fast = fast && p->states == 4 && p->ncodes_cap == 16 && p->rate_cats == parts[0]->rate_cats &&
-           (p->rate_cats == 1 || p->rate_cats == 2 || p->rate_cats == 4 || p->rate_cats == 8) &&
-           ops[i].parent_scaler_index >= 0 && p->sites > 0 && p->device == parts[0]->device &&
-           n_positions[i] >= 1 && n_positions[i] <= root_single_max_positions(p->rate_cats);
+    fast = fast && fast_root_shape(p, ops[i]) && p->rate_cats == parts[0]->rate_cats && p->sites > 0 &&
+           p->device == parts[0]->device && n_positions[i] >= 1 &&
+           n_positions[i] <= root_single_max_positions(p->rate_cats);
   }
   if (!fast || n_items == 1) {
     for (unsigned i = 0; i < n_items; ++i)
@@ -1129,75 +1012,21 @@ int rdamd_root_loglikelihood_fused_multi(unsigned int n_items, rdamd_partition_t
     return RDAMD_SUCCESS;
   }
   rdamd_partition *lead = parts[0];
-  const unsigned R = lead->rate_cats;
-  if (lead->root_items_cap < n_items) {
-    if (lead->d_root_items) (void)hipFree(lead->d_root_items);
-    if (lead->h_root_items) (void)hipHostFree(lead->h_root_items);
-    lead->d_root_items = lead->h_root_items = nullptr;
-    lead->root_items_cap = std::max(64u, n_items * 2);
-    const size_t bytes = (size_t)lead->root_items_cap * (sizeof(RootItem) + kRootMaxPositions * sizeof(double));
-    RDAMD_HIP_TRY(hipMalloc(&lead->d_root_items, bytes), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipHostMalloc(&lead->h_root_items, bytes, hipHostMallocDefault), RDAMD_FAILURE);
-  }
+  if (!reserve_root_items(lead, n_items)) return RDAMD_FAILURE;
   RootItem *h_items = (RootItem *)lead->h_root_items, *d_items = (RootItem *)lead->d_root_items;
   double *h_res = (double *)(h_items + lead->root_items_cap);
+  unsigned max_pos = 0, max_blocks = 0;
   for (unsigned i = 0; i < n_items; ++i) {
-    rdamd_partition *p = parts[i];
-    const unsigned nclv = p->tips + p->clv_buffers;
-    if (ops[i].parent_clv_index < p->tips || ops[i].parent_clv_index >= nclv || ops[i].child1_clv_index >= nclv ||
-        ops[i].child2_clv_index >= nclv || ops[i].child1_matrix_index >= p->prob_matrices ||
-        ops[i].child2_matrix_index >= p->prob_matrices || ops[i].parent_scaler_index >= (int)p->scale_buffers ||
-        ops[i].child1_scaler_index >= (int)p->scale_buffers || ops[i].child2_scaler_index >= (int)p->scale_buffers) {
-      set_error(10, "rdamd_root_loglikelihood_fused_multi: item %u: index out of range", i);
+    if (!fill_root_item(parts[i], lead, i, ops[i], params_indices[i], len1 + 8 * i, len2 + 8 * i, n_positions[i],
+                        h_items[i], h_res + kRootMaxPositions * i))
       return RDAMD_FAILURE;
-    }
-    rdamd_operation_t o;
-    RDAMD_HIP_TRY(op_phys(p, ops[i], &o), RDAMD_FAILURE);
-    RootItem &it = h_items[i];
-    memset(&it, 0, sizeof it);
-    for (unsigned a = 0; a < kRootMaxPositions; ++a) {   // (unused positions repeat the last one: same state left behind)
-      const unsigned src = std::min(a, n_positions[i] - 1);
-      it.ra.len1[a] = len1[8 * i + src];
-      it.ra.len2[a] = len2[8 * i + src];
-      if (!(it.ra.len1[a] >= 0.0) || !(it.ra.len2[a] >= 0.0) || !std::isfinite(it.ra.len1[a]) ||
-          !std::isfinite(it.ra.len2[a])) {
-        set_error(9, "rdamd_root_loglikelihood_fused_multi: item %u: invalid branch length", i);
-        return RDAMD_FAILURE;
-      }
-    }
-    for (unsigned r = 0; r < 8; ++r) {
-      it.ra.params_idx[r] = r < R ? params_indices[i][r] : 0u;
-      if (it.ra.params_idx[r] >= p->rate_matrices) {
-        set_error(7, "rdamd_root_loglikelihood_fused_multi: item %u: params index out of range", i);
-        return RDAMD_FAILURE;
-      }
-    }
-    RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
-    if (p->tiptab_stale) {
-      RDAMD_HIP_TRY((p->stream_dirty = true, launch_tiptab_all(p)), RDAMD_FAILURE);
-      p->tiptab_stale = false;
-    }
-    // whatever this partition's own stream still has queued (parameter uploads just now) must
-    // be done before the leader's stream reads it
-    if (p != lead && (p->stream_dirty || p->stream_external)) RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
-    it.v = p->view();
-    it.op.parent_clv = o.parent_clv_index; it.op.child1_clv = o.child1_clv_index;
-    it.op.child2_clv = o.child2_clv_index; it.op.child1_mat = o.child1_matrix_index;
-    it.op.child2_mat = o.child2_matrix_index; it.op.parent_sc = o.parent_scaler_index;
-    it.op.child1_sc = o.child1_scaler_index; it.op.child2_sc = o.child2_scaler_index;
-    it.q = p->d_q; it.rates = p->d_rates; it.freqs = p->d_freqs; it.rate_w = p->d_rate_weights;
-    it.pw = p->d_pattern_weights; it.codemask = p->d_codemask;
-    it.partials = p->d_partials; it.counter = p->d_counter;
-    it.result = h_res + kRootMaxPositions * i;   // (pinned host memory: the folding wave writes it there, no copy launch)
-    it.blocks = root_single_blocks(p);
-    it.ra.n_positions = n_positions[i];
     max_pos = std::max(max_pos, n_positions[i]);
-    max_blocks = std::max(max_blocks, it.blocks);
+    max_blocks = std::max(max_blocks, h_items[i].blocks);
   }
   RDAMD_HIP_TRY(hipMemcpyAsync(d_items, h_items, sizeof(RootItem) * n_items, hipMemcpyHostToDevice, lead->stream),
                 RDAMD_FAILURE);
   lead->prof_begin(2);
-  hipError_t e = launch_root_multi(d_items, n_items, R, max_pos, max_blocks, lead->stream);
+  hipError_t e = launch_root_multi(d_items, n_items, lead->rate_cats, max_pos, max_blocks, lead->stream);
   lead->prof_end();
   RDAMD_HIP_TRY(e, RDAMD_FAILURE);
   RDAMD_HIP_TRY(sync_main(lead), RDAMD_FAILURE);

@@ -1,4 +1,4 @@
-// CPU check of three pieces of pure host logic added in round 3 (no HIP, no GPU):
+// CPU check of the pure host logic that shapes kernel launches (no HIP, no GPU):
 //   * clade_classes (csrc/clade_classes.hpp): the pattern classes of a subtree -- what decides
 //     which clades the fused evaluator folds into look-up tables -- against a brute-force count;
 //   * k20_split (csrc/k20_split.hpp): cutting a post-order operation list into independent
@@ -8,6 +8,10 @@
 //     symbolically: the running value at the end must be the root's CLV expression, every pop
 //     must meet the sibling that was parked for it, for 4-state (one / two register levels,
 //     pseudo-tips) and 20-state (parking as a step of its own) programs.
+//   * the CLV traversal planner (csrc/clv_plan.hpp): every plan replayed symbolically -- each child
+//     source names a value that is really there (tip, the registers of the operation(s) in front,
+//     an LDS parking slot nobody has overwritten), segments, padding, slot counts and the 20-state
+//     look-ahead are what the traversal kernels rely on.
 // prints "host logic OK <cases>" on success.
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +21,7 @@
 #include <vector>
 
 #include "clade_classes.hpp"
+#include "clv_plan.hpp"
 #include "k20_split.hpp"
 #include "traversal_compiler.hpp"
 
@@ -257,6 +262,182 @@ static int check_compiler(std::mt19937 &rng, int &cases) {
   return 0;
 }
 
+
+// ---- the CLV traversal planner ---------------------------------------------------------------
+// one plan against what the traversal kernels (kernels_clv.hip, kernels_clv_mfma.hip) take for granted
+static int replay_plan(const rdamd::ClvPlanInput &in, const std::vector<rdamd_operation_t> &given, const rdamd::ClvPlan &plan) {
+  using namespace rdamd;
+  const unsigned count = (unsigned)given.size(), tips = in.tips;
+  const std::vector<rdamd_operation_t> &ops = plan.cut.order.empty() ? given : plan.cut.order;
+  if (plan.bad_op >= 0) return fail("plan: an operation in range was refused", plan.bad_op);
+  if (ops.size() != count) return fail("plan: the cut list is no permutation (size)");
+  const std::vector<unsigned> &cuts = plan.cuts, &levels = plan.levels;
+  if (cuts.size() < 2 || cuts.front() != 0 || levels.size() < 2 || levels.front() != 0 || levels.back() != cuts.size() - 1 ||
+      plan.seg_slots.size() != cuts.size() - 1 || plan.launches() != levels.size() - 1)
+    return fail("plan: segment / launch bounds");
+  if (plan.lops.size() != cuts.back() + (in.k20 ? 0u : 1u)) return fail("plan: list length", (int)plan.lops.size(), (int)cuts.back());
+  if (in.k20 && cuts.back() != count) return fail("plan: a 20-state list is not padded");
+  const unsigned most_slots = in.forced_slots >= 0 ? std::max((unsigned)in.forced_slots, in.slots_whole) : in.slots_whole;
+  unsigned next = 0;   // operations of `ops` met so far
+  for (size_t l = 0; l + 1 < levels.size(); ++l) {
+    const unsigned s0 = levels[l], s1 = levels[l + 1];
+    if (s1 <= s0 || s1 - s0 > kMaxListPieces) return fail("plan: pieces per launch", (int)l, (int)(s1 - s0));
+    const ListPieces pc = plan.pieces(l);
+    if (pc.n != s1 - s0) return fail("plan: ListPieces count", (int)l);
+    for (unsigned seg = s0; seg < s1; ++seg) {
+      const unsigned lo = cuts[seg], hi = cuts[seg + 1], nslots = plan.seg_slots[seg];
+      if (hi <= lo) return fail("plan: empty segment", (int)seg);
+      if (pc.start[seg - s0] != lo || pc.len[seg - s0] != hi - lo) return fail("plan: ListPieces bounds", (int)seg);
+      if (nslots != plan.seg_slots[s0] || nslots > most_slots) return fail("plan: slot count", (int)seg, (int)nslots);
+      if (!in.k20 && (hi - lo) % in.chunk) return fail("plan: a segment is no whole number of chunks", (int)seg, (int)(hi - lo));
+      struct Parked { unsigned clv = 0; int sc = 0, writer = -1; };
+      std::vector<Parked> slot(nslots);
+      std::map<unsigned, int> last_writer;   // CLV -> entry of this segment that wrote it last
+      const unsigned first = next;           // (`ops` index of the segment's first operation)
+      bool padding = false;
+      for (unsigned i = lo; i < hi; ++i) {
+        const LevelOp &d = plan.lops[i];
+        if (!in.k20 && d.noop) {   // pads: behind the segment's operations, stores off, nothing read or parked
+          if (d.noop != 1 || d.src1 != 2u || d.src2 != 2u || d.park != 0 || i == lo) return fail("plan: pad entry", (int)i);
+          if (d.parent_clv != plan.lops[i - 1].parent_clv) return fail("plan: a pad is a copy of the segment's last operation", (int)i);
+          padding = true;
+          continue;
+        }
+        if (padding) return fail("plan: an operation behind the padding", (int)i);
+        if (next >= count) return fail("plan: more operations than the list has", (int)i);
+        const rdamd_operation_t &o = ops[next];
+        LevelOp want;
+        level_op_fields(o, want);
+        if (d.parent_clv != want.parent_clv || d.child1_clv != want.child1_clv || d.child2_clv != want.child2_clv ||
+            d.child1_mat != want.child1_mat || d.child2_mat != want.child2_mat || d.parent_sc != want.parent_sc ||
+            d.child1_sc != want.child1_sc || d.child2_sc != want.child2_sc)
+          return fail("plan: descriptor fields", (int)i);
+        auto sc_off = [&](int sc) { return sc >= 0 ? (uint64_t)sc * in.sites * 4u : kNoOffset; };
+        auto clv_off = [&](unsigned clv) { return clv < tips ? (uint64_t)clv * in.tip_stride : (uint64_t)(clv - tips) * in.clv_bytes; };
+        if (d.parent_off != clv_off(d.parent_clv) || d.child1_off != clv_off(d.child1_clv) || d.child2_off != clv_off(d.child2_clv) ||
+            d.parent_sc_off != sc_off(d.parent_sc) || d.child1_sc_off != sc_off(d.child1_sc) || d.child2_sc_off != sc_off(d.child2_sc))
+          return fail("plan: byte offsets", (int)i);
+        const unsigned ch[2] = {d.child1_clv, d.child2_clv}, src[2] = {d.src1, d.src2};
+        const int chsc[2] = {d.child1_sc, d.child2_sc};
+        for (int c = 0; c < 2; ++c) {
+          if ((src[c] == 0u) != (ch[c] < tips)) return fail("plan: source 0 is a tip, every other source an inner CLV", (int)i, c);
+          if (src[c] < 2u) continue;
+          // registers: the parent of the operation `back` places in front, in the same segment
+          const unsigned back = src[c] - 1u;
+          if (in.k20 || src[c] == 2u) {
+            if (back > 2u || (!in.k20 && back != 1u) || i < lo + back) return fail("plan: register source out of the segment", (int)i, c);
+            const LevelOp &b = plan.lops[i - back];
+            if (b.parent_clv != ch[c] || b.parent_sc != chsc[c]) return fail("plan: register source is not that operation's parent", (int)i, c);
+            continue;
+          }
+          const unsigned s = src[c] - 3u;
+          if (s >= nslots) return fail("plan: parking slot beyond the segment's slots", (int)i, (int)s);
+          if (slot[s].writer < 0 || slot[s].clv != ch[c] || slot[s].sc != chsc[c] || !last_writer.count(ch[c]) ||
+              last_writer[ch[c]] != slot[s].writer)
+            return fail("plan: the parking slot does not hold the child's current value", (int)i, (int)s);
+        }
+        if (in.k20) {
+          if (i > lo && k20_hazard(tips, ops.data(), next, first)) return fail("plan: a 20-state hazard inside a segment", (int)i);
+          const bool more = next + 1 < count;
+          const unsigned a1 = more && ops[next + 1].child1_clv_index < tips ? ops[next + 1].child1_clv_index : 0u;
+          const unsigned a2 = more && ops[next + 1].child2_clv_index < tips ? ops[next + 1].child2_clv_index : 0u;
+          if (d.ahead1 != a1 || d.ahead2 != a2) return fail("plan: tip-code look-ahead", (int)i);
+        } else if (d.park) {
+          if (d.park > nslots) return fail("plan: park beyond the segment's slots", (int)i, (int)d.park);
+          slot[d.park - 1].clv = d.parent_clv; slot[d.park - 1].sc = d.parent_sc; slot[d.park - 1].writer = (int)i;
+        }
+        last_writer[d.parent_clv] = (int)i;
+        ++next;
+      }
+    }
+  }
+  if (next != count) return fail("plan: operations lost", (int)next, (int)count);
+  if (!in.k20) {
+    const rdamd::LevelOp &t = plan.lops.back();
+    if (t.noop != 1 || t.park != 0 || t.src1 != 2u || t.src2 != 2u) return fail("plan: terminator");
+  }
+  return 0;
+}
+
+// one input of the planner: a tree of 10 to 1000 tips, the list bent in the ways callers bend it
+static void planner_case(std::mt19937 &rng, int rep, std::vector<rdamd_operation_t> &ops, rdamd::ClvPlanInput &in) {
+  const unsigned n = 10 + rng() % 991;
+  ops = random_postorder(n, rng);
+  switch (rep % 5) {
+    case 1:   // the same CLV as both children
+      for (size_t i = 1; i < ops.size(); ++i)
+        if (ops[i].child1_clv_index >= n && rng() % 4 == 0) {
+          ops[i].child2_clv_index = ops[i].child1_clv_index;
+          ops[i].child2_scaler_index = rng() % 8 ? ops[i].child1_scaler_index : -1;
+        }
+      break;
+    case 2:   // a child under another scaler index than its producer's: must not be forwarded
+      for (size_t i = 1; i < ops.size(); ++i) {
+        if (ops[i].child1_clv_index >= n && rng() % 3 == 0) ops[i].child1_scaler_index = rng() % 2 ? -1 : (int)(rng() % n);
+        if (ops[i].child2_clv_index >= n && rng() % 3 == 0) ops[i].child2_scaler_index = rng() % 2 ? -1 : (int)(rng() % n);
+      }
+      break;
+    case 3:   // a partial list: inner children nothing in it computes
+      ops.erase(ops.begin(), ops.begin() + (std::ptrdiff_t)(rng() % (ops.size() - 1)));
+      break;
+    default: break;
+  }
+  in = rdamd::ClvPlanInput();
+  in.tips = n; in.clv_buffers = in.prob_matrices = in.scale_buffers = 2 * n;
+  in.sites = 1 + rng() % 5000; in.tip_stride = (in.sites + 3u) & ~3u;
+  in.k20 = rep % 2 == 1;
+  in.clv_bytes = in.k20 ? (uint64_t)(in.sites + 15) / 16 * 16 * 4 * 20 * 8 : (uint64_t)in.sites * 4 * 4 * 8;
+  in.slots_whole = in.k20 ? 0u : rng() % 7;
+  in.chunk = !in.k20 && rng() % 2 ? 4u : 1u;   // (the 4-state kernel's chunk, kernels_clv.hip)
+  const unsigned rows[4] = {0, 8, 16, 32};
+  in.rows = rows[rng() % 4];
+  in.small = in.k20 ? 24u : 4u + rng() % 12;
+  in.min_count = 6 + rng() % 24;
+  if (rep % 7 == 0) in.readback_tolerance_pct = rng() % 30;
+  if (rep % 11 == 0) in.forced_slots = (int)(rng() % 7);
+}
+
+static int check_planner(std::mt19937 &rng, int &cases) {
+  unsigned long cut_lists = 0, launches = 0;
+  for (int rep = 0; rep < 600; ++rep) {
+    std::vector<rdamd_operation_t> ops;
+    rdamd::ClvPlanInput in;
+    planner_case(rng, rep, ops, in);
+    const rdamd::ClvPlan plan = rdamd::plan_clv_traversal(in, ops.data(), (unsigned)ops.size());
+    if (replay_plan(in, ops, plan)) return 1;
+    // the figures behind the slot choice, recomputed from the finished plan: a launch of several
+    // pieces has no more read-backs than the tolerance allows over the whole-list slot count
+    for (size_t l = 0; !in.k20 && in.forced_slots < 0 && l < plan.launches(); ++l) {
+      const unsigned s0 = plan.levels[l], s1 = plan.levels[l + 1];
+      if (s1 - s0 < 2) continue;
+      const unsigned n_ops = plan.cut.seg[s1] - plan.cut.seg[s0];
+      const unsigned base = rdamd::clv_plan_readbacks(in, plan, ops.data(), (unsigned)ops.size(), l, in.slots_whole);
+      const unsigned got = rdamd::clv_plan_readbacks(in, plan, ops.data(), (unsigned)ops.size(), l, plan.seg_slots[s0]);
+      if (got > base + n_ops * in.readback_tolerance_pct / 100) return fail("plan: read-backs over the tolerance", (int)got, (int)base);
+    }
+    cut_lists += !plan.cut.order.empty();
+    launches += plan.launches();
+    ++cases;
+  }
+  for (int k20 = 0; k20 < 2; ++k20) {   // an index out of range: the first such operation is named, nothing is planned
+    std::vector<rdamd_operation_t> ops = random_postorder(200, rng);
+    rdamd::ClvPlanInput in;
+    in.tips = 200; in.clv_buffers = in.prob_matrices = in.scale_buffers = 400;
+    in.sites = 100; in.tip_stride = 100; in.clv_bytes = 100 * 128; in.k20 = k20 != 0; in.rows = 8;
+    ops[150].child2_matrix_index = 400;
+    ops[170].parent_scaler_index = 400;
+    const rdamd::ClvPlan plan = rdamd::plan_clv_traversal(in, ops.data(), (unsigned)ops.size());
+    const std::vector<rdamd_operation_t> &order = plan.cut.order.empty() ? ops : plan.cut.order;
+    int first_bad = -1;
+    for (size_t i = 0; i < order.size() && first_bad < 0; ++i)
+      if (!rdamd::operation_in_range(order[i], 200, 400, 400, 400)) first_bad = (int)i;
+    if (plan.bad_op < 0 || plan.bad_op != first_bad) return fail("plan: index out of range", plan.bad_op, first_bad);
+    ++cases;
+  }
+  std::fprintf(stderr, "planner: %lu of 600 lists cut, %lu launches\n", cut_lists, launches);
+  return 0;
+}
+
 int main() {
   std::mt19937 rng(20240603);
   int cases = 0;
@@ -400,6 +581,7 @@ int main() {
     if (!order.empty() || !bounds.empty()) return fail("a list that is no nest of subtree ranges must not be split");
     ++cases;
   }
+  if (check_planner(rng, cases)) return 1;
   std::printf("host logic OK %d\n", cases);
   return 0;
 }
