@@ -982,6 +982,72 @@ int rdamd_rell_tests(const double *site_lnl, unsigned int n_rows, unsigned int n
  * call); rdamd_rell_last_resample_ms holds the resampling kernel's own time of that call */
 double rdamd_rell_last_tests_ms(void);
 
+/* Approximately unbiased (AU) test of the rows (candidate roots) from a MULTISCALE RELL bootstrap
+ * (Shimodaira 2002).  The inputs are those of rdamd_rell_bootstrap: site_lnl[n_rows][n_patterns],
+ * pattern_weights, N = sum(pattern_weights), col2pat.  In addition there are K = n_scales scales,
+ * given as integer draw counts n_draws[K] (scale k resamples M_k = n_draws[k] columns per
+ * replicate, each drawn from all N columns), and B = n_replicates replicates per scale.
+ *
+ * - Scale seed. rdamd_rell_scale_seed(seed, k) = sm((seed + k + 1) mod 2^64), sm as in the
+ *   rdamd_rell_column comment.  Host only.
+ * - Sums. sums[k][b][i] = sum over d in [0, M_k) of
+ *     site_lnl[i][col2pat[rdamd_rell_column(rdamd_rell_scale_seed(seed, k), b, d, N)]].
+ *   The order rule is rdamd_rell_bootstrap's with M_k in place of N: draw d goes to partial sum
+ *   d mod 8; each partial sum adds its draws by increasing d; the eight are combined as
+ *   ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)).  A scale with M_k = N therefore gives exactly
+ *   rdamd_rell_bootstrap's sums for seed rdamd_rell_scale_seed(seed, k), to the bit.  No sum
+ *   depends on K, B, n_rows or a launch shape.
+ * - Counts. counts[k][i] (unsigned) = the number of replicates b of scale k whose largest sum is
+ *   row i's; ties go to the LOWEST i.  Each counts[k] sums to B.
+ *
+ * How the device computes it (csrc/kernels_rell_multiscale.hip): one launch covers every
+ * (scale, replicate) pair, the scales issued longest first; the winner of a replicate is found by
+ * the wave that makes its sums and counted with one integer atomic add (more than 256 rows: the
+ * waves of a replicate leave the largest sum and its lowest row of each 256-row chunk, 16 bytes,
+ * and a second kernel picks among the chunks in row order).  The K x B x n_rows sums are written to
+ * device memory only when `sums` is given; without it the call holds the transposed table,
+ * K x n_rows counts and, beyond 256 rows, K x B x chunks of those 16 bytes.  A repeated call
+ * returns the same bits.
+ * Host pointers: n_draws[n_scales], counts[n_scales][n_rows],
+ * sums[n_scales][n_replicates][n_rows] (may be NULL).
+ * Error 62 -- nothing is launched: everything rdamd_rell_bootstrap refuses; n_scales < 2 or > 64;
+ * an n_draws[k] of 0 or >= 2^32; two equal draw counts; site_lnl, pattern_weights, n_draws or
+ * counts missing. */
+uint64_t rdamd_rell_scale_seed(uint64_t seed, uint64_t k);
+int rdamd_rell_multiscale(const double *site_lnl, unsigned int n_rows, unsigned int n_patterns,
+                          const unsigned int *pattern_weights, unsigned int n_scales,
+                          const uint64_t *n_draws, unsigned int n_replicates, uint64_t seed,
+                          unsigned int *counts, double *sums);
+/* device time of the resampling launch and, beyond 256 rows, the winner launch of this thread's
+ * last rdamd_rell_multiscale call, milliseconds between two HIP events (0 after a failed call) */
+double rdamd_rell_last_multiscale_ms(void);
+/* The AU fit.  Host code, double precision, one row at a time, from the integer counts only; no
+ * device is needed.  N = the column count the scales are relative to, B = n_replicates.
+ * - r_k = M_k / N.  Scale k is usable for row i when 0 < counts[k][i] < B; used[i] = the number of
+ *   usable scales.
+ * - used >= 2: for each usable k, p = counts[k][i] / B, z = -Phi^-1(p) (evaluated as
+ *   Phi^-1((B - counts[k][i]) / B) on the side where the argument is at most 1/2),
+ *   v = p (1 - p) / (phi(z)^2 B), w = 1 / v, x1 = sqrt(r_k), x2 = 1 / sqrt(r_k).
+ *   Minimise sum_k w (z - d x1 - c x2)^2 through the 2 x 2 normal equations
+ *     a11 = sum w x1^2, a12 = sum w x1 x2, a22 = sum w x2^2, t1 = sum w x1 z, t2 = sum w x2 z,
+ *     det = a11 a22 - a12^2, d = (a22 t1 - a12 t2) / det, c = (a11 t2 - a12 t1) / det,
+ *   every sum taking its terms in order of k.
+ *   p_au = 1 - Phi(d - c), computed as the upper tail erfc((d - c) / sqrt 2) / 2;
+ *   rss = sum_k w (z - d x1 - c x2)^2, in order of k (degrees of freedom: used - 2; with
+ *   used = 2 the two points are fitted exactly and rss is 0, not the rounding residue);
+ *   se = phi(d - c) sqrt((a11 + a22 + 2 a12) / det): the standard error of d - c from the
+ *   inverse of the normal matrix, times the density.
+ * - used < 2: p_au = counts[k*][i] / B, k* = the scale whose M_k is nearest N (the lowest k among
+ *   equals), and d = c = rss = se = 0.
+ * Phi^-1 is Wichura's algorithm AS 241, routine PPND16 (Appl. Statist. 37, 1988), followed by one
+ * Halley step against erfc; Phi and phi are erfc and exp of the C library.
+ * p_au[n_rows] is required; d, c, rss, se (doubles) and used (unsigned) [n_rows] may be NULL.
+ * Error 62: counts, n_draws or p_au missing, n_scales < 2 or > 64, n_rows, N or n_replicates 0,
+ * N >= 2^32, an n_draws[k] of 0 or >= 2^32, two equal draw counts, a count above n_replicates. */
+int rdamd_au_fit(const unsigned int *counts, unsigned int n_scales, unsigned int n_rows,
+                 const uint64_t *n_draws, uint64_t N, unsigned int n_replicates, double *p_au,
+                 double *d, double *c, double *rss, double *se, unsigned int *used);
+
 /* RCCL communicator of one site group (librccl is loaded on first use; the
  * library has no link-time dependency on it).  Rank 0 of the group calls
  * rdamd_comm_unique_id and hands the 128 bytes to the others by any means

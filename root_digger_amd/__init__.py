@@ -47,6 +47,12 @@ from .api import (  # noqa: F401
     rell_last_resample_ms,
     rell_tests,
     rell_last_tests_ms,
+    rell_scale_seed,
+    rell_multiscale,
+    rell_last_multiscale_ms,
+    au_scales,
+    au_fit,
+    au_test,
     elw_confidence_set,
 )
 
@@ -59,5 +65,6 @@ __all__ = [
     "device_count", "hip_runtime_path", "mapped_hip_runtimes", "set_device", "device_memory", "msa_probe",
     "rank_order_sum", "COMM_SUM_GATHER", "COMM_SUM_ALLREDUCE",
     "msa_pattern_probe", "rell_column", "rell_bootstrap", "rell_last_resample_ms",
-    "rell_tests", "rell_last_tests_ms", "elw_confidence_set",
+    "rell_tests", "rell_last_tests_ms", "rell_scale_seed", "rell_multiscale", "rell_last_multiscale_ms",
+    "au_scales", "au_fit", "au_test", "elw_confidence_set",
 ]

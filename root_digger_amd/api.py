@@ -295,6 +295,11 @@ _sig("rdamd_rell_bootstrap", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd
 _sig("rdamd_rell_last_resample_ms", C.c_double)
 _sig("rdamd_rell_tests", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd)
 _sig("rdamd_rell_last_tests_ms", C.c_double)
+_pu64 = C.POINTER(C.c_uint64)
+_sig("rdamd_rell_scale_seed", C.c_uint64, C.c_uint64, C.c_uint64)
+_sig("rdamd_rell_multiscale", C.c_int, _pd, _u, _u, _pu, _u, _pu64, _u, C.c_uint64, _pu, _pd)
+_sig("rdamd_rell_last_multiscale_ms", C.c_double)
+_sig("rdamd_au_fit", C.c_int, _pu, _u, _u, _pu64, C.c_uint64, _u, _pd, _pd, _pd, _pd, _pd, _pu)
 
 _libc = C.CDLL(None)
 _libc.free.argtypes = [_vp]
@@ -1051,6 +1056,83 @@ def rell_last_tests_ms():
     """device time of everything this thread's last rell_tests call launched after the resampling
     kernel (HIP events)"""
     return float(lib.rdamd_rell_last_tests_ms())
+
+
+def rell_scale_seed(seed, k):
+    """seed of scale k of a multiscale bootstrap (rdamd_rell_scale_seed; host only)"""
+    return int(lib.rdamd_rell_scale_seed(int(seed) & 0xFFFFFFFFFFFFFFFF, int(k)))
+
+
+def _draw_counts(n_draws):
+    """draw counts as a uint64 array; anything outside 0 .. 2^64 - 1 becomes 0, which the library refuses"""
+    return np.array([int(v) if 0 <= int(v) < (1 << 64) else 0 for v in n_draws], dtype=np.uint64)
+
+
+def rell_multiscale(site_lnl, pattern_weights, n_draws, n_replicates, seed=1, return_sums=False):
+    """multiscale RELL bootstrap of the rows of site_lnl[rows][patterns] on the current device
+    (rdamd_rell_multiscale): scale k resamples n_draws[k] columns per replicate -> counts[K][rows]
+    (uint32: replicates won) or (counts, sums[K][n_replicates][rows])."""
+    a = np.ascontiguousarray(site_lnl, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("site_lnl is [rows][patterns]")
+    w = np.ascontiguousarray(pattern_weights, dtype=np.uint32)
+    if w.shape != (a.shape[1],):
+        raise ValueError("one weight per pattern is required")
+    m = _draw_counts(n_draws)
+    rows = a.shape[0]
+    counts = np.zeros((len(m), rows), dtype=np.uint32)
+    sums = np.zeros((len(m), int(n_replicates), rows), dtype=np.float64) if return_sums else None
+    if lib.rdamd_rell_multiscale(_dptr(a), rows, a.shape[1], _uptr(w), len(m), m.ctypes.data_as(_pu64),
+                                 int(n_replicates), int(seed), _uptr(counts),
+                                 _dptr(sums) if return_sums else None) != 1:
+        _fail("rell_multiscale")
+    return (counts, sums) if return_sums else counts
+
+
+def rell_last_multiscale_ms():
+    """device time of the resampling and winner launches of this thread's last rell_multiscale call
+    (HIP events)"""
+    return float(lib.rdamd_rell_last_multiscale_ms())
+
+
+def au_scales(n_columns):
+    """the ten draw counts of the AU test, 0.5 .. 1.4 times n_columns in steps of 0.1 rounded to
+    the nearest integer (the scales of CONSEL and IQ-TREE); entry 5 is n_columns itself"""
+    n = int(n_columns)
+    return [(n * (5 + k) + 5) // 10 for k in range(10)]
+
+
+def au_fit(counts, n_draws, n_columns, n_replicates):
+    """AU test from multiscale bootstrap counts[K][rows] (rdamd_au_fit; host only) -> dict of
+    arrays p_au, se, d, c, rss, df, used, one entry per row"""
+    n = np.ascontiguousarray(counts, dtype=np.uint32)
+    if n.ndim != 2:
+        raise ValueError("counts is [scales][rows]")
+    m = _draw_counts(n_draws)
+    if len(m) != n.shape[0]:
+        raise ValueError("one draw count per scale is required")
+    rows = n.shape[1]
+    out = {k: np.zeros(rows, dtype=np.float64) for k in ("p_au", "se", "d", "c", "rss")}
+    used = np.zeros(rows, dtype=np.uint32)
+    if lib.rdamd_au_fit(_uptr(n), n.shape[0], rows, m.ctypes.data_as(_pu64), int(n_columns), int(n_replicates),
+                        _dptr(out["p_au"]), _dptr(out["d"]), _dptr(out["c"]), _dptr(out["rss"]), _dptr(out["se"]),
+                        _uptr(used)) != 1:
+        _fail("au_fit")
+    out["used"] = used
+    out["df"] = np.maximum(used.astype(np.int64) - 2, 0)
+    return out
+
+
+def au_test(site_lnl, pattern_weights, n_replicates, seed=1):
+    """AU test of the rows of site_lnl[rows][patterns]: rell_multiscale at the ten au_scales, then
+    au_fit -> au_fit's dict plus counts[10][rows] and n_draws"""
+    n_columns = int(np.sum(np.asarray(pattern_weights, dtype=np.uint64)))
+    n_draws = au_scales(n_columns)
+    counts = rell_multiscale(site_lnl, pattern_weights, n_draws, n_replicates, seed)
+    out = au_fit(counts, n_draws, n_columns, n_replicates)
+    out["counts"] = counts
+    out["n_draws"] = n_draws
+    return out
 
 
 def elw_confidence_set(elw, level=0.95):

@@ -43,6 +43,28 @@ hipError_t launch_rell_support(const double *d_sums, unsigned n_rows, unsigned n
                                double *d_weights, unsigned *d_winner, double *d_bp, double *d_elw,
                                hipStream_t stream);
 
+// ---- multiscale bootstrap (rdamd_rell_multiscale; kernels_rell_multiscale.hip)
+constexpr unsigned RELL_MAX_SCALES = 64;
+// seed of scale k (rdamd_rell_scale_seed)
+inline uint64_t rell_scale_seed(uint64_t seed, uint64_t k) { return rell_sm(seed + k + 1); }
+// The scales of one launch in the order they are issued, longest first: `draws` draws per
+// replicate, replicate b's key is rell_key(seed, b), results go to scale `index` of the outputs.
+struct rell_scales_t {
+  unsigned n;
+  unsigned draws[RELL_MAX_SCALES], index[RELL_MAX_SCALES];
+  uint64_t seed[RELL_MAX_SCALES];
+};
+// row chunks of one replicate: 1 up to 256 rows (one wave holds a replicate)
+inline unsigned rell_row_chunks(const rell_shape_t &shape) { return shape.padded / (shape.lanes * shape.per_lane); }
+// d_counts[scales.n][n_rows] += replicates won (the caller zeroes it; integer atomics),
+// d_sums[scales.n][n_replicates][n_rows] unless NULL.  With more than one row chunk
+// d_chunk_max / d_chunk_row hold scales.n * n_replicates * chunks entries each: the chunks'
+// (largest sum, its lowest row), from which a second kernel picks; otherwise they may be NULL.
+hipError_t launch_rell_multiscale(const double *d_table, const rell_shape_t &shape, const unsigned *d_col2pat,
+                                  unsigned n_columns, unsigned n_rows, unsigned n_replicates,
+                                  const rell_scales_t &scales, unsigned *d_counts, double *d_sums,
+                                  double *d_chunk_max, unsigned *d_chunk_row, hipStream_t stream);
+
 // ---- KH / SH / weighted-SH tests of the rows (rdamd_rell_tests; kernels_rell_tests.hip).
 // c[b][i] = d_sums[b][i] - d_mean[i] is never stored: every kernel subtracts as it loads.
 // All counts are unsigned integers (integer atomics only); no result depends on a launch shape.

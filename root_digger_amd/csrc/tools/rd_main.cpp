@@ -26,7 +26,9 @@
 // bootstrap of B replicates on the device (rdamd_rell_bootstrap), <prefix>.support.tsv and the BP /
 // ELW annotations of <prefix>.lwr.tree.  --root-tests (with --rell): the KH, SH and weighted-SH tests of
 // every candidate from the same replicates (rdamd_rell_tests instead of rdamd_rell_bootstrap):
-// <prefix>.roottests.tsv, and pKH / pSH / pWSH next to BP / ELW on <prefix>.lwr.tree.
+// <prefix>.roottests.tsv, and pKH / pSH / pWSH next to BP / ELW on <prefix>.lwr.tree.  --au (with --rell):
+// the approximately unbiased test from B replicates at each of ten scales (rdamd_rell_multiscale,
+// rdamd_au_fit): <prefix>.au.tsv and pAU on <prefix>.lwr.tree.
 //
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
@@ -63,7 +65,7 @@ struct options_t {
        invariant_sites = false;
   // RELL bootstrap of the candidates' site lnLs (--rell B, 0: off) and the .sitelh file
   long rell = 0;
-  bool rell_given = false, rell_seed_given = false, site_lh = false, root_tests = false;
+  bool rell_given = false, rell_seed_given = false, site_lh = false, root_tests = false, au = false;
   uint64_t rell_seed = 0;
 };
 
@@ -85,7 +87,8 @@ void usage() {
       "  --site-shards <G>  --site-reduce {rccl,rccl-allreduce,host}  --lockstep-rounds {0,1}  --lockstep-groups {1,2}  --stats\n"
       "  --lbfgsb <LIB>  --device <N>  --silent  --echo  --clean  --no-checkpoint  --version\n"
       "  --rell <B>  --rell-seed <N>  --site-lh   (with --exhaustive: RELL support and site lnLs of every root)\n"
-      "  --root-tests   (with --rell: KH, SH and weighted-SH p-values of every root, <prefix>.roottests.tsv)");
+      "  --root-tests   (with --rell: KH, SH and weighted-SH p-values of every root, <prefix>.roottests.tsv)\n"
+      "  --au   (with --rell: AU test of every root from B replicates at each of ten scales, <prefix>.au.tsv)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -111,6 +114,7 @@ options_t parse(int argc, char **argv) {
       {"stats", no_argument, 0, 0},              {"lockstep-groups", required_argument, 0, 0},
       {"rell", required_argument, 0, 0},         {"rell-seed", required_argument, 0, 0},
       {"site-lh", no_argument, 0, 0},            {"root-tests", no_argument, 0, 0},
+      {"au", no_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -158,6 +162,7 @@ options_t parse(int argc, char **argv) {
     else if (name == "rell-seed") { o.rell_seed = std::strtoull(v, nullptr, 10); o.rell_seed_given = true; }
     else if (name == "site-lh") o.site_lh = true;
     else if (name == "root-tests") o.root_tests = true;
+    else if (name == "au") o.au = true;
     else if (name == "site-reduce") {
       const std::string s = v;
       if (s != "rccl" && s != "rccl-allreduce" && s != "host") die("--site-reduce takes rccl, rccl-allreduce or host");
@@ -199,6 +204,8 @@ static int run(int argc, char **argv) {
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
   if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
   if (o.root_tests && o.rell < 2) die("--root-tests: --rell must give at least 2 replicates");
+  if (o.au && !o.rell_given) die("--au: the test is made from --rell <B> replicates at every scale");
+  if (o.au && o.rell < 2) die("--au: --rell must give at least 2 replicates");
   if (support_opt) {
     const std::string opt = support_opt;
     if (o.rell_given && (o.rell < 1 || o.rell > 0x7fffffffl)) die("--rell: the number of replicates must be at least 1");
@@ -483,7 +490,7 @@ static int run(int argc, char **argv) {
   if (n_results == 0) die("no candidate root was evaluated");
 
   // ---- site lnLs of every candidate at its own parameters, .sitelh, RELL support
-  std::vector<double> bp, elw, p_kh, p_sh, p_wsh;
+  std::vector<double> bp, elw, p_kh, p_sh, p_wsh, p_au;
   double site_seconds = 0.0, rell_seconds = 0.0;
   if (support_opt) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -548,6 +555,24 @@ static int run(int argc, char **argv) {
         need(rdamd_rell_bootstrap(lnls.data(), n_results, P, weights.data(), (unsigned)o.rell, o.rell_seed, bp.data(),
                                   elw.data(), nullptr), "rell_bootstrap");
       }
+      // the AU test: B replicates at each of the ten scales 0.5 .. 1.4, then the fit on the host
+      std::vector<double> au_se, au_d, au_c, au_rss;
+      std::vector<unsigned> au_used;
+      if (o.au) {
+        std::vector<uint64_t> n_draws(10);
+        for (unsigned k = 0; k < 10; ++k) n_draws[k] = ((uint64_t)columns * (5 + k) + 5) / 10;
+        std::vector<unsigned> counts((size_t)10 * n_results);
+        need(rdamd_rell_multiscale(lnls.data(), n_results, P, weights.data(), 10, n_draws.data(), (unsigned)o.rell,
+                                   o.rell_seed, counts.data(), nullptr), "rell_multiscale");
+        p_au.assign(n_results, 0.0);
+        au_se.assign(n_results, 0.0);
+        au_d.assign(n_results, 0.0);
+        au_c.assign(n_results, 0.0);
+        au_rss.assign(n_results, 0.0);
+        au_used.assign(n_results, 0u);
+        need(rdamd_au_fit(counts.data(), 10, n_results, n_draws.data(), columns, (unsigned)o.rell, p_au.data(),
+                          au_d.data(), au_c.data(), au_rss.data(), au_se.data(), au_used.data()), "au_fit");
+      }
       rell_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
       double mx = -INFINITY, total = 0.0;
       for (unsigned i = 0; i < n_results; ++i) mx = std::max(mx, llh[i]);
@@ -562,6 +587,21 @@ static int run(int argc, char **argv) {
         std::fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\n", (unsigned long long)ids[i], llh[i],
                      std::exp(llh[i] - mx) / total, bp[i], elw[i]);
       std::fclose(f);
+      if (o.au) {
+        f = std::fopen((o.prefix + ".au.tsv").c_str(), "w");
+        if (!f) die("could not write " + o.prefix + ".au.tsv");
+        std::fprintf(f, "root_id\tllh\tp_au\tse\td\tc\trss\tdf\tused\n");
+        for (unsigned i : by_id)
+          std::fprintf(f, "%llu\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%.17g\t%u\t%u\n", (unsigned long long)ids[i],
+                       llh[i], p_au[i], au_se[i], au_d[i], au_c[i], au_rss[i], au_used[i] >= 2 ? au_used[i] - 2 : 0u,
+                       au_used[i]);
+        std::fclose(f);
+        if (!o.silent) {
+          unsigned kept = 0;
+          for (unsigned i = 0; i < n_results; ++i) kept += p_au[i] >= 0.05;
+          std::cout << "AU test: " << kept << " of " << n_results << " roots kept at 0.05" << std::endl;
+        }
+      }
       if (o.root_tests) {
         // the 95 % ELW set: rows by decreasing elw, equal values by lower index, until the sum reaches 0.95
         std::vector<unsigned> by_elw(n_results);
@@ -614,6 +654,7 @@ static int run(int argc, char **argv) {
           rdamd_tree_annotate_branch(out, &rl, "pSH", std::to_string(p_sh[i]).c_str());
           rdamd_tree_annotate_branch(out, &rl, "pWSH", std::to_string(p_wsh[i]).c_str());
         }
+        if (!p_au.empty()) rdamd_tree_annotate_branch(out, &rl, "pAU", std::to_string(p_au[i]).c_str());
       }
       rdamd_tree_annotate_branch(out, &rl, "LLH", std::to_string(llh[i]).c_str());
       rdamd_tree_annotate_branch_lr(out, &rl, "alpha", std::to_string(alpha[i]).c_str(),
