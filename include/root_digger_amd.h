@@ -392,8 +392,8 @@ int rdamd_get_pmatrix(rdamd_partition_t *p, unsigned int matrix_index,
  * partition is bracketed by HIP events on the partition's stream.
  * rdamd_profile_read synchronises, returns accumulated kernel milliseconds and
  * launch counts per kernel family {0: CLV level, 1: P-matrix, 2: root lnL,
- * 3: fused traversal (+ its finishing reduction), 4: batched P-matrix, 5-7:
- * reserved}, and resets the accumulators. */
+ * 3: fused traversal (+ its finishing reduction), 4: batched P-matrix, 5: the
+ * pre-order pass and the site-rate kernel, 6-7: reserved}, and resets the accumulators. */
 void rdamd_profile_enable(rdamd_partition_t *p, int on);
 int  rdamd_profile_read(rdamd_partition_t *p, double ms_out[8],
                         unsigned int launches_out[8]);
@@ -472,6 +472,10 @@ int  rdamd_tree_rooted(const rdamd_tree_t *t);                             /* :3
 int  rdamd_tree_sanity_check(const rdamd_tree_t *t);                       /* :519 */
 /* newick(annotations), src/tree.cpp:443-492; malloc'd, caller frees */
 char *rdamd_tree_newick(const rdamd_tree_t *t, int annotations);
+/* the same string without annotations and with the inner node whose CLV index is node_clv[k]
+ * labelled N<k> instead of its own label (new here: the tree that goes with the node order of
+ * rdamd_marginal_ancestral_nodes; root the tree with rdamd_tree_root_by first); malloc'd */
+char *rdamd_tree_newick_ancestral(const rdamd_tree_t *t, unsigned int n_nodes, const unsigned int *node_clv);
 int   rdamd_tree_annotate_branch(rdamd_tree_t *t, const rdamd_root_location_t *rl,
                                  const char *key, const char *value); /* :731 */
 /* annotate_branch(rl, key, left_value, right_value), src/tree.cpp:737-760 */
@@ -896,6 +900,75 @@ int rdamd_msa_pattern_probe(const char *msa_filename, const uint64_t *map, unsig
  * Refused (error 61) for a model that sums over a site group. */
 int rdamd_model_site_lnls(rdamd_model_t *m, unsigned int n, const rdamd_root_location_t *rls,
                           const uint64_t *counts, const double *values, double *out_patterns);
+
+/* ------------------------------------------------------------------------
+ * Marginal ancestral states and site rates at a chosen root (Yang, Kumar & Nei 1995; Yang 1995's
+ * empirical Bayes site rates).  NEW relative to the reference, which has no ancestral
+ * reconstruction: it extends the traversal made with corax_update_clvs at src/model.cpp:402 by the
+ * complementary pre-order pass.  Under a non-reversible model the answers depend on the root.
+ *
+ * The tree is rooted as the operation list `ops` says (rdamd_tree_generate_operations: post-order,
+ * the last operation the root's).  For site s and rate category r:
+ *   L_v[i]  CLV of node v as rdamd_update_clvs leaves it (a tip's: its 0/1 code vector)
+ *   P_v     P-matrix of the branch above v, rows = parent state
+ *   pi      frequencies of the rate's frequency set freqs_indices[r];  w_r, rate_r: category weight, rate
+ *   U_v[j]  = P(data outside the subtree of v, state j at v):
+ *             U_root[i] = pi_i;  for an operation with parent u and children a, b
+ *             U_a[j] = sum_i U_u[i] (P_b L_b)[i] P_a[i][j]      (U_b: a and b swapped)
+ *   post[v][s][j] = sum_r w_r U_v[s][r][j] L_v[s][r][j]         normalised over j
+ *   cat[s][r]     = w_r sum_i pi_i L_root[s][r][i]               normalised over r
+ *   mean_rate[s]  = sum_r cat[s][r] rate_r
+ * The outer vectors follow the 2^256 rule of the CLVs (a site below 2^-256 in every rate is
+ * multiplied by 2^256); the rule acts per site, so neither these counts nor the CLVs' scalers
+ * appear in the normalised outputs.  Pattern weights play no part (a pattern of weight 0 gets
+ * posteriors like any other); an all-gap column gets the prior carried down the tree.
+ * ---------------------------------------------------------------------- */
+/* post_out[n_ops][sites][states]: the posterior of every inner node.  Node 0 is the root, node k
+ * the parent of operation n_ops - 1 - k (the list read backwards: every node after its parent);
+ * binary partitions keep their 2-state shape.  Precondition: rdamd_update_prob_matrices and
+ * rdamd_update_clvs on exactly this list -- the inner CLVs are read as that traversal left them,
+ * nothing in the partition is written.  One launch for the whole list: 4-state and binary
+ * partitions, a (site, rate) pair per lane with 1, 2, 4 or 8 rate categories, a plain kernel for any
+ * other count.  Refused (error 63, nothing launched): 20-state partitions, partitions with
+ * RDAMD_ATTRIB_SPARSE_CLVS.  Error 64: the list is not a complete post-order traversal of one
+ * tree ending in the root operation (the rule of rdamd_schedule_create). */
+int rdamd_marginal_ancestral(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                             const unsigned int *freqs_indices, double *post_out);
+/* The nodes in that order (host only): node_clv[n_ops]; node_parent[n_ops], a node index, -1 for
+ * the root; node_children[n_ops][2], CLV indices (below the smallest parent index: a tip, named by
+ * rdamd_tree_tip_label).  Any pointer may be NULL. */
+int rdamd_marginal_ancestral_nodes(const rdamd_operation_t *ops, unsigned int n_ops, unsigned int *node_clv,
+                                   int *node_parent, unsigned int *node_children);
+/* workspace of the pass for this list, in CLV-sized slots: the most outer vectors that wait at
+ * once for an operation that is not the next one (~0u: error 64) */
+unsigned int rdamd_marginal_ancestral_workspace_slots(const rdamd_operation_t *ops, unsigned int n_ops,
+                                                      unsigned int tips);
+/* cat_out[sites][R] and mean_rate_out[sites] from the root CLV `clv_index` (any state count except
+ * the 20-state matrix-core layout, error 63).  scaler_index is checked for range only: per-site
+ * scalers cancel.  Either output may be NULL. */
+int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int scaler_index,
+                               const unsigned int *freqs_indices, double *cat_out, double *mean_rate_out);
+/* device time of the pre-order launch of this thread's last rdamd_marginal_ancestral call,
+ * milliseconds between two HIP events (0 after a failed call); for measurements */
+double rdamd_ancestral_last_ms(void);
+/* All of it for one root of a model.  Parameters in the checkpoint's layout exactly as
+ * rdamd_model_site_lnls takes them for one root (counts[n_partitions][4]; counts = values = NULL:
+ * the model's current parameters).  Outputs, any of which may be NULL: *n_nodes = inner nodes of
+ * the rooted tree (tips - 1); node_clv / node_parent / node_children as above;
+ * post_out[n_nodes][P_total][states] and mean_rate_out[P_total] with the patterns of all
+ * partitions concatenated in partition order (rdamd_model_site_patterns); cat_out: the
+ * partitions' [patterns][R] blocks back to back, each with its own category count
+ * (rdamd_model_partition_shape).  The model's parameters, its rooting
+ * and the conditional likelihoods of that rooting are as before when the call returns.
+ * Refused (error 61) for a model that sums over a site group; a partition whose shape
+ * rdamd_marginal_ancestral refuses fails the call and is named in the message. */
+/* patterns, alignment columns and rate categories of partition p (any pointer may be NULL) */
+int rdamd_model_partition_shape(const rdamd_model_t *m, unsigned int p, unsigned int *patterns,
+                                unsigned int *columns, unsigned int *rate_cats);
+int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl,
+                          const uint64_t *counts, const double *values, unsigned int *n_nodes,
+                          unsigned int *node_clv, int *node_parent, unsigned int *node_children,
+                          double *post_out, double *cat_out, double *mean_rate_out);
 
 /* Column that draw d (0 <= d < N) of bootstrap replicate b resamples, N < 2^32 columns.
  * Stateless and counter-based (all arithmetic mod 2^64):

@@ -293,6 +293,15 @@ _sig("rdamd_model_site_lnls", C.c_int, _vp, _u, _prl, _pu64, _pd, _pd)
 _sig("rdamd_rell_column", C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64)
 _sig("rdamd_rell_bootstrap", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd)
 _sig("rdamd_rell_last_resample_ms", C.c_double)
+_pi = C.POINTER(C.c_int)
+_sig("rdamd_marginal_ancestral", C.c_int, _vp, _pop, _u, _pu, _pd)
+_sig("rdamd_marginal_ancestral_nodes", C.c_int, _pop, _u, _pu, _pi, _pu)
+_sig("rdamd_marginal_ancestral_workspace_slots", C.c_uint, _pop, _u, _u)
+_sig("rdamd_site_rate_posteriors", C.c_int, _vp, _u, C.c_int, _pu, _pd, _pd)
+_sig("rdamd_ancestral_last_ms", C.c_double)
+_sig("rdamd_model_partition_shape", C.c_int, _vp, _u, _pu, _pu, _pu)
+_sig("rdamd_model_ancestral", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd, _pd)
+_sig("rdamd_tree_newick_ancestral", _vp, _vp, _u, _pu)
 _sig("rdamd_rell_tests", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd)
 _sig("rdamd_rell_last_tests_ms", C.c_double)
 _pu64 = C.POINTER(C.c_uint64)
@@ -559,6 +568,11 @@ class Tree:
     def newick(self, annotations=True):
         return _take_string(lib.rdamd_tree_newick(self._h, 1 if annotations else 0))
 
+    def newick_ancestral(self, node_clv):
+        """the tree as it is rooted now, inner node node_clv[k] labelled N<k> (rdamd_tree_newick_ancestral)"""
+        nc = np.ascontiguousarray(node_clv, dtype=np.uint32)
+        return _take_string(lib.rdamd_tree_newick_ancestral(self._h, nc.size, _uptr(nc)))
+
     def annotate_branch(self, rl, key, value, right_value=None):
         right = value if right_value is None else right_value
         if lib.rdamd_tree_annotate_branch_lr(self._h, C.byref(rl), key.encode(),
@@ -742,6 +756,28 @@ class Partition:
                                               _dptr(l1), _dptr(l2), l1.size, _dptr(out)) != 1:
             _fail("root_loglikelihood_fused")
         return out
+
+    def marginal_ancestral(self, ops, freqs_indices=None):
+        """Posterior of every state at every inner node of the tree `ops` roots -> array
+        [len(ops)][sites][states], node 0 the root, then every node after its parent
+        (rdamd_marginal_ancestral; ancestral_nodes(ops) names the nodes).  Call
+        update_prob_matrices and update_clvs on this list first."""
+        ops = _op_array(ops)
+        fi = self.params_indices if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        out = np.zeros((len(ops), self.sites, self.states), dtype=np.float64)
+        if lib.rdamd_marginal_ancestral(self._h, ops, len(ops), _uptr(fi), _dptr(out)) != 1:
+            _fail("marginal_ancestral")
+        return out
+
+    def site_rate_posteriors(self, clv_index, scaler_index=SCALE_BUFFER_NONE, freqs_indices=None):
+        """(cat[sites][R], mean_rate[sites]): posterior of every rate category and posterior mean rate of
+        every site, from the root CLV (rdamd_site_rate_posteriors)."""
+        fi = self.params_indices if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        cat = np.zeros((self.sites, self.rate_cats), dtype=np.float64)
+        mean = np.zeros(self.sites, dtype=np.float64)
+        if lib.rdamd_site_rate_posteriors(self._h, clv_index, scaler_index, _uptr(fi), _dptr(cat), _dptr(mean)) != 1:
+            _fail("site_rate_posteriors")
+        return cat, mean
 
     def get_clv(self, idx):
         out = np.zeros((self.sites, self.rate_cats, self.states), dtype=np.float64)
@@ -1021,6 +1057,43 @@ def rell_bootstrap(site_lnl, pattern_weights, n_replicates, seed=1, return_sums=
                                 _dptr(elw), _dptr(sums) if return_sums else None) != 1:
         _fail("rell_bootstrap")
     return (bp, elw, sums) if return_sums else (bp, elw)
+
+
+def _op_array(ops):
+    if isinstance(ops, C.Array):
+        return ops
+    arr = (Operation * len(ops))()
+    for i, o in enumerate(ops):
+        arr[i] = o
+    return arr
+
+
+def ancestral_nodes(ops):
+    """The inner nodes of the tree the post-order list `ops` roots, in the order of
+    Partition.marginal_ancestral: (node_clv[n], node_parent[n] (node index, -1: the root),
+    node_children[n][2] (CLV indices; tips are named by Tree.tip_label)).  Host only."""
+    n = len(ops)
+    ops = _op_array(ops)
+    clv = np.zeros(n, dtype=np.uint32)
+    parent = np.zeros(n, dtype=np.int32)
+    children = np.zeros((n, 2), dtype=np.uint32)
+    if lib.rdamd_marginal_ancestral_nodes(ops, n, _uptr(clv), parent.ctypes.data_as(_pi), _uptr(children)) != 1:
+        _fail("marginal_ancestral_nodes")
+    return clv, parent, children
+
+
+def ancestral_workspace_slots(ops, tips):
+    """CLV-sized workspace slots the pre-order pass needs for `ops` (rdamd_marginal_ancestral_workspace_slots)"""
+    n = len(ops)
+    v = lib.rdamd_marginal_ancestral_workspace_slots(_op_array(ops), n, tips)
+    if _errno():
+        _fail("marginal_ancestral_workspace_slots")
+    return int(v)
+
+
+def ancestral_last_ms():
+    """device milliseconds of the pre-order launch of this thread's last marginal_ancestral call"""
+    return float(lib.rdamd_ancestral_last_ms())
 
 
 def rell_last_resample_ms():
@@ -1475,6 +1548,45 @@ class Model:
                                            _dptr(values) if values is not None else None, _dptr(out)),
                  "site_lnls")
         return out
+
+    def partition_shape(self, p):
+        """(patterns, alignment columns, rate categories) of partition p"""
+        a, b, c = C.c_uint(0), C.c_uint(0), C.c_uint(0)
+        self._ok(lib.rdamd_model_partition_shape(self._h, p, C.byref(a), C.byref(b), C.byref(c)), "partition_shape")
+        return a.value, b.value, c.value
+
+    def ancestral(self, rl, params=None):
+        """Marginal ancestral states and site rates at root rl (rdamd_model_ancestral) ->
+        (node_clv[n], node_parent[n], node_children[n][2], post[n][P_total][states],
+        cat, mean_rate[P_total]); nodes as ancestral_nodes orders them, patterns of all partitions
+        concatenated.  cat: [P_total][R], or -- partitions with different category counts -- the list of
+        the partitions' [patterns][R] arrays.  params: the per-partition dicts Checkpoint.read_results
+        returns for one root; None: the model's current parameters."""
+        shapes = [self.partition_shape(p) for p in range(self.partition_count())]
+        total = sum(sh[0] for sh in shapes)
+        n = self._tree.tip_count() - 1
+        clv = np.zeros(n, dtype=np.uint32)
+        parent = np.zeros(n, dtype=np.int32)
+        children = np.zeros((n, 2), dtype=np.uint32)
+        post = np.zeros((n, total, self.states), dtype=np.float64)
+        cat = np.zeros(max(1, sum(sh[0] * sh[2] for sh in shapes)), dtype=np.float64)
+        mean = np.zeros(total, dtype=np.float64)
+        counts = values = None
+        if params is not None:
+            counts, values = _flatten_params(list(params))
+        nn = C.c_uint(0)
+        self._ok(lib.rdamd_model_ancestral(self._h, C.byref(rl),
+                                           counts.ctypes.data_as(_pu64) if counts is not None else None,
+                                           _dptr(values) if values is not None else None, C.byref(nn), _uptr(clv),
+                                           parent.ctypes.data_as(_pi), _uptr(children), _dptr(post), _dptr(cat),
+                                           _dptr(mean)), "ancestral")
+        assert nn.value == n
+        if len({sh[2] for sh in shapes}) == 1:
+            cat = cat[:total * shapes[0][2]].reshape(total, shapes[0][2])
+        else:
+            cuts = np.cumsum([0] + [sh[0] * sh[2] for sh in shapes])
+            cat = [cat[cuts[i]:cuts[i + 1]].reshape(sh[0], sh[2]) for i, sh in enumerate(shapes)]
+        return clv, parent, children, post, cat, mean
 
     def partition_second_passes(self, p):
         """batches of the model's own partition p that needed the evaluator's second pass so far"""

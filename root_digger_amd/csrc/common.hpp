@@ -273,6 +273,19 @@ void clv_k20_traversal_cut(const rdamd_partition *p, unsigned count, unsigned *p
 hipError_t launch_clv_k20_traversal(rdamd_partition *p, const LevelOp *d_ops, const ListPieces &pieces);
 size_t k20_mfma_copy_doubles();               // doubles per (matrix, rate) in d_pmat_mfma
 
+// kernels_outer.hip: the pre-order pass (outer vectors, ancestral state and site-rate posteriors)
+struct OuterOp;   // outer_plan.hpp
+// does the one-lane-per-(site, rate) kernel take the partition (else the generic one)?
+bool outer_fast_shape(const rdamd_partition *p);
+// doubles of workspace a program with `slots` slots needs on this partition
+size_t outer_workspace_doubles(const rdamd_partition *p, unsigned slots);
+// the whole program in one launch; d_post: [nops][sites][api_states]
+hipError_t launch_outer_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_fidx, double *d_work, double *d_post);
+// d_cat [sites][R] and d_mean [sites] (either may be null) from the CLV in device buffer clv_phys_index
+hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,
+                             double *d_mean);
+
 // kernels_root.hip
 hipError_t launch_root_lnl(rdamd_partition *p, unsigned clv_index, int scaler_index,
                            const unsigned *d_freqs_indices, double *d_persite,

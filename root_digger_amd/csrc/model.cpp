@@ -376,6 +376,42 @@ size_t model_t::pattern_count() const {
   return n;
 }
 
+// What site_lnls and ancestral change for the duration of a call and put back: the partitions'
+// parameters, the rooting, and (by one compute_lh) the conditional likelihoods of that rooting.
+struct model_t::saved_parameters_t {
+  struct part_t { std::vector<double> subst, freqs, rates, rate_weights; };
+  std::vector<part_t> parts;
+  std::vector<model_params_t> rate_rates;
+  bool was_rooted;
+  root_location_t rl;
+  explicit saved_parameters_t(const model_t &m)
+      : parts(m._partitions.size()), rate_rates(m._rate_rates), was_rooted(m._tree.rooted()), rl(m._tree.root_location()) {
+    for (size_t p = 0; p < parts.size(); ++p) {
+      const rdamd_partition_t *part = m._partitions[p];
+      const unsigned K = rdamd_partition_states(part);
+      const double *s = rdamd_partition_subst_params(part, 0), *f = rdamd_partition_frequencies(part, 0);
+      parts[p].subst.assign(s, s + (size_t)K * K - K);
+      parts[p].freqs.assign(f, f + K);
+      parts[p].rates = part->rates;
+      parts[p].rate_weights = part->rate_weights;
+    }
+  }
+  void restore(model_t &m) const {
+    m._rate_rates = rate_rates;
+    for (size_t p = 0; p < parts.size(); ++p) {
+      rdamd_set_subst_params(m._partitions[p], 0, parts[p].subst.data());
+      rdamd_set_frequencies(m._partitions[p], 0, parts[p].freqs.data());
+      rdamd_set_category_rates(m._partitions[p], parts[p].rates.data());
+      rdamd_set_category_weights(m._partitions[p], parts[p].rate_weights.data());
+    }
+  }
+  // the rooting, and the conditional likelihoods the root-only calls read, as they were
+  void restore_rooting(model_t &m) const {
+    if (was_rooted) m.compute_lh(rl);
+    else m._tree.unroot();
+  }
+};
+
 // The path compute_lh takes, with the root kernel's per-site output switched on.  That output is
 // weight x lnL; the partitions carry unit weights for the duration of the call (exact, and a
 // pattern of weight 0 keeps its lnL), so the rows are unweighted.
@@ -387,33 +423,12 @@ void model_t::site_lnls(const std::vector<root_location_t> &rls,
   if (params && params->size() != rls.size())
     throw std::invalid_argument("site_lnls: one parameter set per root is required");
   const size_t P = _partitions.size(), total = pattern_count();
-  struct saved_t {
-    std::vector<double> subst, freqs, rates, rate_weights;
-    std::vector<unsigned> pattern_weights;
-  };
-  std::vector<saved_t> saved(P);
-  const auto saved_rate_rates = _rate_rates;
-  const bool was_rooted = _tree.rooted();
-  const root_location_t saved_rl = _tree.root_location();
-  for (size_t p = 0; p < P; ++p) {
-    const rdamd_partition_t *part = _partitions[p];
-    const unsigned K = rdamd_partition_states(part);
-    const double *s = rdamd_partition_subst_params(part, 0), *f = rdamd_partition_frequencies(part, 0);
-    saved[p].subst.assign(s, s + (size_t)K * K - K);
-    saved[p].freqs.assign(f, f + K);
-    saved[p].rates = part->rates;
-    saved[p].rate_weights = part->rate_weights;
-    saved[p].pattern_weights = part->pattern_weights;
-  }
+  const saved_parameters_t saved_params(*this);
+  std::vector<std::vector<unsigned>> saved_weights(P);
+  for (size_t p = 0; p < P; ++p) saved_weights[p] = _partitions[p]->pattern_weights;
   const auto restore = [&] {
-    _rate_rates = saved_rate_rates;
-    for (size_t p = 0; p < P; ++p) {
-      rdamd_set_pattern_weights(_partitions[p], saved[p].pattern_weights.data());
-      rdamd_set_subst_params(_partitions[p], 0, saved[p].subst.data());
-      rdamd_set_frequencies(_partitions[p], 0, saved[p].freqs.data());
-      rdamd_set_category_rates(_partitions[p], saved[p].rates.data());
-      rdamd_set_category_weights(_partitions[p], saved[p].rate_weights.data());
-    }
+    for (size_t p = 0; p < P; ++p) rdamd_set_pattern_weights(_partitions[p], saved_weights[p].data());
+    saved_params.restore(*this);
   };
   try {
     for (size_t p = 0; p < P; ++p) {
@@ -454,9 +469,72 @@ void model_t::site_lnls(const std::vector<root_location_t> &rls,
     throw;
   }
   restore();
-  // the rooting, and the conditional likelihoods the root-only calls read, as they were
-  if (was_rooted) compute_lh(saved_rl);
-  else _tree.unroot();
+  saved_params.restore_rooting(*this);
+}
+
+// Marginal ancestral states and site rates at one root: compute_lh's traversal, then the pre-order
+// pass and the site-rate kernel per partition (rdamd_marginal_ancestral, rdamd_site_rate_posteriors).
+// Saves and restores what site_lnls does.
+void model_t::ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                        std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
+                        std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate) {
+  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
+    throw std::invalid_argument("ancestral: this model sums over a site group and holds one block of the "
+                                "columns; per-site output of a site-sharded model is not supported");
+  const size_t P = _partitions.size(), total = pattern_count();
+  if (params) {
+    if (params->size() != P) throw std::invalid_argument("ancestral: a parameter set needs one entry per partition");
+    for (size_t p = 0; p < P; ++p) {
+      const auto &pp = (*params)[p];
+      const size_t K = rdamd_partition_states(_partitions[p]);
+      if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
+          (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
+        throw std::invalid_argument("ancestral: the parameters do not fit partition " + std::to_string(p));
+    }
+  }
+  const saved_parameters_t saved(*this);
+  try {
+    if (params) set_model_params(*params);
+    auto sched = _tree.generate_operations(rl);
+    const auto &ops = std::get<0>(sched);
+    const unsigned n_ops = (unsigned)ops.size();
+    if (node_clv) node_clv->resize(n_ops);
+    if (node_parent) node_parent->resize(n_ops);
+    if (node_children) node_children->resize(2 * (size_t)n_ops);
+    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, node_clv ? node_clv->data() : nullptr,
+                                       node_parent ? node_parent->data() : nullptr,
+                                       node_children ? node_children->data() : nullptr) != RDAMD_SUCCESS)
+      fail("marginal_ancestral_nodes");
+    update_pmatrices(std::get<1>(sched), std::get<2>(sched));
+    ++_n_full;
+    size_t at = 0;   // first pattern of the partition in the concatenated list
+    std::vector<double> part_post;
+    for (size_t p = 0; p < P; ++p) {
+      rdamd_partition_t *part = _partitions[p];
+      const size_t sites = rdamd_partition_sites(part), K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part);
+      rdamd_update_clvs(part, ops.data(), n_ops);
+      if (rdamd_errno()) fail("update_clvs");
+      if (post) {
+        part_post.resize((size_t)n_ops * sites * K);
+        if (rdamd_marginal_ancestral(part, ops.data(), n_ops, _param_indicies[p].data(), part_post.data()) != RDAMD_SUCCESS)
+          throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+        for (size_t k = 0; k < n_ops; ++k)
+          std::copy(part_post.begin() + k * sites * K, part_post.begin() + (k + 1) * sites * K, post + (k * total + at) * K);
+      }
+      if ((cat || mean_rate) &&
+          rdamd_site_rate_posteriors(part, _tree.root_clv_index(), _tree.root_scaler_index(), _param_indicies[p].data(),
+                                     cat, mean_rate ? mean_rate + at : nullptr) != RDAMD_SUCCESS)
+        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+      if (cat) cat += sites * R;
+      at += sites;
+    }
+  } catch (...) {
+    saved.restore(*this);
+    saved.restore_rooting(*this);
+    throw;
+  }
+  saved.restore(*this);
+  saved.restore_rooting(*this);
 }
 
 // compute_lh for the searches, between optimize_params and the root-only steps: the same

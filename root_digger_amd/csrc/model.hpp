@@ -140,6 +140,13 @@ public:
   void site_lnls(const std::vector<root_location_t> &rls,
                  const std::vector<std::vector<partition_parameters_t>> *params, double *out);
   size_t pattern_count() const;
+  // Marginal ancestral states and site rates at one root (include/root_digger_amd.h,
+  // rdamd_model_ancestral): node arrays in pre-order (root first), post[nodes][pattern_count()][states],
+  // cat: the partitions' [patterns][R] blocks back to back, mean_rate[pattern_count()]; any output may
+  // be null.  params (optional): applied with set_model_params.  Saves and restores like site_lnls.
+  void ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                 std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
+                 std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate);
 
   // batched objective: lnL of (root, parameter set) pairs, all partitions,
   // through rdamd_evaluate_batch (one fused launch per partition)
@@ -290,6 +297,7 @@ public:
   rdamd_partition_t   *partition(size_t i) { return _partitions[i]; }
 
 private:
+  struct saved_parameters_t;   // model.cpp: what site_lnls and ancestral put back
   std::pair<root_location_t, double> brents(root_location_t beg, dlh_t d_beg,
                                             root_location_t end, dlh_t d_end, double atol);
   void set_tip_states(size_t p, const msa_t &msa);   // :302-325

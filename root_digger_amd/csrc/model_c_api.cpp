@@ -382,6 +382,46 @@ int rdamd_model_site_lnls(rdamd_model_t *m, unsigned int n, const rdamd_root_loc
   })
 }
 
+int rdamd_model_partition_shape(const rdamd_model_t *m, unsigned int p, unsigned int *patterns,
+                                unsigned int *columns, unsigned int *rate_cats) {
+  GUARD(RDAMD_FAILURE, {
+    if (p >= m->model->partition_count() || p >= m->msas.size()) throw std::invalid_argument("partition index out of range");
+    unsigned P = 0, N = 0;
+    concat_patterns({m->msas[p]}, &P, &N, nullptr, nullptr);
+    if (patterns) *patterns = P;
+    if (columns) *columns = N;
+    if (rate_cats) *rate_cats = rdamd_partition_rate_cats(m->model->partition(p));
+    return RDAMD_SUCCESS;
+  })
+}
+int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                          const double *values, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
+                          unsigned int *node_children, double *post_out, double *cat_out, double *mean_rate_out) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_ancestral")) return RDAMD_FAILURE;
+    if ((counts == nullptr) != (values == nullptr))
+      throw std::invalid_argument("rdamd_model_ancestral: counts and values come together");
+    if (!rl) throw std::invalid_argument("rdamd_model_ancestral: null argument");
+    std::vector<rdamd::partition_parameters_t> params;
+    if (counts) {
+      params.resize(m->model->partition_count());
+      for (rdamd::partition_parameters_t &pp : params)
+        for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
+          v->assign(values, values + *counts);
+          values += *counts++;
+        }
+    }
+    std::vector<unsigned> clv, children;
+    std::vector<int> parent;
+    m->model->ancestral(to_cpp(rl), counts ? &params : nullptr, &clv, &parent, &children, post_out, cat_out, mean_rate_out);
+    if (n_nodes) *n_nodes = (unsigned)clv.size();
+    if (node_clv) std::copy(clv.begin(), clv.end(), node_clv);
+    if (node_parent) std::copy(parent.begin(), parent.end(), node_parent);
+    if (node_children) std::copy(children.begin(), children.end(), node_children);
+    return RDAMD_SUCCESS;
+  })
+}
+
 namespace {
 void fill_model(const rdamd::model_info_t &mi, rdamd_partition_info_t *out) {
   std::snprintf(out->subst_str, sizeof out->subst_str, "%s", mi.subst_str.c_str());

@@ -13,6 +13,7 @@
 #include "clades.hpp"
 #include "clv_plan.hpp"
 #include "common.hpp"
+#include "outer_plan.hpp"
 
 namespace rdamd {
 
@@ -1032,6 +1033,164 @@ int rdamd_root_loglikelihood_fused_multi(unsigned int n_items, rdamd_partition_t
   RDAMD_HIP_TRY(sync_main(lead), RDAMD_FAILURE);
   for (unsigned i = 0; i < n_items; ++i)
     for (unsigned a = 0; a < n_positions[i]; ++a) out[8 * i + a] = h_res[8 * i + a];
+  return RDAMD_SUCCESS;
+}
+
+// ---- marginal ancestral states and site rates (kernels_outer.hip) ---------------------------
+namespace {
+thread_local double g_ancestral_ms = 0.0;
+// device memory and events of one call, given back however the call ends
+struct OuterScratch {
+  double *work = nullptr, *post = nullptr, *cat = nullptr, *mean = nullptr;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  ~OuterScratch() {
+    for (double *d : {work, post, cat, mean})
+      if (d) (void)hipFree(d);
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+  }
+};
+}  // namespace
+
+double rdamd_ancestral_last_ms(void) { return g_ancestral_ms; }
+
+int rdamd_marginal_ancestral_nodes(const rdamd_operation_t *ops, unsigned int n_ops, unsigned int *node_clv,
+                                   int *node_parent, unsigned int *node_children) {
+  clear_error();
+  // (host only, no partition: tips are the CLVs below every parent, as the tree numbers them)
+  unsigned tips = ~0u;
+  for (unsigned i = 0; i < n_ops; ++i) tips = std::min(tips, ops[i].parent_clv_index);
+  const OuterPlan plan = plan_outer_program(ops, n_ops, tips);
+  if (plan.bad_op >= 0) {
+    set_error(64, "rdamd_marginal_ancestral_nodes: operation %d: %s", plan.bad_op, plan.why);
+    return RDAMD_FAILURE;
+  }
+  if (node_parent) node_parent[0] = -1;
+  for (unsigned k = 0; k < n_ops; ++k) {
+    const OuterOp &d = plan.prog[k];
+    const rdamd_operation_t &o = ops[d.op];
+    if (node_clv) node_clv[k] = o.parent_clv_index;
+    if (node_children) { node_children[2 * k] = o.child1_clv_index; node_children[2 * k + 1] = o.child2_clv_index; }
+    for (int c = 0; c < 2; ++c)
+      if (d.inner[c] && node_parent) node_parent[d.node[c]] = (int)k;
+  }
+  return RDAMD_SUCCESS;
+}
+
+// the shapes the pre-order pass does not take; says so and returns true
+static bool outer_refused(const rdamd_partition *p, const char *what) {
+  if (p->states != 4 || p->mfma_layout) {
+    set_error(63, "%s: %u-state partitions are not supported (ancestral states are computed for 4-state and binary data)",
+              what, p->api_states);
+    return true;
+  }
+  if (p->sparse) {
+    set_error(63, "%s: partitions with RDAMD_ATTRIB_SPARSE_CLVS are not supported (the pass reads every inner CLV of a "
+                  "materialising traversal)", what);
+    return true;
+  }
+  return false;
+}
+
+int rdamd_marginal_ancestral(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                             const unsigned int *freqs_indices, double *post_out) {
+  clear_error();
+  g_ancestral_ms = 0.0;
+  if (outer_refused(p, "rdamd_marginal_ancestral")) return RDAMD_FAILURE;
+  if (!ops || !freqs_indices || !post_out) {
+    set_error(64, "rdamd_marginal_ancestral: null argument");
+    return RDAMD_FAILURE;
+  }
+  for (unsigned i = 0; i < n_ops; ++i)
+    if (!op_in_range(p, ops[i])) {
+      set_error(10, "rdamd_marginal_ancestral: operation %u has an index out of range", i);
+      return RDAMD_FAILURE;
+    }
+  const OuterPlan plan = plan_outer_program(ops, n_ops, p->tips);
+  if (plan.bad_op >= 0) {
+    set_error(64, "rdamd_marginal_ancestral: not a complete post-order traversal ending in the root operation: "
+                  "operation %d: %s", plan.bad_op, plan.why);
+    return RDAMD_FAILURE;
+  }
+  if (bad_rate_index(p, freqs_indices)) {
+    set_error(7, "rdamd_marginal_ancestral: freqs index out of range");
+    return RDAMD_FAILURE;
+  }
+  if (p->sites == 0) return RDAMD_SUCCESS;
+  const unsigned R = p->rate_cats;
+  const size_t prog_bytes = sizeof(OuterOp) * plan.prog.size();
+  const size_t post_doubles = (size_t)n_ops * p->sites * p->api_states;
+  OuterScratch mem;
+  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(ensure_scratch(p, prog_bytes + sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.work, std::max<size_t>(8, sizeof(double) * outer_workspace_doubles(p, plan.slots))),
+                RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.post, sizeof(double) * post_doubles), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t0), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t1), RDAMD_FAILURE);
+  Scratch sc{p};
+  OuterOp *d_prog = (OuterOp *)sc.take(prog_bytes);
+  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
+  RDAMD_HIP_TRY(upload(p, d_prog, plan.prog.data(), prog_bytes), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
+  p->prof_begin(5);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t0, p->stream), RDAMD_FAILURE);
+  const hipError_t le = launch_outer_program(p, d_prog, n_ops, plan.slots, d_fi, mem.work, mem.post);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t1, p->stream), RDAMD_FAILURE);
+  p->prof_end();
+  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
+  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, mem.t0, mem.t1) == hipSuccess) g_ancestral_ms = ms;
+  RDAMD_HIP_TRY(hipMemcpy(post_out, mem.post, sizeof(double) * post_doubles, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  return RDAMD_SUCCESS;
+}
+
+unsigned int rdamd_marginal_ancestral_workspace_slots(const rdamd_operation_t *ops, unsigned int n_ops, unsigned int tips) {
+  clear_error();
+  const OuterPlan plan = plan_outer_program(ops, n_ops, tips);
+  if (plan.bad_op >= 0) {
+    set_error(64, "rdamd_marginal_ancestral_workspace_slots: operation %d: %s", plan.bad_op, plan.why);
+    return ~0u;
+  }
+  return plan.slots;
+}
+
+int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int scaler_index,
+                               const unsigned int *freqs_indices, double *cat_out, double *mean_rate_out) {
+  clear_error();
+  if (p->mfma_layout) {
+    set_error(63, "rdamd_site_rate_posteriors: %u-state partitions in the matrix-core CLV layout are not supported",
+              p->api_states);
+    return RDAMD_FAILURE;
+  }
+  if (clv_index < p->tips || clv_index >= p->tips + p->clv_buffers || scaler_index >= (int)p->scale_buffers) {
+    set_error(11, "rdamd_site_rate_posteriors: index out of range (clv %u, scaler %d)", clv_index, scaler_index);
+    return RDAMD_FAILURE;
+  }
+  if (!freqs_indices || bad_rate_index(p, freqs_indices)) {
+    set_error(7, "rdamd_site_rate_posteriors: freqs index out of range");
+    return RDAMD_FAILURE;
+  }
+  if (p->sites == 0 || (!cat_out && !mean_rate_out)) return RDAMD_SUCCESS;
+  const size_t S = p->sites, R = p->rate_cats;
+  OuterScratch mem;
+  RDAMD_HIP_TRY(clv_phys(p, clv_index, &clv_index), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(ensure_scratch(p, sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
+  if (cat_out) RDAMD_HIP_TRY(hipMalloc(&mem.cat, sizeof(double) * S * R), RDAMD_FAILURE);
+  if (mean_rate_out) RDAMD_HIP_TRY(hipMalloc(&mem.mean, sizeof(double) * S), RDAMD_FAILURE);
+  Scratch sc{p};
+  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
+  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
+  p->prof_begin(5);
+  const hipError_t le = launch_site_rates(p, clv_index, d_fi, mem.cat, mem.mean);
+  p->prof_end();
+  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
+  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
+  if (cat_out) RDAMD_HIP_TRY(hipMemcpy(cat_out, mem.cat, sizeof(double) * S * R, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (mean_rate_out)
+    RDAMD_HIP_TRY(hipMemcpy(mean_rate_out, mem.mean, sizeof(double) * S, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 

@@ -30,6 +30,13 @@
 // the approximately unbiased test from B replicates at each of ten scales (rdamd_rell_multiscale,
 // rdamd_au_fit): <prefix>.au.tsv and pAU on <prefix>.lwr.tree.
 //
+// --ancestral / --site-rates (new here, with --exhaustive): after the search rank 0 takes the best
+// record's root and parameters from the checkpoint and reconstructs what that root implies
+// (rdamd_model_ancestral, one call): <prefix>.ancestral.tsv, the posterior of every state at every inner
+// node and alignment column; <prefix>.ancestral.tree, the tree rooted there with the inner nodes named
+// N0 (the root), N1, ... as in the rows; with --site-rates <prefix>.siterates.tsv, the posterior mean
+// rate and the rate-category posteriors of every column.
+//
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
 #include <chrono>
@@ -66,6 +73,8 @@ struct options_t {
   // RELL bootstrap of the candidates' site lnLs (--rell B, 0: off) and the .sitelh file
   long rell = 0;
   bool rell_given = false, rell_seed_given = false, site_lh = false, root_tests = false, au = false;
+  // what the best root implies: ancestral states (.ancestral.tsv, .ancestral.tree), site rates (.siterates.tsv)
+  bool ancestral = false, site_rates = false;
   uint64_t rell_seed = 0;
 };
 
@@ -88,7 +97,9 @@ void usage() {
       "  --lbfgsb <LIB>  --device <N>  --silent  --echo  --clean  --no-checkpoint  --version\n"
       "  --rell <B>  --rell-seed <N>  --site-lh   (with --exhaustive: RELL support and site lnLs of every root)\n"
       "  --root-tests   (with --rell: KH, SH and weighted-SH p-values of every root, <prefix>.roottests.tsv)\n"
-      "  --au   (with --rell: AU test of every root from B replicates at each of ten scales, <prefix>.au.tsv)");
+      "  --au   (with --rell: AU test of every root from B replicates at each of ten scales, <prefix>.au.tsv)\n"
+      "  --ancestral   (with --exhaustive: ancestral state posteriors at the best root, <prefix>.ancestral.tsv / .tree)\n"
+      "  --site-rates   (with --exhaustive: posterior mean rate of every column at the best root, <prefix>.siterates.tsv)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -114,7 +125,8 @@ options_t parse(int argc, char **argv) {
       {"stats", no_argument, 0, 0},              {"lockstep-groups", required_argument, 0, 0},
       {"rell", required_argument, 0, 0},         {"rell-seed", required_argument, 0, 0},
       {"site-lh", no_argument, 0, 0},            {"root-tests", no_argument, 0, 0},
-      {"au", no_argument, 0, 0},
+      {"au", no_argument, 0, 0},                 {"ancestral", no_argument, 0, 0},
+      {"site-rates", no_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -163,6 +175,8 @@ options_t parse(int argc, char **argv) {
     else if (name == "site-lh") o.site_lh = true;
     else if (name == "root-tests") o.root_tests = true;
     else if (name == "au") o.au = true;
+    else if (name == "ancestral") o.ancestral = true;
+    else if (name == "site-rates") o.site_rates = true;
     else if (name == "site-reduce") {
       const std::string s = v;
       if (s != "rccl" && s != "rccl-allreduce" && s != "host") die("--site-reduce takes rccl, rccl-allreduce or host");
@@ -200,7 +214,9 @@ static int run(int argc, char **argv) {
   if (world > 1 && o.no_checkpoint) die("--no-checkpoint: the ranks of a run meet in the checkpoint file");
   // the candidates' records and parameters are read back from the checkpoint; a site group's
   // member holds one block of the columns
-  const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : nullptr;
+  const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : o.ancestral ? "--ancestral"
+                            : o.site_rates ? "--site-rates" : nullptr;
+  const bool site_support = o.rell_given || o.site_lh;   // the site lnLs of every candidate are wanted
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
   if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
   if (o.root_tests && o.rell < 2) die("--root-tests: --rell must give at least 2 replicates");
@@ -492,7 +508,7 @@ static int run(int argc, char **argv) {
   // ---- site lnLs of every candidate at its own parameters, .sitelh, RELL support
   std::vector<double> bp, elw, p_kh, p_sh, p_wsh, p_au;
   double site_seconds = 0.0, rell_seconds = 0.0;
-  if (support_opt) {
+  if (site_support) {
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<rdamd_root_location_t> rls(n_results);
     std::vector<uint64_t> counts;
@@ -635,6 +651,103 @@ static int run(int argc, char **argv) {
       }
     }
   }
+  // ---- what the best root implies: ancestral states and site rates at its own parameters
+  if (o.ancestral || o.site_rates) {
+    unsigned k = 0;
+    for (unsigned i = 1; i < n_results; ++i)
+      if (llh[i] > llh[k]) k = i;   // the record `best` was taken from
+    uint64_t id = 0, nv = 0;
+    double l = 0, a = 0;
+    unsigned np = 0;
+    need(rdamd_checkpoint_result(ckp, k, &id, &l, &a, &np, &nv), "checkpoint result");
+    std::vector<uint64_t> counts(4 * (size_t)np);
+    std::vector<double> values(nv + 1);
+    need(rdamd_checkpoint_result_params(ckp, k, counts.data(), values.data()), "checkpoint result_params");
+    unsigned P = 0, columns = 0;
+    need(rdamd_model_site_patterns(model, &P, &columns, nullptr, nullptr), "site_patterns");
+    std::vector<unsigned> pattern_of(columns);
+    need(rdamd_model_site_patterns(model, nullptr, nullptr, nullptr, pattern_of.data()), "site_patterns");
+    const unsigned n_parts = (unsigned)rdamd_model_partition_count(model), K = o.states;
+    std::vector<unsigned> part_columns(n_parts), part_cats(n_parts);
+    size_t cat_doubles = 0;
+    unsigned max_cats = 1;
+    for (unsigned p = 0; p < n_parts; ++p) {
+      unsigned patterns = 0;
+      need(rdamd_model_partition_shape(model, p, &patterns, &part_columns[p], &part_cats[p]), "partition_shape");
+      cat_doubles += (size_t)patterns * part_cats[p];
+      max_cats = std::max(max_cats, part_cats[p]);
+    }
+    unsigned n_nodes = rdamd_tree_tip_count(tree) - 1;
+    std::vector<unsigned> node_clv(n_nodes);
+    std::vector<double> post(o.ancestral ? (size_t)n_nodes * P * K : 0), cat(o.site_rates ? cat_doubles + 1 : 0),
+        mean(o.site_rates ? P : 0);
+    need(rdamd_model_ancestral(model, &best, counts.data(), values.data(), &n_nodes, node_clv.data(), nullptr, nullptr,
+                               o.ancestral ? post.data() : nullptr, o.site_rates ? cat.data() : nullptr,
+                               o.site_rates ? mean.data() : nullptr), "ancestral");
+    std::string files;
+    if (o.ancestral) {
+      const char *letters = K == 2 ? "01" : "ACGT";
+      std::FILE *f = std::fopen((o.prefix + ".ancestral.tsv").c_str(), "w");
+      if (!f) die("could not write " + o.prefix + ".ancestral.tsv");
+      std::fprintf(f, "node\tpartition\tcolumn\tstate");
+      for (unsigned j = 0; j < K; ++j) std::fprintf(f, "\tp_%c", letters[j]);
+      std::fputc('\n', f);
+      for (unsigned v = 0; v < n_nodes; ++v) {
+        size_t col = 0;   // column of the concatenated partitions
+        for (unsigned p = 0; p < n_parts; ++p)
+          for (unsigned c = 0; c < part_columns[p]; ++c, ++col) {
+            const double *row = post.data() + ((size_t)v * P + pattern_of[col]) * K;
+            unsigned top = 0;
+            for (unsigned j = 1; j < K; ++j)
+              if (row[j] > row[top]) top = j;   // the first state with the largest posterior
+            std::fprintf(f, "N%u\t%u\t%u\t%c", v, p, c + 1, letters[top]);
+            for (unsigned j = 0; j < K; ++j) std::fprintf(f, "\t%.6f", row[j]);
+            std::fputc('\n', f);
+          }
+      }
+      std::fclose(f);
+      rdamd_tree_t *named = rdamd_tree_from_file(o.tree.c_str());
+      if (!named) die(rdamd_errmsg());
+      rdamd_root_location_t rl;
+      need(rdamd_tree_root_location(named, (unsigned)best.id, &rl), "root_location");
+      rl.brlen_ratio = best.brlen_ratio;
+      need(rdamd_tree_root_by(named, &rl), "root_by");
+      char *nw = rdamd_tree_newick_ancestral(named, n_nodes, node_clv.data());
+      if (!nw) die(rdamd_errmsg());
+      std::ofstream(o.prefix + ".ancestral.tree") << nw;
+      std::free(nw);
+      rdamd_tree_destroy(named);
+      files = o.prefix + ".ancestral.tsv " + o.prefix + ".ancestral.tree";
+    }
+    if (o.site_rates) {
+      std::FILE *f = std::fopen((o.prefix + ".siterates.tsv").c_str(), "w");
+      if (!f) die("could not write " + o.prefix + ".siterates.tsv");
+      std::fprintf(f, "partition\tcolumn\tmean_rate\tcategory");
+      for (unsigned r = 0; r < max_cats; ++r) std::fprintf(f, "\tp_%u", r + 1);
+      std::fputc('\n', f);
+      size_t col = 0, pat0 = 0, cat0 = 0;   // first column / pattern / category posterior of the partition
+      for (unsigned p = 0; p < n_parts; ++p) {
+        unsigned patterns = 0;
+        need(rdamd_model_partition_shape(model, p, &patterns, nullptr, nullptr), "partition_shape");
+        const unsigned R = part_cats[p];
+        for (unsigned c = 0; c < part_columns[p]; ++c, ++col) {
+          const size_t pat = pattern_of[col];
+          const double *row = cat.data() + cat0 + (pat - pat0) * R;
+          unsigned top = 0;
+          for (unsigned r = 1; r < R; ++r)
+            if (row[r] > row[top]) top = r;
+          std::fprintf(f, "%u\t%u\t%.6f\t%u", p, c + 1, mean[pat], top + 1);
+          for (unsigned r = 0; r < R; ++r) std::fprintf(f, "\t%.6f", row[r]);
+          std::fputc('\n', f);
+        }
+        pat0 += patterns;
+        cat0 += (size_t)patterns * R;
+      }
+      std::fclose(f);
+      files += (files.empty() ? "" : " ") + o.prefix + ".siterates.tsv";
+    }
+    if (!o.silent) std::cout << "Ancestral reconstruction at root " << best.id << " written to: " << files << std::endl;
+  }
   rdamd_tree_t *out = rdamd_tree_from_file(o.tree.c_str());
   std::string final_tree;
   if (o.exhaustive) {
@@ -681,7 +794,7 @@ static int run(int argc, char **argv) {
   }
   if (!o.silent) std::printf("Final LogLH: %.5f\n", best_llh);
   std::cout << final_tree << std::endl;
-  if (!o.silent && support_opt) {
+  if (!o.silent && site_support) {
     std::cout << "Search took: " << search_took.count() << "s" << std::endl;
     std::cout << "Site lnLs took: " << site_seconds << "s" << std::endl;
     if (o.rell_given) std::cout << "RELL bootstrap took: " << rell_seconds << "s" << std::endl;

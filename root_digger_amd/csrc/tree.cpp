@@ -497,11 +497,19 @@ bool rooted_tree_t::branch_length_sanity_check() const {
 }
 
 // src/tree.cpp:443-492 (label:length with six decimals + NHX annotations)
-std::string rooted_tree_t::newick(bool annotations) const {
+std::string rooted_tree_t::newick(bool annotations, const std::unordered_map<unsigned int, std::string> *inner_names) const {
+  // (inner_names: the label of an inner node whose CLV index it holds, instead of the input's own)
+  auto label = [&](int n) -> const std::string & {
+    if (inner_names && _next[n] >= 0) {
+      const auto it = inner_names->find(_clv[n]);
+      if (it != inner_names->end()) return it->second;
+    }
+    return _label[n];
+  };
   auto serialize = [&](int n) {
     char buf[64];
     snprintf(buf, sizeof(buf), "%f", _length[n]);
-    std::string s = _label[n] + ":" + buf;
+    std::string s = label(n) + ":" + buf;
     if (annotations) {
       auto it = _annotations.find(n);
       if (it != _annotations.end() && !it->second.empty()) {
@@ -526,7 +534,7 @@ std::string rooted_tree_t::newick(bool annotations) const {
   int root = _vroot;
   std::string s = "(" + sub(_back[root]);
   for (int k = _next[root]; k != root; k = _next[k]) s += "," + sub(_back[k]);
-  return s + ")" + _label[root] + ";";
+  return s + ")" + label(root) + ";";
 }
 
 // src/tree.cpp:731-760

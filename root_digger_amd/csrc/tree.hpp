@@ -82,7 +82,10 @@ public:
   bool branch_length_sanity_check() const;   // src/tree.cpp:498-517
   bool sanity_check() const { return branch_length_sanity_check(); }
 
-  std::string newick(bool annotations = true) const;   // src/tree.cpp:443-492
+  // src/tree.cpp:443-492.  inner_names (not in the reference): CLV index -> label of that inner
+  // node in this string, instead of the input's own (the tree file of the ancestral states)
+  std::string newick(bool annotations = true,
+                     const std::unordered_map<unsigned int, std::string> *inner_names = nullptr) const;
   void annotate_branch(const root_location_t &rl, const std::string &key,
                        const std::string &value) { annotate_branch(rl, key, value, value); }
   void annotate_branch(const root_location_t &rl, const std::string &key,

@@ -183,6 +183,13 @@ int rdamd_tree_sanity_check(const rdamd_tree_t *t) { return t->tree.sanity_check
 char *rdamd_tree_newick(const rdamd_tree_t *t, int annotations) {
   GUARD({ return dup(t->tree.newick(annotations != 0)); })
 }
+char *rdamd_tree_newick_ancestral(const rdamd_tree_t *t, unsigned int n_nodes, const unsigned int *node_clv) {
+  GUARD({
+    std::unordered_map<unsigned int, std::string> names;
+    for (unsigned k = 0; k < n_nodes; ++k) names[node_clv[k]] = "N" + std::to_string(k);
+    return dup(t->tree.newick(false, &names));
+  })
+}
 int rdamd_tree_annotate_branch(rdamd_tree_t *t, const rdamd_root_location_t *rl,
                                const char *key, const char *value) {
   GUARD({ t->tree.annotate_branch(to_cpp(rl), key, value); return RDAMD_SUCCESS; })
