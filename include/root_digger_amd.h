@@ -1073,8 +1073,8 @@ double rdamd_rell_last_tests_ms(void);
  * - Counts. counts[k][i] (unsigned) = the number of replicates b of scale k whose largest sum is
  *   row i's; ties go to the LOWEST i.  Each counts[k] sums to B.
  *
- * How the device computes it (csrc/kernels_rell_multiscale.hip): one launch covers every
- * (scale, replicate) pair, the scales issued longest first; the winner of a replicate is found by
+ * How the device computes it (csrc/kernels_rell.hip, the bootstrap's kernel template): one launch
+ * covers every (scale, replicate) pair, the scales issued longest first; the winner of a replicate is found by
  * the wave that makes its sums and counted with one integer atomic add (more than 256 rows: the
  * waves of a replicate leave the largest sum and its lowest row of each 256-row chunk, 16 bytes,
  * and a second kernel picks among the chunks in row order).  The K x B x n_rows sums are written to

@@ -5,8 +5,11 @@ on the two shapes of profiles/r10_au.md.
 usage: au_bench.py [--shape c2|c5|w8|w16|w32|w64|w128] [--runs 3] [--baseline-library PATH/librdamd.so]
 (default: c2 and c5; the w shapes are the narrower launch shapes on 20 000 columns)
 --baseline-library: another build of the library (the previous commit's), loaded next to this one;
-its rdamd_rell_bootstrap runs on the same matrix in the same process and is the yardstick, and this
-build's own kernel is timed next to it (it must not have moved).  One line per run."""
+its rdamd_rell_bootstrap and rdamd_rell_multiscale run on the same matrix in the same process,
+interleaved with this build's, after one untimed full-size call of each; the two builds must return
+equal counts and proportions.  One line per run, then per shape the medians of both builds, the
+baseline's own spread (max - min) / median over its runs, and whether this build's medians lie
+within it."""
 import argparse
 import ctypes as C
 import os
@@ -39,7 +42,7 @@ def matrix(rows, patterns, seed):
 
 
 class Baseline:
-    """rdamd_rell_bootstrap of another build of the library"""
+    """rdamd_rell_bootstrap and rdamd_rell_multiscale of another build of the library"""
 
     def __init__(self, path):
         self.lib = C.CDLL(path)
@@ -47,6 +50,9 @@ class Baseline:
         self.lib.rdamd_rell_bootstrap.restype = C.c_int
         self.lib.rdamd_rell_bootstrap.argtypes = [pd, u, u, pu, u, C.c_uint64, pd, pd, pd]
         self.lib.rdamd_rell_last_resample_ms.restype = C.c_double
+        self.lib.rdamd_rell_multiscale.restype = C.c_int
+        self.lib.rdamd_rell_multiscale.argtypes = [pd, u, u, pu, u, C.POINTER(C.c_uint64), u, C.c_uint64, pu, pd]
+        self.lib.rdamd_rell_last_multiscale_ms.restype = C.c_double
         self.lib.rdamd_version.restype = C.c_char_p
 
     def resample_ms(self, m, w, reps, seed):
@@ -56,6 +62,26 @@ class Baseline:
                                          bp.ctypes.data_as(pd), elw.ctypes.data_as(pd), None) != 1:
             raise RuntimeError("the baseline library's rdamd_rell_bootstrap failed")
         return float(self.lib.rdamd_rell_last_resample_ms()), bp
+
+    def multiscale_ms(self, m, w, n_draws, reps, seed):
+        pd, pu = C.POINTER(C.c_double), C.POINTER(C.c_uint)
+        draws = np.asarray(n_draws, dtype=np.uint64)
+        counts = np.zeros((len(draws), m.shape[0]), dtype=np.uint32)
+        if self.lib.rdamd_rell_multiscale(m.ctypes.data_as(pd), m.shape[0], m.shape[1], w.ctypes.data_as(pu), len(draws),
+                                          draws.ctypes.data_as(C.POINTER(C.c_uint64)), reps, seed,
+                                          counts.ctypes.data_as(pu), None) != 1:
+            raise RuntimeError("the baseline library's rdamd_rell_multiscale failed")
+        return float(self.lib.rdamd_rell_last_multiscale_ms()), counts
+
+
+def summary(name, what, ours, theirs):
+    """this build's median against the baseline's, judged by the baseline's own spread"""
+    med, ref = float(np.median(ours)), float(np.median(theirs))
+    spread = (max(theirs) - min(theirs)) / ref
+    off = med / ref - 1.0
+    return ("%-3s %-10s median %9.3f ms, baseline %9.3f ms (%s), baseline spread %.2f %%, this build %+.2f %%: %s"
+            % (name, what, med, ref, " ".join("%.3f" % t for t in theirs), 100 * spread, 100 * off,
+               "within" if abs(off) <= spread else "OUTSIDE, faster" if off < 0 else "OUTSIDE, SLOWER"))
 
 
 def main():
@@ -74,8 +100,14 @@ def main():
         # (code objects loaded, every kernel of this shape's instantiation launched once)
         rd.au_test(m[:, :64], w[:64], 64, seed=1)
         rd.rell_bootstrap(m[:, :64], w[:64], 64, seed=1)
+        times = {"multi": [], "prev_multi": [], "single": [], "prev_single": []}
         if base:
             base.resample_ms(m[:, :64].copy(), w[:64].copy(), 64, 1)
+            # (the first large launches of a process run slow: one untimed full-size call of each)
+            rd.rell_multiscale(m, w, n_draws, reps, 99)
+            base.multiscale_ms(m, w, n_draws, reps, 99)
+            rd.rell_bootstrap(m, w, reps, seed=99)
+            base.resample_ms(m, w, reps, 99)
         for run in range(args.runs):
             seed = run + 1
             t = time.time()
@@ -90,13 +122,20 @@ def main():
                     "x %.2f (sum M_k / N) = %9.3f ms, ratio %.4f"
                     % (name, rows, patterns, reps, run, multi, single, factor, factor * single, multi / (factor * single)))
             if base:
+                prev_multi, prev_counts = base.multiscale_ms(m, w, n_draws, reps, seed)
+                assert np.array_equal(prev_counts, counts)
                 prev, prev_bp = base.resample_ms(m, w, reps, rd.rell_scale_seed(seed, 5))
                 assert np.array_equal(prev_bp, bp)
-                line += ("; previous build's bootstrap %8.3f ms, x %.2f = %9.3f ms, ratio %.4f"
-                         % (prev, factor, factor * prev, multi / (factor * prev)))
+                line += ("; previous build's multiscale %9.3f ms, bootstrap %8.3f ms, x %.2f = %9.3f ms, ratio %.4f"
+                         % (prev_multi, prev, factor, factor * prev, multi / (factor * prev)))
+                for key, t in (("multi", multi), ("prev_multi", prev_multi), ("single", single), ("prev_single", prev)):
+                    times[key].append(t)
             line += ("; whole multiscale call %.2f s; rows fitted %d, kept at 0.05 %d"
                      % (wall, int((fit["used"] >= 2).sum()), int((fit["p_au"] >= 0.05).sum())))
             print(line, flush=True)
+        if base:
+            print(summary(name, "multiscale", times["multi"], times["prev_multi"]), flush=True)
+            print(summary(name, "bootstrap", times["single"], times["prev_single"]), flush=True)
 
 
 if __name__ == "__main__":

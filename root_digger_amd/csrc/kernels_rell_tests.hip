@@ -75,16 +75,12 @@ __global__ void __launch_bounds__(64)
 rell_best_kernel(const double *__restrict__ lnl, unsigned n, unsigned *__restrict__ best) {
   const unsigned lane = threadIdx.x;
   double top = 0.0;
-  unsigned at = 0xffffffffu;
+  unsigned at = RELL_NO_ROW;
   for (unsigned i = lane; i < n; i += 64) {
     const double x = lnl[i];
-    if (at == 0xffffffffu || x > top) { top = x; at = i; }
+    if (at == RELL_NO_ROW || x > top) { top = x; at = i; }
   }
-  for (int off = 32; off; off >>= 1) {
-    const double ot = __shfl_xor(top, off);
-    const unsigned oa = (unsigned)__shfl_xor((int)at, off);
-    if (oa != 0xffffffffu && (at == 0xffffffffu || ot > top || (ot == top && oa < at))) { top = ot; at = oa; }
-  }
+  for (int off = 32; off; off >>= 1) rell_merge_best(top, at, off);
   if (lane == 0) best[0] = at;
 }
 

@@ -14,46 +14,84 @@
 
 namespace {
 
-// everything the call allocates; released on every way out
-struct rell_buffers_t {
-  double *rows = nullptr, *table = nullptr, *sums = nullptr, *weights = nullptr, *bp = nullptr, *elw = nullptr;
-  unsigned *col2pat = nullptr, *winner = nullptr;
-  // the tests' own
-  double *partial = nullptr, *lnl = nullptr, *mean = nullptr, *cmax = nullptr, *cbest = nullptr, *rinv = nullptr,
-         *spread = nullptr, *tobs = nullptr;
-  unsigned *pattern_weights = nullptr, *best = nullptr, *counts = nullptr;   // counts: kh, sh, wsh
-  hipStream_t stream = nullptr;
-  hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
-  ~rell_buffers_t() {
-    for (void *p : {(void *)rows, (void *)table, (void *)sums, (void *)weights, (void *)bp, (void *)elw,
-                    (void *)col2pat, (void *)winner, (void *)partial, (void *)lnl, (void *)mean, (void *)cmax,
-                    (void *)cbest, (void *)rinv, (void *)spread, (void *)tobs, (void *)pattern_weights,
-                    (void *)best, (void *)counts})
-      if (p) (void)hipFree(p);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-    if (t2) (void)hipEventDestroy(t2);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
 thread_local double g_last_resample_ms = 0.0, g_last_tests_ms = 0.0, g_last_multiscale_ms = 0.0;
 
-// what rdamd_rell_multiscale allocates; released on every way out
-struct multiscale_buffers_t {
-  double *rows = nullptr, *table = nullptr, *sums = nullptr, *chunk_max = nullptr;
-  unsigned *col2pat = nullptr, *counts = nullptr, *chunk_row = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  ~multiscale_buffers_t() {
-    for (void *p : {(void *)rows, (void *)table, (void *)sums, (void *)chunk_max, (void *)col2pat, (void *)counts,
-                    (void *)chunk_row})
-      if (p) (void)hipFree(p);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+// A call's device allocations, its stream and its events: released on every way out.
+template <class T> struct device_array_t {
+  T *p = nullptr;
+  device_array_t() = default;
+  device_array_t(const device_array_t &) = delete;
+  device_array_t &operator=(const device_array_t &) = delete;
+  ~device_array_t() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+  operator T *() const { return p; }
 };
+template <class T, hipError_t (*DESTROY)(T)> struct owned_t {
+  T h = nullptr;
+  owned_t() = default;
+  owned_t(const owned_t &) = delete;
+  owned_t &operator=(const owned_t &) = delete;
+  ~owned_t() { if (h) (void)DESTROY(h); }
+  operator T() const { return h; }
+};
+using stream_t = owned_t<hipStream_t, hipStreamDestroy>;
+using event_t = owned_t<hipEvent_t, hipEventDestroy>;
+
+// What both calls resample from: the padded table [n_patterns][shape.padded] and the column ->
+// pattern map of the N columns on the device, the call's stream and the events around its
+// resampling launches.  (Members are destroyed last first: the buffers, the events, the stream.)
+struct rell_staged_t {
+  stream_t stream;
+  event_t t0, t1;
+  device_array_t<double> table;
+  device_array_t<unsigned> col2pat;
+  rdamd::rell_shape_t shape;
+  unsigned N;
+};
+
+// The checks both calls share (own_checks() -> false: the call's own have failed and set the
+// error; they come after "nothing to resample", before the column count), the upload and the
+// transposition.  The row-major copy is gone when this returns: the large shapes need the room for
+// what the caller allocates next.
+template <class F>
+int rell_stage(const char *who, const double *site_lnl, unsigned n_rows, unsigned n_patterns,
+               const unsigned *pattern_weights, unsigned n_replicates, F &&own_checks, rell_staged_t &s) {
+  using rdamd::set_error;
+  if (n_rows == 0 || n_patterns == 0 || n_replicates == 0) {
+    set_error(62, "%s: nothing to resample (%u rows, %u patterns, %u replicates)", who, n_rows, n_patterns,
+              n_replicates);
+    return RDAMD_FAILURE;
+  }
+  if (!own_checks()) return RDAMD_FAILURE;
+  uint64_t N = 0;
+  for (unsigned p = 0; p < n_patterns; ++p) N += pattern_weights[p];
+  if (N == 0 || (N >> 32)) {
+    set_error(62, "%s: the pattern weights sum to %llu columns; 1 .. 2^32 - 1 are supported", who,
+              (unsigned long long)N);
+    return RDAMD_FAILURE;
+  }
+  // pattern p owns pattern_weights[p] consecutive columns
+  std::vector<unsigned> col2pat;
+  col2pat.reserve((size_t)N);
+  for (unsigned p = 0; p < n_patterns; ++p) col2pat.insert(col2pat.end(), pattern_weights[p], p);
+
+  s.shape = rdamd::rell_shape(n_rows);
+  s.N = (unsigned)N;
+  const size_t cells = (size_t)n_rows * n_patterns;
+  device_array_t<double> rows;
+  RDAMD_HIP_TRY(hipStreamCreateWithFlags(&s.stream.h, hipStreamNonBlocking), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&s.t0.h), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&s.t1.h), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(rows.alloc(cells), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(s.table.alloc((size_t)n_patterns * s.shape.padded), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(s.col2pat.alloc((size_t)N), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMemcpy(rows, site_lnl, cells * sizeof(double), hipMemcpyHostToDevice), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMemcpy(s.col2pat, col2pat.data(), (size_t)N * sizeof(unsigned), hipMemcpyHostToDevice),
+                RDAMD_FAILURE);
+  RDAMD_HIP_TRY(rdamd::launch_rell_transpose(rows, n_rows, n_patterns, s.shape, s.table, s.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipStreamSynchronize(s.stream), RDAMD_FAILURE);
+  return RDAMD_SUCCESS;
+}
 
 // what rdamd_rell_tests returns beyond the bootstrap's (host pointers; lnl, p_wsh, spread may be NULL)
 struct rell_tests_out_t {
@@ -89,38 +127,28 @@ int rdamd_rell_multiscale(const double *site_lnl, unsigned int n_rows, unsigned 
     set_error(62, "%s: site_lnl, pattern_weights, n_draws and counts are required", who);
     return RDAMD_FAILURE;
   }
-  if (n_rows == 0 || n_patterns == 0 || n_replicates == 0) {
-    set_error(62, "%s: nothing to resample (%u rows, %u patterns, %u replicates)", who, n_rows, n_patterns,
-              n_replicates);
-    return RDAMD_FAILURE;
-  }
-  if (n_scales < 2 || n_scales > rdamd::RELL_MAX_SCALES) {
-    set_error(62, "%s: 2 .. %u scales are supported (%u given)", who, rdamd::RELL_MAX_SCALES, n_scales);
-    return RDAMD_FAILURE;
-  }
-  for (unsigned k = 0; k < n_scales; ++k) {
-    if (n_draws[k] == 0 || (n_draws[k] >> 32)) {
-      set_error(62, "%s: scale %u draws %llu columns; 1 .. 2^32 - 1 are supported", who, k,
-                (unsigned long long)n_draws[k]);
-      return RDAMD_FAILURE;
+  const auto own_checks = [&] {
+    if (n_scales < 2 || n_scales > rdamd::RELL_MAX_SCALES) {
+      set_error(62, "%s: 2 .. %u scales are supported (%u given)", who, rdamd::RELL_MAX_SCALES, n_scales);
+      return false;
     }
-    for (unsigned j = 0; j < k; ++j)
-      if (n_draws[j] == n_draws[k]) {
-        set_error(62, "%s: scales %u and %u both draw %llu columns", who, j, k, (unsigned long long)n_draws[k]);
-        return RDAMD_FAILURE;
+    for (unsigned k = 0; k < n_scales; ++k) {
+      if (n_draws[k] == 0 || (n_draws[k] >> 32)) {
+        set_error(62, "%s: scale %u draws %llu columns; 1 .. 2^32 - 1 are supported", who, k,
+                  (unsigned long long)n_draws[k]);
+        return false;
       }
-  }
-  uint64_t N = 0;
-  for (unsigned p = 0; p < n_patterns; ++p) N += pattern_weights[p];
-  if (N == 0 || (N >> 32)) {
-    set_error(62, "%s: the pattern weights sum to %llu columns; 1 .. 2^32 - 1 are supported", who,
-              (unsigned long long)N);
+      for (unsigned j = 0; j < k; ++j)
+        if (n_draws[j] == n_draws[k]) {
+          set_error(62, "%s: scales %u and %u both draw %llu columns", who, j, k, (unsigned long long)n_draws[k]);
+          return false;
+        }
+    }
+    return true;
+  };
+  rell_staged_t st;
+  if (rell_stage(who, site_lnl, n_rows, n_patterns, pattern_weights, n_replicates, own_checks, st) != RDAMD_SUCCESS)
     return RDAMD_FAILURE;
-  }
-  // pattern p owns pattern_weights[p] consecutive columns
-  std::vector<unsigned> col2pat;
-  col2pat.reserve((size_t)N);
-  for (unsigned p = 0; p < n_patterns; ++p) col2pat.insert(col2pat.end(), pattern_weights[p], p);
   // longest first; equal lengths do not occur
   rdamd::rell_scales_t scales;
   scales.n = n_scales;
@@ -134,41 +162,27 @@ int rdamd_rell_multiscale(const double *site_lnl, unsigned int n_rows, unsigned 
     scales.seed[s] = on ? rdamd::rell_scale_seed(seed, order[s]) : 0u;
   }
 
-  const rdamd::rell_shape_t shape = rdamd::rell_shape(n_rows);
-  const unsigned chunks = rdamd::rell_row_chunks(shape);
-  const size_t cells = (size_t)n_rows * n_patterns, count_cells = (size_t)n_scales * n_rows,
-               out_cells = (size_t)n_scales * n_replicates * n_rows,
+  const unsigned chunks = rdamd::rell_row_chunks(st.shape);
+  const size_t count_cells = (size_t)n_scales * n_rows, out_cells = (size_t)n_scales * n_replicates * n_rows,
                chunk_cells = (size_t)n_scales * n_replicates * chunks;
-  multiscale_buffers_t d;
-  RDAMD_HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&d.t0), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&d.t1), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.rows, cells * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.table, (size_t)n_patterns * shape.padded * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.col2pat, (size_t)N * sizeof(unsigned)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.counts, count_cells * sizeof(unsigned)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemcpy(d.rows, site_lnl, cells * sizeof(double), hipMemcpyHostToDevice), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemcpy(d.col2pat, col2pat.data(), (size_t)N * sizeof(unsigned), hipMemcpyHostToDevice),
-                RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemsetAsync(d.counts, 0, count_cells * sizeof(unsigned), d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(rdamd::launch_rell_transpose(d.rows, n_rows, n_patterns, shape, d.table, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipStreamSynchronize(d.stream), RDAMD_FAILURE);
-  (void)hipFree(d.rows);   // (the row-major copy has served: the large shapes need the room)
-  d.rows = nullptr;
-  if (sums) RDAMD_HIP_TRY(hipMalloc(&d.sums, out_cells * sizeof(double)), RDAMD_FAILURE);
+  device_array_t<double> d_sums, d_chunk_max;
+  device_array_t<unsigned> d_counts, d_chunk_row;
+  RDAMD_HIP_TRY(d_counts.alloc(count_cells), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMemsetAsync(d_counts, 0, count_cells * sizeof(unsigned), st.stream), RDAMD_FAILURE);
+  if (sums) RDAMD_HIP_TRY(d_sums.alloc(out_cells), RDAMD_FAILURE);
   if (chunks > 1) {
-    RDAMD_HIP_TRY(hipMalloc(&d.chunk_max, chunk_cells * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.chunk_row, chunk_cells * sizeof(unsigned)), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d_chunk_max.alloc(chunk_cells), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d_chunk_row.alloc(chunk_cells), RDAMD_FAILURE);
   }
-  RDAMD_HIP_TRY(hipEventRecord(d.t0, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(rdamd::launch_rell_multiscale(d.table, shape, d.col2pat, (unsigned)N, n_rows, n_replicates, scales,
-                                              d.counts, d.sums, d.chunk_max, d.chunk_row, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventRecord(d.t1, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipStreamSynchronize(d.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventRecord(st.t0, st.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(rdamd::launch_rell_multiscale(st.table, st.shape, st.col2pat, st.N, n_rows, n_replicates, scales,
+                                              d_counts, d_sums, d_chunk_max, d_chunk_row, st.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventRecord(st.t1, st.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipStreamSynchronize(st.stream), RDAMD_FAILURE);
   float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, d.t0, d.t1) == hipSuccess) g_last_multiscale_ms = ms;
-  RDAMD_HIP_TRY(hipMemcpy(counts, d.counts, count_cells * sizeof(unsigned), hipMemcpyDeviceToHost), RDAMD_FAILURE);
-  if (sums) RDAMD_HIP_TRY(hipMemcpy(sums, d.sums, out_cells * sizeof(double), hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (hipEventElapsedTime(&ms, st.t0, st.t1) == hipSuccess) g_last_multiscale_ms = ms;
+  RDAMD_HIP_TRY(hipMemcpy(counts, d_counts, count_cells * sizeof(unsigned), hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (sums) RDAMD_HIP_TRY(hipMemcpy(sums, d_sums, out_cells * sizeof(double), hipMemcpyDeviceToHost), RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 
@@ -207,98 +221,81 @@ int rell_run(const char *who, const double *site_lnl, unsigned int n_rows, unsig
     set_error(62, "%s: p_kh and p_sh are required", who);
     return RDAMD_FAILURE;
   }
-  if (n_rows == 0 || n_patterns == 0 || n_replicates == 0) {
-    set_error(62, "%s: nothing to resample (%u rows, %u patterns, %u replicates)", who, n_rows, n_patterns,
-              n_replicates);
-    return RDAMD_FAILURE;
-  }
-  if (tests && n_replicates < 2) {
-    set_error(62, "%s: the tests need at least 2 replicates", who);
-    return RDAMD_FAILURE;
-  }
   const bool pairs = tests && (tests->p_wsh || tests->spread);
-  if (pairs && n_rows > rdamd::RELL_MAX_PAIR_ROWS) {
-    set_error(62, "%s: p_wsh and spread take a table of n_rows^2 doubles; at most %u rows are supported (%u given)",
-              who, rdamd::RELL_MAX_PAIR_ROWS, n_rows);
+  const auto own_checks = [&] {
+    if (tests && n_replicates < 2) {
+      set_error(62, "%s: the tests need at least 2 replicates", who);
+      return false;
+    }
+    if (pairs && n_rows > rdamd::RELL_MAX_PAIR_ROWS) {
+      set_error(62, "%s: p_wsh and spread take a table of n_rows^2 doubles; at most %u rows are supported (%u given)",
+                who, rdamd::RELL_MAX_PAIR_ROWS, n_rows);
+      return false;
+    }
+    return true;
+  };
+  rell_staged_t st;
+  if (rell_stage(who, site_lnl, n_rows, n_patterns, pattern_weights, n_replicates, own_checks, st) != RDAMD_SUCCESS)
     return RDAMD_FAILURE;
-  }
-  uint64_t N = 0;
-  for (unsigned p = 0; p < n_patterns; ++p) N += pattern_weights[p];
-  if (N == 0 || (N >> 32)) {
-    set_error(62, "%s: the pattern weights sum to %llu columns; 1 .. 2^32 - 1 are supported", who,
-              (unsigned long long)N);
-    return RDAMD_FAILURE;
-  }
-  // pattern p owns pattern_weights[p] consecutive columns
-  std::vector<unsigned> col2pat;
-  col2pat.reserve((size_t)N);
-  for (unsigned p = 0; p < n_patterns; ++p) col2pat.insert(col2pat.end(), pattern_weights[p], p);
-
-  const rdamd::rell_shape_t shape = rdamd::rell_shape(n_rows);
-  const size_t cells = (size_t)n_rows * n_patterns, out_cells = (size_t)n_replicates * n_rows;
-  rell_buffers_t d;
-  RDAMD_HIP_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&d.t0), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&d.t1), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.rows, cells * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.table, (size_t)n_patterns * shape.padded * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.col2pat, (size_t)N * sizeof(unsigned)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemcpy(d.rows, site_lnl, cells * sizeof(double), hipMemcpyHostToDevice), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemcpy(d.col2pat, col2pat.data(), (size_t)N * sizeof(unsigned), hipMemcpyHostToDevice),
-                RDAMD_FAILURE);
-  RDAMD_HIP_TRY(rdamd::launch_rell_transpose(d.rows, n_rows, n_patterns, shape, d.table, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipStreamSynchronize(d.stream), RDAMD_FAILURE);
-  (void)hipFree(d.rows);   // (the row-major copy has served: the large shapes need the room)
-  d.rows = nullptr;
-  RDAMD_HIP_TRY(hipMalloc(&d.sums, out_cells * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.weights, out_cells * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.winner, (size_t)n_replicates * sizeof(unsigned)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.bp, (size_t)n_rows * sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&d.elw, (size_t)n_rows * sizeof(double)), RDAMD_FAILURE);
+  const hipStream_t stream = st.stream;
+  const size_t out_cells = (size_t)n_replicates * n_rows;
+  struct {
+    device_array_t<double> sums, weights, bp, elw;
+    device_array_t<unsigned> winner;
+    // the tests' own
+    device_array_t<double> partial, lnl, mean, cmax, cbest, rinv, spread, tobs;
+    device_array_t<unsigned> pattern_weights, best, counts;   // counts: kh, sh, wsh
+    event_t t2;
+  } d;
+  RDAMD_HIP_TRY(d.sums.alloc(out_cells), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(d.weights.alloc(out_cells), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(d.winner.alloc(n_replicates), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(d.bp.alloc(n_rows), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(d.elw.alloc(n_rows), RDAMD_FAILURE);
   if (tests) {
     const size_t chunks = std::max(rdamd::rell_chunks(n_patterns), rdamd::rell_chunks(n_replicates));
-    RDAMD_HIP_TRY(hipEventCreate(&d.t2), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.pattern_weights, (size_t)n_patterns * sizeof(unsigned)), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(hipEventCreate(&d.t2.h), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.pattern_weights.alloc(n_patterns), RDAMD_FAILURE);
     RDAMD_HIP_TRY(hipMemcpy(d.pattern_weights, pattern_weights, (size_t)n_patterns * sizeof(unsigned),
                             hipMemcpyHostToDevice), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.partial, chunks * n_rows * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.lnl, (size_t)n_rows * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.mean, (size_t)n_rows * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.tobs, (size_t)n_rows * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.cmax, (size_t)n_replicates * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.cbest, (size_t)n_replicates * sizeof(double)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.best, sizeof(unsigned)), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipMalloc(&d.counts, 3 * (size_t)n_rows * sizeof(unsigned)), RDAMD_FAILURE);
-    if (pairs) RDAMD_HIP_TRY(hipMalloc(&d.rinv, (size_t)n_rows * n_rows * sizeof(double)), RDAMD_FAILURE);
-    if (tests->spread) RDAMD_HIP_TRY(hipMalloc(&d.spread, (size_t)n_rows * n_rows * sizeof(double)), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.partial.alloc(chunks * n_rows), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.lnl.alloc(n_rows), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.mean.alloc(n_rows), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.tobs.alloc(n_rows), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.cmax.alloc(n_replicates), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.cbest.alloc(n_replicates), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.best.alloc(1), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(d.counts.alloc(3 * (size_t)n_rows), RDAMD_FAILURE);
+    if (pairs) RDAMD_HIP_TRY(d.rinv.alloc((size_t)n_rows * n_rows), RDAMD_FAILURE);
+    if (tests->spread) RDAMD_HIP_TRY(d.spread.alloc((size_t)n_rows * n_rows), RDAMD_FAILURE);
   }
 
-  RDAMD_HIP_TRY(hipEventRecord(d.t0, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(rdamd::launch_rell_sums(d.table, shape, d.col2pat, (unsigned)N, n_rows, n_replicates, seed, d.sums,
-                                        d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventRecord(d.t1, d.stream), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(rdamd::launch_rell_support(d.sums, n_rows, n_replicates, d.weights, d.winner, d.bp, d.elw, d.stream),
+  RDAMD_HIP_TRY(hipEventRecord(st.t0, stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(rdamd::launch_rell_sums(st.table, st.shape, st.col2pat, st.N, n_rows, n_replicates, seed, d.sums,
+                                        stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventRecord(st.t1, stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(rdamd::launch_rell_support(d.sums, n_rows, n_replicates, d.weights, d.winner, d.bp, d.elw, stream),
                 RDAMD_FAILURE);
   if (tests) {
     unsigned *kh = d.counts, *sh = d.counts + n_rows, *wsh = d.counts + 2 * (size_t)n_rows;
-    RDAMD_HIP_TRY(rdamd::launch_rell_totals(d.table, shape.padded, d.pattern_weights, n_patterns, n_rows, d.partial,
-                                            d.lnl, d.best, d.stream), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(rdamd::launch_rell_means(d.sums, n_rows, n_replicates, d.partial, d.mean, d.stream), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(rdamd::launch_rell_totals(st.table, st.shape.padded, d.pattern_weights, n_patterns, n_rows, d.partial,
+                                            d.lnl, d.best, stream), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(rdamd::launch_rell_means(d.sums, n_rows, n_replicates, d.partial, d.mean, stream), RDAMD_FAILURE);
     RDAMD_HIP_TRY(rdamd::launch_rell_kh_sh(d.sums, d.mean, d.lnl, d.best, n_rows, n_replicates, d.cmax, d.cbest, kh,
-                                           sh, d.stream), RDAMD_FAILURE);
+                                           sh, stream), RDAMD_FAILURE);
     if (pairs)
-      RDAMD_HIP_TRY(rdamd::launch_rell_spreads(d.sums, d.mean, n_rows, n_replicates, d.rinv, d.spread, d.stream),
+      RDAMD_HIP_TRY(rdamd::launch_rell_spreads(d.sums, d.mean, n_rows, n_replicates, d.rinv, d.spread, stream),
                     RDAMD_FAILURE);
     if (tests->p_wsh)
       RDAMD_HIP_TRY(rdamd::launch_rell_wsh(d.sums, d.mean, d.lnl, d.rinv, n_rows, n_replicates, d.tobs, wsh,
-                                           d.stream), RDAMD_FAILURE);
-    RDAMD_HIP_TRY(hipEventRecord(d.t2, d.stream), RDAMD_FAILURE);
+                                           stream), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(hipEventRecord(d.t2, stream), RDAMD_FAILURE);
   }
-  RDAMD_HIP_TRY(hipStreamSynchronize(d.stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipStreamSynchronize(stream), RDAMD_FAILURE);
   float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, d.t0, d.t1) == hipSuccess) g_last_resample_ms = ms;
+  if (hipEventElapsedTime(&ms, st.t0, st.t1) == hipSuccess) g_last_resample_ms = ms;
   if (tests) {
-    if (hipEventElapsedTime(&ms, d.t1, d.t2) == hipSuccess) g_last_tests_ms = ms;
+    if (hipEventElapsedTime(&ms, st.t1, d.t2) == hipSuccess) g_last_tests_ms = ms;
     std::vector<unsigned> counts(3 * (size_t)n_rows);
     RDAMD_HIP_TRY(hipMemcpy(counts.data(), d.counts, counts.size() * sizeof(unsigned), hipMemcpyDeviceToHost),
                   RDAMD_FAILURE);

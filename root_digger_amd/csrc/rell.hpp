@@ -1,5 +1,6 @@
-// RELL bootstrap (include/root_digger_amd.h, rdamd_rell_bootstrap): the draw function shared by
-// host and device, and the launchers of kernels_rell.hip.
+// RELL bootstrap (include/root_digger_amd.h, rdamd_rell_bootstrap and rdamd_rell_multiscale): the
+// draw function shared by host and device, the tie-break of a replicate's winner shared by the
+// kernels, and the launchers of kernels_rell.hip and kernels_rell_tests.hip.
 #pragma once
 
 #include <cstdint>
@@ -20,6 +21,18 @@ __host__ __device__ inline uint64_t rell_key(uint64_t seed, uint64_t b) { return
 __host__ __device__ inline uint32_t rell_draw(uint64_t key, uint64_t d, uint32_t N) {
   return (uint32_t)(((rell_sm(key + d) >> 32) * (uint64_t)N) >> 32);
 }
+
+#ifdef __HIPCC__
+// A running (largest value, the lowest row that has it); RELL_NO_ROW: no row yet, the value means nothing.
+constexpr unsigned RELL_NO_ROW = 0xffffffffu;
+// One butterfly step: this lane's pair merged with lane ^ off's.  The larger value wins, among
+// equals the lowest row, an empty pair never.
+__device__ __forceinline__ void rell_merge_best(double &best, unsigned &at, int off) {
+  const double ob = __shfl_xor(best, off);
+  const unsigned oa = (unsigned)__shfl_xor((int)at, off);
+  if (oa != RELL_NO_ROW && (at == RELL_NO_ROW || ob > best || (ob == best && oa < at))) { best = ob; at = oa; }
+}
+#endif
 
 // How the rows (candidate roots) of one replicate are laid over a wave: `lanes` lanes per replicate
 // (8, 16, 32 or 64; 64 / lanes replicates share a wave), `per_lane` consecutive rows per lane
@@ -43,7 +56,8 @@ hipError_t launch_rell_support(const double *d_sums, unsigned n_rows, unsigned n
                                double *d_weights, unsigned *d_winner, double *d_bp, double *d_elw,
                                hipStream_t stream);
 
-// ---- multiscale bootstrap (rdamd_rell_multiscale; kernels_rell_multiscale.hip)
+// ---- multiscale bootstrap (rdamd_rell_multiscale; kernels_rell.hip: launch_rell_sums' kernel
+// template with a scale per wave and the winner found in place)
 constexpr unsigned RELL_MAX_SCALES = 64;
 // seed of scale k (rdamd_rell_scale_seed)
 inline uint64_t rell_scale_seed(uint64_t seed, uint64_t k) { return rell_sm(seed + k + 1); }

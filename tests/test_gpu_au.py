@@ -1,6 +1,7 @@
-"""rell_multiscale / au_test (rdamd_rell_multiscale, csrc/kernels_rell_multiscale.hip) against the
-NumPy multiscale bootstrap of tests/test_au_host.py, the order rule of the sums at every scale and
-launch shape, and `rd_amd --rell B --au`.
+"""rell_multiscale / au_test (rdamd_rell_multiscale, csrc/kernels_rell.hip: the bootstrap's
+rell_resample_kernel with a scale per wave) against the NumPy multiscale bootstrap of
+tests/test_au_host.py, the order rule of the sums at every scale and launch shape, the bootstrap
+itself at every launch shape, and `rd_amd --rell B --au`.
 
 Bounds (derived, not tuned), u = 2**-53, scale k with M_k draws, S = the reference sums of the scale:
   sums    within 2 M_k u max|S|: M_k same-sign additions on the device, at most M_k roundings in
@@ -98,6 +99,21 @@ def test_the_scale_of_the_alignment_is_the_bootstrap(name):
     bp, _, plain = rd.rell_bootstrap(matrix, weights, B, seed=rd.rell_scale_seed(seed, 5), return_sums=True)
     assert np.array_equal(sums[5], plain)
     assert np.array_equal(counts[5], np.rint(bp * B)) and np.all(np.abs(bp * B - counts[5]) < 1e-9)
+
+
+def test_every_launch_shape_of_a_scale_is_the_bootstrap():
+    """the bootstrap and the multiscale bootstrap are one kernel template: at every lane count and
+    rows per lane, and in the chunked path beyond 256 rows, the scale that draws N columns has the
+    bootstrap's bits and its winners (no tolerance: equal, or the two tails have diverged)"""
+    matrix = random_walk_matrix(300, 1237, 3)
+    weights = np.random.default_rng(6).integers(1, 4, 1237).astype(np.uint32)
+    n, B, seed = int(weights.sum()), 37, 3
+    n_draws = [n // 2, n, 7 * n // 5]
+    for rows in (1, 5, 9, 17, 33, 64, 65, 129, 257, 300):
+        counts, sums = rd.rell_multiscale(matrix[:rows], weights, n_draws, B, seed, return_sums=True)
+        bp, _, plain = rd.rell_bootstrap(matrix[:rows], weights, B, seed=rd.rell_scale_seed(seed, 1), return_sums=True)
+        assert np.array_equal(sums[1], plain), rows
+        assert np.array_equal(counts[1], np.rint(bp * B)), rows
 
 
 def test_launch_shapes_give_the_same_bits():

@@ -1,6 +1,6 @@
-"""rell_bootstrap (rdamd_rell_bootstrap, csrc/kernels_rell.hip) against a NumPy re-implementation
-of its definition in include/root_digger_amd.h, the order rule of its sums, and the
-`rd_amd --rell / --site-lh` outputs.
+"""rell_bootstrap (rdamd_rell_bootstrap, csrc/kernels_rell.hip: rell_resample_kernel without the
+scales, then the support kernels) against a NumPy re-implementation of its definition in
+include/root_digger_amd.h, the order rule of its sums, and the `rd_amd --rell / --site-lh` outputs.
 
 Bounds (derived, not tuned), u = 2**-53, N columns:
   sums   relative 2 N u: N same-sign additions on the device, at most N roundings in the reference;
