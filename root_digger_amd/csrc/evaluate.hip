@@ -8,14 +8,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <unordered_map>
 
 #include <cstdlib>
 #include "clades.hpp"
 #include "common.hpp"
 #include "fused.hpp"
-#include "traversal_compiler.hpp"
+#include "schedule_plan.hpp"
 
 struct rdamd_schedule {
   rdamd_partition *part = nullptr;
@@ -33,7 +32,6 @@ struct rdamd_schedule {
   // launch's tables make the pseudo-tips' missing rescale counts matter, fused.hpp)
   rdamd::FusedOp *d_prog_plain = nullptr;     // == d_prog without pseudo-tips
   unsigned n_ops_plain = 0, depth_plain = 0, reg_levels_plain = 1;
-  unsigned lds_pos = 0, lds_pos_plain = 0;    // FusedJob::lds_pos of the two programs
   rdamd::CladeStep *d_steps = nullptr;
   rdamd::CladeGroup *d_groups = nullptr;
   uint32_t *d_tipmask = nullptr;              // 20 states: bit m = P-matrix m belongs to a branch that ends in a tip
@@ -86,13 +84,18 @@ struct FusedWorkspace {
   } pend;
 };
 
-void fused_workspace_free(FusedWorkspace *w) {
-  if (!w) return;
+// every buffer a workspace owns, device and pinned (the pointers are left as they are)
+static void workspace_free_buffers(FusedWorkspace *w) {
   void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20, w->d_spill20};
   for (void *d : dev)
     if (d) (void)hipFree(d);
   if (w->h_out) (void)hipHostFree(w->h_out);
   if (w->h_in) (void)hipHostFree(w->h_in);
+}
+
+void fused_workspace_free(FusedWorkspace *w) {
+  if (!w) return;
+  workspace_free_buffers(w);
   if (w->ev_ready) (void)hipEventDestroy(w->ev_ready);
   if (w->ev_done) (void)hipEventDestroy(w->ev_done);
   delete w;
@@ -140,17 +143,34 @@ static void schedule_block_release(rdamd_partition *p, char *ptr, size_t bytes) 
   else p->sched_retired.push_back({ptr, bytes, seq});
 }
 
+// bytes of a batch's inputs: jobs + Q + frequencies + rates + rate weights, the layout of the pinned
+// staging block and of its device mirror (the batch's any-unsafe word, 8 bytes, sits behind them)
+static size_t input_block_bytes(const rdamd_partition *p, size_t n_jobs) {
+  const size_t R = p->rate_cats, K = p->states;
+  return n_jobs * (sizeof(FusedJob) + sizeof(double) * (K * K + K + 2 * R));
+}
+
+// A workspace buffer that a batch has outgrown (`have`, in the caller's units): nothing queued may
+// still read the old one.
+template <class T>
+static hipError_t grow_buffer(rdamd_partition *p, T *&buf, size_t &have, size_t want, size_t bytes) {
+  hipError_t e = sync_streams(p);
+  if (e != hipSuccess) return e;
+  if (buf) (void)hipFree(buf);
+  buf = nullptr;
+  have = 0;
+  e = hipMalloc((void **)&buf, bytes);
+  if (e == hipSuccess) have = want;
+  return e;
+}
+
 static hipError_t ensure_workspace(rdamd_partition *p, FusedWorkspace *&slot, unsigned n_jobs) {
   if (!slot) slot = new FusedWorkspace();
   FusedWorkspace *w = slot;
   if (n_jobs <= w->cap_jobs) return hipSuccess;
   hipError_t e = sync_streams(p);
   if (e != hipSuccess) return e;
-  void *dev[] = {w->d_in, w->d_pmat, w->d_tiptab, w->d_partials, w->d_out, w->d_clade_scratch, w->d_export_cnt, w->d_qpow20, w->d_spill20};
-  for (void *d : dev)
-    if (d) (void)hipFree(d);
-  if (w->h_out) (void)hipHostFree(w->h_out);
-  if (w->h_in) (void)hipHostFree(w->h_in);
+  workspace_free_buffers(w);
   {
     hipEvent_t r = w->ev_ready, d = w->ev_done;   // (the events survive a larger workspace)
     *w = FusedWorkspace();
@@ -170,7 +190,8 @@ static hipError_t ensure_workspace(rdamd_partition *p, FusedWorkspace *&slot, un
   // jobs + Q + frequencies + rates + rate weights of a batch live in ONE device block
   // with the layout of the pinned staging block: one copy per batch instead of five
   // (+ 8 bytes: the batch's any-unsafe word, zeroed by the same copy, FusedArgs::any_unsafe)
-  A(w->d_in, (size_t)cap * (sizeof(FusedJob) + sizeof(double) * (K * K + K + 2 * R)) + 8);
+  w->h_in_bytes = input_block_bytes(p, cap) + 8;
+  A(w->d_in, w->h_in_bytes);
   A(w->d_pmat, sizeof(double) * pm_per_job * cap);
   if (K == 20) A(w->d_qpow20, sizeof(double) * fused20_qpow_doubles() * cap);
   w->tiptab_doubles = (K == 4 ? pm_per_job * 4 : (size_t)p->prob_matrices * R * kFused20TabDoubles) * cap;
@@ -180,7 +201,6 @@ static hipError_t ensure_workspace(rdamd_partition *p, FusedWorkspace *&slot, un
 #undef A
   e = hipHostMalloc((void **)&w->h_out, sizeof(double) * (cap + 1), hipHostMallocDefault);   // (+ the any-unsafe word)
   if (e != hipSuccess) return e;
-  w->h_in_bytes = (size_t)cap * (sizeof(FusedJob) + sizeof(double) * (K * K + K + 2 * R)) + 8;
   e = hipHostMalloc((void **)&w->h_in, w->h_in_bytes, hipHostMallocDefault);
   if (e != hipSuccess) return e;
   w->cap_jobs = cap;
@@ -196,6 +216,54 @@ static void rdamd_schedule_destroy_locked(rdamd_schedule *s) {
   if (!s) return;
   if (s->part) schedule_block_release(s->part, s->d_block, s->block_bytes);
   delete s;
+}
+
+// compile_program (schedule_plan.hpp), with the refusal worded
+static bool compile_or_refuse(const ScheduleShape &sh, const std::vector<rdamd_operation_t> &list, const ClvMap &pseudo_row,
+                              const ClvMap &pseudo_wide, Program &out) {
+  const unsigned lost = compile_program(sh, list, pseudo_row, pseudo_wide, out);
+  if (lost)
+    set_error(43, "rdamd_schedule_create: %u of %u operations are not reachable from the "
+                  "root operation", lost, (unsigned)list.size());
+  return lost == 0;
+}
+
+// every operation's node in the partition's clade cache: its id and its class count
+static void intern_clades(rdamd_partition *p, const rdamd_operation_t *ops, unsigned n_ops, const ClvMap &producer,
+                          std::vector<unsigned> &node_id, std::vector<unsigned> &n_classes) {
+  node_id.assign(n_ops, 0);
+  n_classes.assign(n_ops, 0);
+  auto id_of = [&](unsigned clv) { return clv < p->tips ? clv : node_id[producer.at(clv)]; };
+  for (unsigned i = 0; i < n_ops; ++i) {
+    const rdamd_operation_t &o = ops[i];
+    node_id[i] = clade_intern(p, id_of(o.child1_clv_index), id_of(o.child2_clv_index),
+                              o.child1_matrix_index, o.child2_matrix_index);
+    n_classes[i] = clade_node(*p->clades, p->tips, node_id[i])->n_classes;
+  }
+}
+
+// the selected clades' class maps and the pseudo-tips' code rows on the device; pseudo_row: clv of a
+// pseudo-tip -> its row in the code arena.  false: a HIP call failed (the error is set)
+static bool upload_clades(rdamd_partition *p, const rdamd_operation_t *ops, CladeSelection &sel,
+                          const std::vector<unsigned> &node_id, bool wide_mode, ClvMap &pseudo_row) {
+  for (CladeStep &st : sel.steps) {
+    RDAMD_HIP_TRY(clade_upload_map(p, st.pad), false);
+    st.map_off = (uint32_t)clade_node(*p->clades, p->tips, st.pad)->map_off;
+    st.pad = 0;
+  }
+  for (unsigned i : sel.tip_ops) {
+    const hipError_t ce = clade_upload_codes(p, node_id[i], wide_mode);
+    if (ce != hipSuccess && p->code_arena_full) {
+      // no room for another row of class codes within 32-bit offsets: this schedule runs its
+      // plain program (rows handed out earlier stay valid for the schedules that hold them)
+      sel = CladeSelection();
+      pseudo_row.clear();
+      return true;
+    }
+    RDAMD_HIP_TRY(ce, false);
+    pseudo_row[ops[i].parent_clv_index] = (unsigned)clade_node(*p->clades, p->tips, node_id[i])->code_row[wide_mode];
+  }
+  return true;
 }
 
 // allow_repeats = false: the plain program only, 16-row tables, nothing of the clade cache is
@@ -220,178 +288,42 @@ static rdamd_schedule_t *schedule_create_impl(rdamd_partition_t *p, const rdamd_
                   "32-bit offsets (tips*sites or matrices*rates*512 >= 4 GiB)");
     return nullptr;
   }
-  // ---- validation: a full post-order traversal ------------------------------------------
-  const unsigned nclv = p->tips + p->clv_buffers;
-  std::unordered_map<unsigned, unsigned> producer;   // clv -> op index
-  std::vector<int> consumer(n_ops, -1);              // op -> the op that takes its result
-  for (unsigned i = 0; i < n_ops; ++i) {
-    const rdamd_operation_t &o = ops[i];
-    bool bad = o.parent_clv_index < p->tips || o.parent_clv_index >= nclv ||
-               o.child1_clv_index >= nclv || o.child2_clv_index >= nclv ||
-               o.child1_matrix_index >= p->prob_matrices ||
-               o.child2_matrix_index >= p->prob_matrices;
-    for (unsigned ch : {o.child1_clv_index, o.child2_clv_index}) {
-      if (ch < p->tips) continue;
-      auto it = producer.find(ch);
-      if (it == producer.end() || consumer[it->second] >= 0) bad = true;   // not yet computed / used twice
-      else consumer[it->second] = (int)i;
-    }
-    if (producer.count(o.parent_clv_index)) bad = true;       // written twice
-    if (bad) {
-      set_error(42, "rdamd_schedule_create: operation %u is not part of a valid post-order "
-                    "traversal (the fused evaluator needs the full schedule of "
-                    "generate_operations)", i);
-      return nullptr;
-    }
-    producer[o.parent_clv_index] = i;
+  const ScheduleCheck v = validate_schedule(p->tips, p->clv_buffers, p->prob_matrices, ops, n_ops, matrix_indices,
+                                            branch_lengths, n_matrices);
+  if (v.kind == ScheduleCheck::kOperation) {
+    set_error(42, "rdamd_schedule_create: operation %u is not part of a valid post-order "
+                  "traversal (the fused evaluator needs the full schedule of "
+                  "generate_operations)", v.at);
+    return nullptr;
   }
-  std::vector<double> brlen(p->prob_matrices, 0.0);
-  for (unsigned m = 0; m < n_matrices; ++m) {
-    if (matrix_indices[m] >= p->prob_matrices || !(branch_lengths[m] >= 0.0) ||
-        !std::isfinite(branch_lengths[m])) {
-      set_error(9, "rdamd_schedule_create: invalid branch (matrix %u, length %g)",
-                matrix_indices[m], branch_lengths[m]);
-      return nullptr;
-    }
-    brlen[matrix_indices[m]] = branch_lengths[m];
-  }
-
-  // ---- one program from one operation list -------------------------------------------------
-  struct Program {
-    std::vector<FusedOp> steps;
-    unsigned depth = 1, reg_levels = 1, matvecs = 0;
-    unsigned lds_pos = 0;   // 4 states, stacks with private-segment levels: which in-memory entry sits in LDS
-  };
-  // 64-row tables (and the 16-bit code arena that goes with them) when the partition's class
-  // limit asks for them; every program of the schedule then addresses that arena
-  // A pseudo-tip's table is written into the tip-table slot of the branch above it
-  // (kernels_clade.hip): that slot is only free when the branch's matrix index is used by this
-  // one child.  The C ABI (like coraxlib's) lets a caller share a matrix index between
-  // branches; such a list is evaluated without folding -- its tip tables are all code-indexed.
-  bool matrix_shared = false;
-  {
-    std::vector<unsigned char> uses(p->prob_matrices, 0);
-    for (unsigned i = 0; i < n_ops; ++i)
-      for (unsigned m : {ops[i].child1_matrix_index, ops[i].child2_matrix_index})
-        if (uses[m]++) matrix_shared = true;
+  if (v.kind == ScheduleCheck::kBranch) {
+    set_error(9, "rdamd_schedule_create: invalid branch (matrix %u, length %g)",
+              matrix_indices[v.at], branch_lengths[v.at]);
+    return nullptr;
   }
   const bool repeats = allow_repeats && !k20 && (p->attributes & RDAMD_ATTRIB_SITE_REPEATS) && p->sites > 0;
   if (repeats && !p->clades) p->clades = new CladeCache();
+  // 64-row tables (and the 16-bit code arena that goes with them) when the partition's class
+  // limit asks for them; every program of the schedule then addresses that arena
   // (the 16-bit arena needs twice the bytes per row: a partition whose tip rows alone would not
   // fit 32-bit offsets there keeps the 8-bit arena and 16-row tables -- for every schedule, so
   // that all of them can share a launch)
   const bool wide_fits = ((size_t)p->tips + 16) * p->tip_stride() * 2 + kTipcodePad <= 0xffffffffull;
-  const bool wide_mode = repeats && p->clades->max_classes > 16 && wide_fits;
-  const unsigned class_limit = wide_mode ? 64u : 16u;   // what this schedule's table slots hold
-  auto compile = [&](const std::vector<rdamd_operation_t> &list,
-                     const std::unordered_map<unsigned, unsigned> &pseudo_row,
-                     const std::unordered_map<unsigned, unsigned> &pseudo_wide, Program &out) -> bool {
-    Compiler c;
-    c.ops = list.data(); c.n_ops = (unsigned)list.size(); c.tips = p->tips; c.sites = p->sites;
-    c.tip_stride = p->tip_stride() * (wide_mode ? 2u : 1u); c.rate_cats = p->rate_cats;
-    c.unit = p->rate_cats * (k20 ? 3200u : 128u);
-    c.split_park = k20;
-    c.pseudo_row = pseudo_row;
-    c.pseudo_wide = pseudo_wide;
-    c.wide_base = 8u * p->prob_matrices * p->rate_cats * 16u;
-    c.dma_offsets = !k20 && wide_mode;
-    c.place_parks = !k20 && wide_mode;   // (the kernels of these programs: one register slot, one LDS slot, a private-segment stack)
-    {   // the steps that compute the root operation's inner children (fused.hpp, 0x8000 / 0x10000)
-      const rdamd_operation_t &root = list.back();
-      if (root.child1_clv_index >= p->tips) c.mark_clv[0] = root.child1_clv_index;
-      if (root.child2_clv_index >= p->tips) c.mark_clv[1] = root.child2_clv_index;
-    }
-    for (unsigned i = 0; i < c.n_ops; ++i) c.producer[list[i].parent_clv_index] = i;
-    c.need.assign(c.n_ops, 0);
-    c.compute_need(c.n_ops - 1);
-    c.out.reserve(c.n_ops);
-    c.emit(c.n_ops - 1, false, 0);
-    // second pass: the register slot to the busiest stack level, the LDS slot to the runner-up
-    // (traversal_compiler.hpp)
-    // (two register levels: from 8 in-memory entries on where the kernel has private-segment
-    // levels, i.e. 64-row table slots; from 3 on an all-LDS stack -- kernels_fused.hip)
-    const unsigned lds_pos = c.place_levels(k20 ? 0u : (wide_mode ? 1u + kFusedSpillLevels : 3u), kFusedSpillLevels - 1u);
-    size_t n_real = 0;
-    for (const FusedOp &f : c.out)
-      if (!c.split_park || (f.flags & 3u) != kFusedPark) ++n_real;
-    if (n_real != c.n_ops) {
-      set_error(43, "rdamd_schedule_create: %u of %u operations are not reachable from the "
-                    "root operation", (unsigned)(c.n_ops - n_real), c.n_ops);
-      return false;
-    }
-    // LDS levels = stack depth minus the register levels (at least one is allocated)
-    // (20 states: parking steps count as steps)
-    // (parks placed one by one: the LDS slot + the private-segment entries)
-    out.depth = !c.park_class.empty() ? 1u + c.mem_depth
-                                      : std::max(1u, c.max_depth > c.reg_levels ? c.max_depth - c.reg_levels : 0);
-    out.reg_levels = c.reg_levels;
-    out.lds_pos = lds_pos;
-    out.matvecs = c.matvecs;
-    out.steps = std::move(c.out);
-    return true;
-  };
+  ScheduleShape sh;
+  sh.tips = p->tips; sh.sites = p->sites; sh.tip_stride = p->tip_stride(); sh.rate_cats = p->rate_cats;
+  sh.prob_matrices = p->prob_matrices; sh.k20 = k20;
+  sh.wide_mode = repeats && p->clades->max_classes > 16 && wide_fits;
 
   const std::vector<rdamd_operation_t> all_ops(ops, ops + n_ops);
   Program plain, folded;
-  if (!compile(all_ops, {}, {}, plain)) return nullptr;
+  if (!compile_or_refuse(sh, all_ops, {}, {}, plain)) return nullptr;
 
-  // ---- subtree site repeats: which clades become pseudo-tips (clades.hpp) -----------------
-  // A node is SMALL when the sites fall into at most max_classes classes below it; small is
-  // inherited downwards, so the small nodes form whole subtrees and the topmost small node
-  // of each is the pseudo-tip.  The root operation is never folded (a program has >= 1 step).
-  std::vector<char> small(n_ops, 0);
-  std::vector<unsigned> node_id(n_ops, 0);
-  std::vector<CladeStep> steps;
-  std::vector<CladeGroup> groups;
-  std::unordered_map<unsigned, unsigned> pseudo_row, pseudo_wide;
-  unsigned clade_rows = 0, n_wide = 0;
+  CladeSelection sel;
+  std::vector<unsigned> node_id;
   if (repeats) {
-    auto id_of = [&](unsigned clv) { return clv < p->tips ? clv : node_id[producer.at(clv)]; };
-    for (unsigned i = 0; i < n_ops; ++i) {
-      const rdamd_operation_t &o = ops[i];
-      node_id[i] = clade_intern(p, id_of(o.child1_clv_index), id_of(o.child2_clv_index),
-                                o.child1_matrix_index, o.child2_matrix_index);
-      const unsigned nc = clade_node(*p->clades, p->tips, node_id[i])->n_classes;
-      // (a parent has at least as many classes as either child: small is inherited downwards
-      // under any limit)
-      small[i] = i + 1 < n_ops && !matrix_shared && nc > 0 && nc <= class_limit;
-    }
-    // the branch above operation i: the matrix index its consumer uses for it
-    auto mat_above = [&](unsigned i) {
-      const rdamd_operation_t &c = ops[consumer[i]];
-      return c.child1_clv_index == ops[i].parent_clv_index ? c.child1_matrix_index : c.child2_matrix_index;
-    };
-    for (unsigned i = 0; i + 1 < n_ops; ++i) {
-      if (!small[i] || small[consumer[i]]) continue;     // not a pseudo-tip
-      CladeGroup g;
-      g.first = (unsigned)steps.size();
-      // post-order over the small subtree below i; local index = position inside the group
-      std::function<unsigned(unsigned)> walk = [&](unsigned j) -> unsigned {
-        const rdamd_operation_t &o = ops[j];
-        CladeStep st;
-        memset(&st, 0, sizeof st);
-        const unsigned ch[2] = {o.child1_clv_index, o.child2_clv_index};
-        const unsigned mt[2] = {o.child1_matrix_index, o.child2_matrix_index};
-        for (int k = 0; k < 2; ++k)
-          st.src[k] = ch[k] < p->tips ? mt[k] : (0x80000000u | walk(producer.at(ch[k])));
-        const CladeNode *node = clade_node(*p->clades, p->tips, node_id[j]);
-        st.n_classes = node->n_classes;
-        st.out_mat = mat_above(j);
-        st.last = j == i ? 1u : 0u;
-        st.wide_slot = 0xffffffffu;
-        if (j == i && node->n_classes > 16) {
-          st.wide_slot = n_wide;
-          pseudo_wide[o.parent_clv_index] = n_wide++;
-        }
-        st.pad = node_id[j];   // (host only: the map offset is filled in below)
-        clade_rows += node->n_classes;
-        steps.push_back(st);
-        return (unsigned)steps.size() - 1 - g.first;
-      };
-      walk(i);
-      g.count = (unsigned)steps.size() - g.first;
-      groups.push_back(g);
-    }
+    std::vector<unsigned> n_classes;
+    intern_clades(p, ops, n_ops, v.producer, node_id, n_classes);
+    sel = select_clades(ops, n_ops, p->tips, v, node_id, n_classes, sh.wide_mode ? 64u : 16u);   // what this schedule's table slots hold
   }
   rdamd_schedule *s = new rdamd_schedule();
   s->part = p;
@@ -399,85 +331,41 @@ static rdamd_schedule_t *schedule_create_impl(rdamd_partition_t *p, const rdamd_
   s->root_child_clv[0] = ops[n_ops - 1].child1_clv_index; s->root_child_sc[0] = ops[n_ops - 1].child1_scaler_index;
   s->root_child_clv[1] = ops[n_ops - 1].child2_clv_index; s->root_child_sc[1] = ops[n_ops - 1].child2_scaler_index;
 #define TRY(expr) RDAMD_HIP_TRY(expr, (rdamd_schedule_destroy_locked(s), nullptr))
-  s->table_rows = wide_mode ? 64u : 16u;
-  s->n_wide = n_wide;
-  if (wide_mode) TRY(ensure_wide_arena(p));
-  if (!groups.empty()) {
-    for (CladeStep &st : steps) {
-      TRY(clade_upload_map(p, st.pad));
-      st.map_off = (uint32_t)clade_node(*p->clades, p->tips, st.pad)->map_off;
-      st.pad = 0;
-    }
-    std::vector<rdamd_operation_t> kept;
-    for (unsigned i = 0; i < n_ops; ++i) {
-      if (!small[i]) { kept.push_back(ops[i]); continue; }
-      if (small[consumer[i]]) continue;
-      const hipError_t ce = clade_upload_codes(p, node_id[i], wide_mode);
-      if (ce != hipSuccess && p->code_arena_full) {
-        // no room for another row of class codes within 32-bit offsets: this schedule runs its
-        // plain program (rows handed out earlier stay valid for the schedules that hold them)
-        groups.clear(); steps.clear(); pseudo_row.clear(); pseudo_wide.clear();
-        n_wide = 0; clade_rows = 0;
-        break;
-      }
-      TRY(ce);
-      pseudo_row[ops[i].parent_clv_index] = (unsigned)clade_node(*p->clades, p->tips, node_id[i])->code_row[wide_mode];
-    }
-    if (!groups.empty() && !compile(kept, pseudo_row, pseudo_wide, folded)) { rdamd_schedule_destroy_locked(s); return nullptr; }
+  s->table_rows = sh.wide_mode ? 64u : 16u;
+  if (sh.wide_mode) TRY(ensure_wide_arena(p));
+  ClvMap pseudo_row;
+  bool ok = sel.groups.empty() || upload_clades(p, ops, sel, node_id, sh.wide_mode, pseudo_row);
+  // (a full code arena leaves the selection empty: the plain program is the schedule's only one)
+  const bool is_folded = ok && !sel.groups.empty();
+  if (is_folded) ok = compile_or_refuse(sh, sel.kept(ops), pseudo_row, sel.pseudo_wide, folded);
+  if (!ok) {
+    rdamd_schedule_destroy_locked(s);
+    return nullptr;
   }
-  s->n_wide = n_wide;
-  const Program &main_prog = groups.empty() ? plain : folded;
+  const Program &main_prog = is_folded ? folded : plain;
+  s->n_wide = sel.n_wide;
   s->n_ops = (unsigned)main_prog.steps.size();
   s->depth = main_prog.depth; s->reg_levels = main_prog.reg_levels; s->matvecs = main_prog.matvecs;
   s->n_ops_plain = (unsigned)plain.steps.size();
   s->depth_plain = plain.depth; s->reg_levels_plain = plain.reg_levels; s->matvecs_plain = plain.matvecs;
-  s->lds_pos = main_prog.lds_pos; s->lds_pos_plain = plain.lds_pos;
-  s->n_steps = (unsigned)steps.size(); s->n_groups = (unsigned)groups.size(); s->clade_rows = clade_rows;
+  s->n_steps = (unsigned)sel.steps.size(); s->n_groups = (unsigned)sel.groups.size(); s->clade_rows = sel.clade_rows;
   s->prog = main_prog.steps;
-  // ---- the device block: [program | plain program | clade steps | clade groups | lengths] ----
-  {
-    auto padded = [](const Program &pr) {
-      std::vector<FusedOp> v = pr.steps;
-      // harmless tail entries: the kernel prefetches descriptors up to i + 3
-      for (int k = 0; k < 4; ++k) v.push_back(v.back());
-      return v;
-    };
-    const std::vector<FusedOp> pm = padded(main_prog), pp = groups.empty() ? std::vector<FusedOp>() : padded(plain);
-    auto up = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_prog = 0, o_plain = up(o_prog + sizeof(FusedOp) * pm.size()),
-                 o_steps = up(o_plain + sizeof(FusedOp) * pp.size()),
-                 o_groups = up(o_steps + sizeof(CladeStep) * steps.size()),
-                 o_brlen = up(o_groups + sizeof(CladeGroup) * groups.size()),
-                 o_tipmask = up(o_brlen + sizeof(double) * p->prob_matrices),
-                 total = up(o_tipmask + (k20 ? sizeof(uint32_t) * ((p->prob_matrices + 31) / 32) : 0));
-    std::vector<char> host(total, 0);
-    memcpy(host.data() + o_prog, pm.data(), sizeof(FusedOp) * pm.size());
-    if (!pp.empty()) memcpy(host.data() + o_plain, pp.data(), sizeof(FusedOp) * pp.size());
-    if (!steps.empty()) memcpy(host.data() + o_steps, steps.data(), sizeof(CladeStep) * steps.size());
-    if (!groups.empty()) memcpy(host.data() + o_groups, groups.data(), sizeof(CladeGroup) * groups.size());
-    memcpy(host.data() + o_brlen, brlen.data(), sizeof(double) * p->prob_matrices);
-    if (k20) {   // which branches end in a tip: only their tip tables are ever read (fused20_pmatrix_kernel)
-      uint32_t *mask = (uint32_t *)(host.data() + o_tipmask);
-      for (unsigned i = 0; i < n_ops; ++i) {
-        if (ops[i].child1_clv_index < p->tips) mask[ops[i].child1_matrix_index >> 5] |= 1u << (ops[i].child1_matrix_index & 31u);
-        if (ops[i].child2_clv_index < p->tips) mask[ops[i].child2_matrix_index >> 5] |= 1u << (ops[i].child2_matrix_index & 31u);
-      }
-    }
-    s->d_block = schedule_block_alloc(p, total, &s->block_bytes);
-    if (!s->d_block) {
-      set_error(100 + (int)hipErrorOutOfMemory, "rdamd_schedule_create: no device memory for a %zu-byte schedule", total);
-      rdamd_schedule_destroy_locked(s);
-      return nullptr;
-    }
-    TRY(hipMemcpy(s->d_block, host.data(), total, hipMemcpyHostToDevice));
-    s->d_prog = (FusedOp *)(s->d_block + o_prog);
-    s->d_prog_plain = groups.empty() ? s->d_prog : (FusedOp *)(s->d_block + o_plain);
-    s->d_steps = groups.empty() ? nullptr : (CladeStep *)(s->d_block + o_steps);
-    s->d_groups = groups.empty() ? nullptr : (CladeGroup *)(s->d_block + o_groups);
-    s->d_brlen = (double *)(s->d_block + o_brlen);
-    s->d_tipmask = k20 ? (uint32_t *)(s->d_block + o_tipmask) : nullptr;
+  const ScheduleBlock b = pack_schedule_block(main_prog, is_folded ? &plain : nullptr, sel.steps, sel.groups, v.brlen, k20,
+                                              p->tips, ops, n_ops);
+  s->d_block = schedule_block_alloc(p, b.total, &s->block_bytes);
+  if (!s->d_block) {
+    set_error(100 + (int)hipErrorOutOfMemory, "rdamd_schedule_create: no device memory for a %zu-byte schedule", b.total);
+    rdamd_schedule_destroy_locked(s);
+    return nullptr;
   }
+  TRY(hipMemcpy(s->d_block, b.host.data(), b.total, hipMemcpyHostToDevice));
 #undef TRY
+  s->d_prog = (FusedOp *)(s->d_block + b.o_prog);
+  s->d_prog_plain = is_folded ? (FusedOp *)(s->d_block + b.o_plain) : s->d_prog;
+  s->d_steps = is_folded ? (CladeStep *)(s->d_block + b.o_steps) : nullptr;
+  s->d_groups = is_folded ? (CladeGroup *)(s->d_block + b.o_groups) : nullptr;
+  s->d_brlen = (double *)(s->d_block + b.o_brlen);
+  s->d_tipmask = k20 ? (uint32_t *)(s->d_block + b.o_tipmask) : nullptr;
   return s;
 }
 
@@ -560,6 +448,80 @@ int rdamd_partition_set_site_repeats(rdamd_partition_t *p, unsigned int max_clas
   if (!p->clades) p->clades = new rdamd::CladeCache();
   p->clades->max_classes = max_classes;
   return RDAMD_SUCCESS;
+}
+
+// a partition's two batch slots (null: no such slot)
+static FusedWorkspace **workspace_slot(rdamd_partition_t *p, unsigned slot) {
+  return slot > 1 ? nullptr : (slot ? &p->fused1 : &p->fused);
+}
+
+// batches of one stream finish in submission order: everything up to `seq` is done
+static void mark_completed(rdamd_partition_t *p, uint64_t seq) {
+  uint64_t cur = p->batch_completed.load(std::memory_order_relaxed);
+  while (cur < seq && !p->batch_completed.compare_exchange_weak(cur, seq, std::memory_order_release)) {}
+}
+
+// The code arena a 4-state launch of a.table_rows reads, as it is NOW (launch_mu is held): compiling
+// a schedule may grow it (kernels_clade.hip, ensure_code_rows: new block, old one freed).
+// (rdamd_set_tip_states drops the 16-bit arena; a 64-row schedule WITHOUT pseudo-tips
+// survives that call -- its programs only address tip rows -- and finds the arena rebuilt here)
+static hipError_t point_at_code_arena(rdamd_partition_t *p, FusedArgs &a) {
+  const bool wide_codes = a.table_rows > 16;
+  if (wide_codes) {
+    const hipError_t e = ensure_wide_arena(p);
+    if (e != hipSuccess) return e;
+  }
+  a.tipcodes = wide_codes ? p->d_codes_wide : p->d_tipcodes16;
+  a.tipcodes_bytes = (unsigned)std::min<size_t>(wide_codes ? (size_t)p->wide_rows * p->tip_stride() * 2
+                                                           : (size_t)p->code_rows * p->tip_stride(), 0xffffffffu);
+  return hipSuccess;
+}
+
+// Where the root operation's inner children go (rdamd_evaluate_root_children): the partition's own
+// CLV / scaler buffers, and the workspace's rescale counts [2 children][site][rate]; all null for a
+// tip child, which leaves nothing behind.
+struct ExportTargets {
+  double *clv[2] = {nullptr, nullptr};
+  unsigned *cnt[2] = {nullptr, nullptr}, *scaler[2] = {nullptr, nullptr};
+};
+static int resolve_export_targets(rdamd_partition_t *p, FusedWorkspace *w, const rdamd_schedule_t *s0, ExportTargets &t) {
+  unsigned phys_clv[2] = {0, 0};   // (sparse partitions: the children's pool slots, taken now -- both
+  int phys_sc[2] = {-1, -1};       // before any address is formed: a pool that grows moves)
+  for (int k = 0; k < 2; ++k) {
+    if (s0->root_child_clv[k] < p->tips) continue;
+    if (s0->root_child_sc[k] < 0 || (unsigned)s0->root_child_sc[k] >= p->scale_buffers) {
+      set_error(50, "rdamd_evaluate_root_children: child %d of the root operation needs a scale buffer", k + 1);
+      return RDAMD_FAILURE;
+    }
+    RDAMD_HIP_TRY(clv_phys(p, s0->root_child_clv[k], &phys_clv[k]), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(scaler_phys(p, s0->root_child_sc[k], &phys_sc[k]), RDAMD_FAILURE);
+  }
+  const size_t R = p->rate_cats;
+  for (int k = 0; k < 2; ++k) {
+    if (s0->root_child_clv[k] < p->tips) continue;
+    if (!w->d_export_cnt)
+      RDAMD_HIP_TRY(hipMalloc((void **)&w->d_export_cnt, sizeof(unsigned) * 2 * (size_t)p->sites * R), RDAMD_FAILURE);
+    t.clv[k] = p->d_clv + (size_t)(phys_clv[k] - p->tips) * p->clv_doubles();
+    t.cnt[k] = w->d_export_cnt + (size_t)k * p->sites * R;
+    t.scaler[k] = p->d_scaler + (size_t)phys_sc[k] * p->sites;
+  }
+  return RDAMD_SUCCESS;
+}
+
+// The second pass over a slot's batch -- plain programs, tip-tip rescale test, the jobs whose
+// tt_unsafe flag went up (fused.hpp) -- queued behind it on the partition's stream.  launch_mu is
+// held.  Between submit and here another thread may have compiled a schedule that GREW the code
+// arena: the pointer the first pass was queued with may be gone.  The plain programs of this pass
+// address tip rows only, which every generation of the arena holds at the same offsets.
+static hipError_t queue_second_pass(rdamd_partition_t *p, FusedWorkspace *w) {
+  FusedWorkspace::Pending &pd = w->pend;
+  hipError_t e = point_at_code_arena(p, pd.a);
+  if (e != hipSuccess) return e;
+  p->prof_begin(3);
+  e = launch_fused_eval(pd.a, pd.n_jobs, pd.max_depth, w->blocks_x, pd.ns, pd.reg_levels, true, pd.d_out,
+                        pd.host_out ? w->h_out : nullptr, nullptr, p->stream);
+  p->prof_end();
+  return e;
 }
 
 // A batch in two halves.  batch_submit queues everything a batch needs -- inputs, P-matrices,
@@ -647,7 +609,7 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     hj[j].depth = hj[j].depth_plain = 0;   // patched below: every block uses the launch-wide depth
     hj[j].tt_unsafe = export_children ? 1u : 0u;   // (set again by the P-matrix / clade-table steps of this batch;
                                                    // the exporting variant is one with every rescale test)
-    hj[j].lds_pos = s->lds_pos | (s->lds_pos_plain << 16);
+    hj[j].lds_pos = 0;   // (no kernel reads the word any more, fused.hpp)
     max_depth[0] = std::max(max_depth[0], s->depth);
     max_depth[1] = std::max(max_depth[1], s->depth_plain);
     reg_levels[0] = std::max(reg_levels[0], s->reg_levels);
@@ -686,22 +648,15 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
   // the job's tables: one 16-row table per (matrix, rate), then its 64-row tables
   const size_t tiptab_job = k20 ? (size_t)p->prob_matrices * R * kFused20TabDoubles
                                 : (size_t)p->prob_matrices * R * 64 + (size_t)max_wide * R * 256;
-  if (tiptab_job * n_jobs > w->tiptab_doubles) {
-    RDAMD_HIP_TRY(sync_streams(p), RDAMD_FAILURE);
-    if (w->d_tiptab) (void)hipFree(w->d_tiptab);
-    w->d_tiptab = nullptr;
-    w->tiptab_doubles = tiptab_job * std::max(n_jobs, w->cap_jobs);
-    RDAMD_HIP_TRY(hipMalloc((void **)&w->d_tiptab, (w->tiptab_doubles + kTiptabPad) * sizeof(double)), RDAMD_FAILURE);
-  }
-  if (clade_scratch_job * n_jobs > w->clade_scratch_doubles) {
-    RDAMD_HIP_TRY(sync_streams(p), RDAMD_FAILURE);
-    if (w->d_clade_scratch) (void)hipFree(w->d_clade_scratch);
-    w->d_clade_scratch = nullptr;
-    w->clade_scratch_doubles = clade_scratch_job * std::max(n_jobs, w->cap_jobs);
-    RDAMD_HIP_TRY(hipMalloc((void **)&w->d_clade_scratch, w->clade_scratch_doubles * sizeof(double)), RDAMD_FAILURE);
-  }
+  const size_t most_jobs = std::max(n_jobs, w->cap_jobs);
+  if (tiptab_job * n_jobs > w->tiptab_doubles)
+    RDAMD_HIP_TRY(grow_buffer(p, w->d_tiptab, w->tiptab_doubles, tiptab_job * most_jobs,
+                              (tiptab_job * most_jobs + kTiptabPad) * sizeof(double)), RDAMD_FAILURE);
+  if (clade_scratch_job * n_jobs > w->clade_scratch_doubles)
+    RDAMD_HIP_TRY(grow_buffer(p, w->d_clade_scratch, w->clade_scratch_doubles, clade_scratch_job * most_jobs,
+                              clade_scratch_job * most_jobs * sizeof(double)), RDAMD_FAILURE);
   {   // the device block mirrors the staging block: one copy
-    const size_t in_bytes = (size_t)n_jobs * (sizeof(FusedJob) + sizeof(double) * (K * K + K + 2 * R));
+    const size_t in_bytes = input_block_bytes(p, n_jobs);
     memset(w->h_in + in_bytes, 0, 8);   // the any-unsafe word behind the block
     w->d_any_unsafe = (unsigned *)(w->d_in + in_bytes);
     p->stream_dirty = true;
@@ -729,14 +684,7 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     b.spill = nullptr; b.spill_levels = 0;
     if (const size_t spill = fused20_spill_bytes(R, w->blocks_x, n_jobs, max_depth[0])) {
       // stacks deeper than LDS holds at this R: their lower levels in global memory
-      if (spill > w->spill20_bytes) {
-        RDAMD_HIP_TRY(sync_streams(p), RDAMD_FAILURE);
-        if (w->d_spill20) (void)hipFree(w->d_spill20);
-        w->d_spill20 = nullptr;
-        w->spill20_bytes = 0;
-        RDAMD_HIP_TRY(hipMalloc((void **)&w->d_spill20, spill), RDAMD_FAILURE);
-        w->spill20_bytes = spill;
-      }
+      if (spill > w->spill20_bytes) RDAMD_HIP_TRY(grow_buffer(p, w->d_spill20, w->spill20_bytes, spill, spill), RDAMD_FAILURE);
       b.spill = w->d_spill20;
     }
     if (!pipelined) p->prof_begin(4);
@@ -747,39 +695,18 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
       RDAMD_HIP_TRY(hipEventRecord(w->ev_ready, pre), RDAMD_FAILURE);
       RDAMD_HIP_TRY(hipStreamWaitEvent(p->stream, w->ev_ready, 0), RDAMD_FAILURE);
     }
-    unsigned *export_scaler20[2] = {nullptr, nullptr};
-    b.export_clv[0] = b.export_clv[1] = nullptr;
-    b.export_cnt[0] = b.export_cnt[1] = nullptr;
+    ExportTargets t;
     if (export_children) {
-      // where the root operation's inner children go: the partition's own CLV / scaler buffers
       // (operand layout: rdamd_evaluate_root_children only takes partitions that keep it)
-      const rdamd_schedule_t *s0 = schedules[0];
       if (n_jobs != 1 || pipelined || !p->mfma_layout) {
         set_error(50, "rdamd_evaluate_root_children: one job on the partition's stream (20 states: up to 8 rate categories)");
         return RDAMD_FAILURE;
       }
-      unsigned phys_clv[2] = {0, 0};
-      int phys_sc[2] = {-1, -1};
-      for (int k = 0; k < 2; ++k) {
-        if (s0->root_child_clv[k] < p->tips) continue;   // a tip: nothing to leave behind
-        if (s0->root_child_sc[k] < 0 || (unsigned)s0->root_child_sc[k] >= p->scale_buffers) {
-          set_error(50, "rdamd_evaluate_root_children: child %d of the root operation needs a scale buffer", k + 1);
-          return RDAMD_FAILURE;
-        }
-        RDAMD_HIP_TRY(clv_phys(p, s0->root_child_clv[k], &phys_clv[k]), RDAMD_FAILURE);
-        RDAMD_HIP_TRY(scaler_phys(p, s0->root_child_sc[k], &phys_sc[k]), RDAMD_FAILURE);
-      }
-      for (int k = 0; k < 2; ++k) {
-        if (s0->root_child_clv[k] < p->tips) continue;
-        if (!w->d_export_cnt)
-          RDAMD_HIP_TRY(hipMalloc((void **)&w->d_export_cnt, sizeof(unsigned) * 2 * (size_t)p->sites * R), RDAMD_FAILURE);
-        b.export_clv[k] = p->d_clv + (size_t)(phys_clv[k] - p->tips) * p->clv_doubles();
-        b.export_cnt[k] = w->d_export_cnt + (size_t)k * p->sites * R;
-        export_scaler20[k] = p->d_scaler + (size_t)phys_sc[k] * p->sites;
-      }
+      if (resolve_export_targets(p, w, schedules[0], t) != RDAMD_SUCCESS) return RDAMD_FAILURE;
     }
+    for (int k = 0; k < 2; ++k) { b.export_clv[k] = t.clv[k]; b.export_cnt[k] = t.cnt[k]; }
     p->prof_begin(3);
-    e = export_children ? launch_fused20_export(b, max_depth[0], export_scaler20, d_out, p->stream)
+    e = export_children ? launch_fused20_export(b, max_depth[0], t.scaler, d_out, p->stream)
                         : launch_fused20_eval(b, n_jobs, max_depth[0], d_out, p->stream);
     p->prof_end();
     RDAMD_HIP_TRY(e, RDAMD_FAILURE);
@@ -791,14 +718,10 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     }
   } else {
     FusedArgs a = {};
-    const bool wide_codes = table_rows > 16;
-    // (rdamd_set_tip_states drops the 16-bit arena; a 64-row schedule WITHOUT pseudo-tips
-    // survives that call -- its programs only address tip rows -- and finds the arena rebuilt here)
-    if (wide_codes) RDAMD_HIP_TRY(ensure_wide_arena(p), RDAMD_FAILURE);
-    a.jobs = w->d_jobs; a.tipcodes = wide_codes ? p->d_codes_wide : p->d_tipcodes16;
-    a.pattern_weights = p->d_pattern_weights;
     a.table_rows = table_rows;
-    a.rates_across_waves = 0;   // (set below, once the size of the code arena is known)
+    RDAMD_HIP_TRY(point_at_code_arena(p, a), RDAMD_FAILURE);
+    a.jobs = w->d_jobs;
+    a.pattern_weights = p->d_pattern_weights;
 
     a.tiptab_job_stride = tiptab_job;
     a.pmat = w->d_pmat; a.tiptab = w->d_tiptab + kTiptabPad; a.freqs = w->d_freqs; a.rate_weights = w->d_rw;
@@ -806,8 +729,6 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     a.any_unsafe = w->d_any_unsafe;
     a.pmat_job_stride = (size_t)p->prob_matrices * R * 16;
     a.sites = p->sites; a.rate_cats = R;
-    a.tipcodes_bytes = (unsigned)std::min<size_t>(wide_codes ? (size_t)p->wide_rows * p->tip_stride() * 2
-                                                             : (size_t)p->code_rows * p->tip_stride(), 0xffffffffu);
     // One wave per rate category (kernels_fused.hip, RW) where re-reading the code arena once
     // per rate pass is what hurts: when it is far beyond every cache level.  Measured (one
     // box): c4 (850 MB of codes) 200.6 -> 181.1 ms per launch; c5 (340 MB) 77.9 -> 78.2; c2
@@ -837,33 +758,14 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     // kernels are one-wave workgroups, so such a launch does without one wave per rate category.
     a.speculate = p->rescale_speculation < 0 ? p->tips <= kSpeculateTips : p->rescale_speculation > 0;
     if (a.speculate) a.rates_across_waves = 0;
-    unsigned *export_scaler[2] = {nullptr, nullptr};
+    ExportTargets t;
     if (export_children) {
-      // where the root operation's inner children go: the partition's own CLV / scaler buffers
-      const rdamd_schedule_t *s0 = schedules[0];
       if (n_jobs != 1 || pipelined || table_rows != 16 || p->mfma_layout) {
         set_error(50, "rdamd_evaluate_root_children: one job of a 16-row schedule on the partition's stream");
         return RDAMD_FAILURE;
       }
-      unsigned phys_clv[2] = {0, 0};   // (sparse partitions: the children's pool slots, taken now -- both
-      int phys_sc[2] = {-1, -1};       // before any address is formed: a pool that grows moves)
-      for (int k = 0; k < 2; ++k) {
-        if (s0->root_child_clv[k] < p->tips) continue;   // a tip: nothing to leave behind
-        if (s0->root_child_sc[k] < 0 || (unsigned)s0->root_child_sc[k] >= p->scale_buffers) {
-          set_error(50, "rdamd_evaluate_root_children: child %d of the root operation needs a scale buffer", k + 1);
-          return RDAMD_FAILURE;
-        }
-        RDAMD_HIP_TRY(clv_phys(p, s0->root_child_clv[k], &phys_clv[k]), RDAMD_FAILURE);
-        RDAMD_HIP_TRY(scaler_phys(p, s0->root_child_sc[k], &phys_sc[k]), RDAMD_FAILURE);
-      }
-      for (int k = 0; k < 2; ++k) {
-        if (s0->root_child_clv[k] < p->tips) continue;
-        if (!w->d_export_cnt)
-          RDAMD_HIP_TRY(hipMalloc((void **)&w->d_export_cnt, sizeof(unsigned) * 2 * (size_t)p->sites * R), RDAMD_FAILURE);
-        a.export_clv[k] = p->d_clv + (size_t)(phys_clv[k] - p->tips) * p->clv_doubles();
-        a.export_cnt[k] = w->d_export_cnt + (size_t)k * p->sites * R;
-        export_scaler[k] = p->d_scaler + (size_t)phys_sc[k] * p->sites;
-      }
+      if (resolve_export_targets(p, w, schedules[0], t) != RDAMD_SUCCESS) return RDAMD_FAILURE;
+      for (int k = 0; k < 2; ++k) { a.export_clv[k] = t.clv[k]; a.export_cnt[k] = t.cnt[k]; }
       a.rates_across_waves = 0;
       a.job_major = 0;
       a.speculate = 0;
@@ -893,7 +795,7 @@ static int batch_submit_impl(rdamd_partition_t *p, FusedWorkspace *&slot, bool p
     unsigned *h_flag = (unsigned *)(w->h_out + w->cap_jobs);
     if (export_children) {
       *h_flag = 0;   // (no second pass behind this one: batch_wait reads the word)
-      e = launch_fused_export(a, max_depth[1], w->blocks_x, reg_levels[1], export_scaler, d_out,
+      e = launch_fused_export(a, max_depth[1], w->blocks_x, reg_levels[1], t.scaler, d_out,
                               host_out ? w->h_out : nullptr, p->stream);
     } else
     e = launch_fused_eval(a, n_jobs, max_depth, w->blocks_x, ns, reg_levels, false, d_out,
@@ -925,8 +827,7 @@ static void drain_after_failure(rdamd_partition_t *p, uint64_t at_least) {
     upto = std::max(p->batch_submitted, at_least);
   }
   (void)sync_streams(p);
-  uint64_t cur = p->batch_completed.load(std::memory_order_relaxed);
-  while (cur < upto && !p->batch_completed.compare_exchange_weak(cur, upto, std::memory_order_release)) {}
+  mark_completed(p, upto);
 }
 
 // A submit that fails half-way may have queued copies and kernels on the slot's workspace: nothing
@@ -956,10 +857,6 @@ static int batch_wait(rdamd_partition_t *p, FusedWorkspace *w, bool pipelined, d
     if (lnl_host && pd.host_out) std::fill(lnl_host, lnl_host + pd.n_jobs, 0.0);
     return RDAMD_SUCCESS;
   }
-  auto completed = [&] {   // (batches of one stream finish in submission order)
-    uint64_t cur = p->batch_completed.load(std::memory_order_relaxed);
-    while (cur < pd.seq && !p->batch_completed.compare_exchange_weak(cur, pd.seq, std::memory_order_release)) {}
-  };
   // A failed wait or second pass must not leave the sequence number behind (parked schedule
   // blocks would wait for it for ever): drain the partition's streams, then everything queued
   // so far HAS finished, one way or the other.
@@ -973,24 +870,10 @@ static int batch_wait(rdamd_partition_t *p, FusedWorkspace *w, bool pipelined, d
   const unsigned *h_flag = (const unsigned *)(w->h_out + w->cap_jobs);
   if (!pd.k20 && *h_flag) {
     p->second_passes.fetch_add(1, std::memory_order_relaxed);
-    hipError_t e = hipSuccess;
+    hipError_t e;
     {
       std::lock_guard<std::mutex> guard(p->launch_mu);
-      // Between submit and here another thread may have compiled a schedule that GREW the code
-      // arena (kernels_clade.hip, ensure_code_rows: new block, old one freed): the pointer the
-      // first pass was queued with may be gone.  The plain programs of this pass address tip rows
-      // only, which every generation of the arena holds at the same offsets.
-      const bool wide_codes = pd.a.table_rows > 16;
-      if (wide_codes) e = ensure_wide_arena(p);
-      pd.a.tipcodes = wide_codes ? p->d_codes_wide : p->d_tipcodes16;
-      pd.a.tipcodes_bytes = (unsigned)std::min<size_t>(wide_codes ? (size_t)p->wide_rows * p->tip_stride() * 2
-                                                                  : (size_t)p->code_rows * p->tip_stride(), 0xffffffffu);
-      if (e == hipSuccess) {
-        p->prof_begin(3);
-        e = launch_fused_eval(pd.a, pd.n_jobs, pd.max_depth, w->blocks_x, pd.ns, pd.reg_levels, true, pd.d_out,
-                              pd.host_out ? w->h_out : nullptr, nullptr, p->stream);
-        p->prof_end();
-      }
+      e = queue_second_pass(p, w);
       if (e == hipSuccess && pipelined) e = hipEventRecord(w->ev_done, p->stream);
     }
     WAIT_TRY(e);
@@ -998,7 +881,7 @@ static int batch_wait(rdamd_partition_t *p, FusedWorkspace *w, bool pipelined, d
     else WAIT_TRY(hipStreamSynchronize(p->stream));
   }
 #undef WAIT_TRY
-  completed();
+  mark_completed(p, pd.seq);
   if (lnl_host && pd.host_out) memcpy(lnl_host, w->h_out, sizeof(double) * pd.n_jobs);
   return RDAMD_SUCCESS;
 }
@@ -1063,11 +946,12 @@ int rdamd_evaluate_batch_submit(rdamd_partition_t *p, unsigned int slot, unsigne
                                 const double *subst, const double *freqs,
                                 const double *rates, const double *rate_weights) {
   clear_error();
-  if (slot > 1) {
+  FusedWorkspace **ws = workspace_slot(p, slot);
+  if (!ws) {
     set_error(49, "rdamd_evaluate_batch_submit: slot %u (a partition has slots 0 and 1)", slot);
     return RDAMD_FAILURE;
   }
-  return batch_submit(p, slot ? p->fused1 : p->fused, true, n_jobs, schedules, subst, freqs, rates, rate_weights, true, nullptr);
+  return batch_submit(p, *ws, true, n_jobs, schedules, subst, freqs, rates, rate_weights, true, nullptr);
 }
 
 // ---- the stream-ordered form (include/root_digger_amd.h) ------------------------------------
@@ -1076,17 +960,19 @@ int rdamd_evaluate_batch_submit_device(rdamd_partition_t *p, unsigned int slot, 
                                        const double *subst, const double *freqs,
                                        const double *rates, const double *rate_weights, void *d_lnl_out) {
   clear_error();
-  if (slot > 1 || !d_lnl_out) {
+  FusedWorkspace **ws = workspace_slot(p, slot);
+  if (!ws || !d_lnl_out) {
     set_error(49, "rdamd_evaluate_batch_submit_device: slot %u (0 or 1), device destination %p", slot, d_lnl_out);
     return RDAMD_FAILURE;
   }
-  return batch_submit(p, slot ? p->fused1 : p->fused, true, n_jobs, schedules, subst, freqs, rates, rate_weights, false,
+  return batch_submit(p, *ws, true, n_jobs, schedules, subst, freqs, rates, rate_weights, false,
                       nullptr, false, (double *)d_lnl_out);
 }
 
 int rdamd_evaluate_batch_redo_device(rdamd_partition_t *p, unsigned int slot, void *d_lnl_out) {
   clear_error();
-  FusedWorkspace *w = slot > 1 ? nullptr : (slot ? p->fused1 : p->fused);
+  FusedWorkspace **ws = workspace_slot(p, slot);
+  FusedWorkspace *w = ws ? *ws : nullptr;
   if (!w || !w->pend.active || !w->pend.mirror || !d_lnl_out) {
     set_error(49, "rdamd_evaluate_batch_redo_device: no device batch on slot %u", slot);
     return RDAMD_FAILURE;
@@ -1100,18 +986,9 @@ int rdamd_evaluate_batch_redo_device(rdamd_partition_t *p, unsigned int slot, vo
   RDAMD_HIP_TRY(hipEventSynchronize(w->ev_done), RDAMD_FAILURE);
   const unsigned *h_flag = (const unsigned *)(w->h_out + w->cap_jobs);
   std::lock_guard<std::mutex> guard(p->launch_mu);
-  if (!pd.k20 && *h_flag) {   // THIS rank's jobs need the pass (batch_wait has the notes)
+  if (!pd.k20 && *h_flag) {   // THIS rank's jobs need the pass (a device batch has no host destination)
     p->second_passes.fetch_add(1, std::memory_order_relaxed);
-    const bool wide_codes = pd.a.table_rows > 16;
-    if (wide_codes) RDAMD_HIP_TRY(ensure_wide_arena(p), RDAMD_FAILURE);
-    pd.a.tipcodes = wide_codes ? p->d_codes_wide : p->d_tipcodes16;
-    pd.a.tipcodes_bytes = (unsigned)std::min<size_t>(wide_codes ? (size_t)p->wide_rows * p->tip_stride() * 2
-                                                                : (size_t)p->code_rows * p->tip_stride(), 0xffffffffu);
-    p->prof_begin(3);
-    hipError_t e = launch_fused_eval(pd.a, pd.n_jobs, pd.max_depth, w->blocks_x, pd.ns, pd.reg_levels, true, pd.d_out,
-                                     nullptr, nullptr, p->stream);
-    p->prof_end();
-    RDAMD_HIP_TRY(e, RDAMD_FAILURE);
+    RDAMD_HIP_TRY(queue_second_pass(p, w), RDAMD_FAILURE);
   }
   // this rank's results again (a collective has summed over the first copy in place), flag down
   RDAMD_HIP_TRY(hipMemcpyAsync(d_lnl_out, pd.d_out, sizeof(double) * pd.n_jobs, hipMemcpyDeviceToDevice, p->stream),
@@ -1123,7 +1000,8 @@ int rdamd_evaluate_batch_redo_device(rdamd_partition_t *p, unsigned int slot, vo
 
 int rdamd_evaluate_batch_finish_device(rdamd_partition_t *p, unsigned int slot) {
   clear_error();
-  FusedWorkspace *w = slot > 1 ? nullptr : (slot ? p->fused1 : p->fused);
+  FusedWorkspace **ws = workspace_slot(p, slot);
+  FusedWorkspace *w = ws ? *ws : nullptr;
   if (!w || !w->pend.active || !w->pend.mirror) {
     set_error(49, "rdamd_evaluate_batch_finish_device: no device batch on slot %u", slot);
     return RDAMD_FAILURE;
@@ -1136,18 +1014,18 @@ int rdamd_evaluate_batch_finish_device(rdamd_partition_t *p, unsigned int slot) 
     drain_after_failure(p, pd.seq);
     return RDAMD_FAILURE;
   }
-  uint64_t cur = p->batch_completed.load(std::memory_order_relaxed);
-  while (cur < pd.seq && !p->batch_completed.compare_exchange_weak(cur, pd.seq, std::memory_order_release)) {}
+  mark_completed(p, pd.seq);
   return RDAMD_SUCCESS;
 }
 
 int rdamd_evaluate_batch_wait(rdamd_partition_t *p, unsigned int slot, double *lnl_out) {
   clear_error();
-  if (slot > 1) {
+  FusedWorkspace **ws = workspace_slot(p, slot);
+  if (!ws) {
     set_error(49, "rdamd_evaluate_batch_wait: slot %u (a partition has slots 0 and 1)", slot);
     return RDAMD_FAILURE;
   }
-  return batch_wait(p, slot ? p->fused1 : p->fused, true, lnl_out);
+  return batch_wait(p, *ws, true, lnl_out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The traversal compiler of the fused evaluators (pure host code: no HIP call, no device
 // memory -- tests/cpp/host_logic_check.cpp runs it on the CPU and replays its programs
-// symbolically).  rdamd_schedule_create (evaluate.hip) is its only caller in the library.
+// symbolically).  compile_program (schedule_plan.hpp), the recipe rdamd_schedule_create runs, is
+// its only caller in the library.
 #pragma once
 
 #include <algorithm>

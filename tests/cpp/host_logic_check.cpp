@@ -3,18 +3,25 @@
 //     which clades the fused evaluator folds into look-up tables -- against a brute-force count;
 //   * k20_split (csrc/k20_split.hpp): cutting a post-order operation list into independent
 //     subtree pieces -- against the properties the 20-state traversal kernel relies on.
-//   * the traversal compiler (csrc/traversal_compiler.hpp): its programs -- step order, which
-//     stack level sits in the register slot(s), which in-memory entry in the LDS slot -- replayed
-//     symbolically: the running value at the end must be the root's CLV expression, every pop
-//     must meet the sibling that was parked for it, for 4-state (one / two register levels,
-//     pseudo-tips) and 20-state (parking as a step of its own) programs.
+//   * the traversal compiler (csrc/traversal_compiler.hpp) as the schedule planner sets it up
+//     (csrc/schedule_plan.hpp, compile_program: the recipe rdamd_schedule_create hands the kernels):
+//     its programs -- step order, which stack level sits in the register slot(s), which in-memory
+//     entry in the LDS slot -- replayed symbolically: the running value at the end must be the
+//     root's CLV expression, every pop must meet the sibling that was parked for it, for 4-state
+//     (one / two register levels, pseudo-tips) and 20-state (parking as a step of its own) programs.
+//   * the rest of the schedule planner: which operation lists it refuses and where, the producer /
+//     consumer maps, which clades it folds into pseudo-tips (whole small subtrees, post-order,
+//     64-row slots), the folded programs replayed, and the layout of the schedule's device block.
 //   * the CLV traversal planner (csrc/clv_plan.hpp): every plan replayed symbolically -- each child
 //     source names a value that is really there (tip, the registers of the operation(s) in front,
 //     an LDS parking slot nobody has overwritten), segments, padding, slot counts and the 20-state
 //     look-ahead are what the traversal kernels rely on.
 // prints "host logic OK <cases>" on success.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <limits>
 #include <map>
 #include <random>
 #include <set>
@@ -23,7 +30,7 @@
 #include "clade_classes.hpp"
 #include "clv_plan.hpp"
 #include "k20_split.hpp"
-#include "traversal_compiler.hpp"
+#include "schedule_plan.hpp"
 
 static int fail(const char *what, int a = 0, int b = 0) {
   std::printf("FAILED: %s (%d, %d)\n", what, a, b);
@@ -71,6 +78,27 @@ static std::vector<rdamd_operation_t> random_postorder(unsigned n, std::mt19937 
     clv_of[(size_t)f.node] = (int)next_clv++;
     ops.push_back(o);
     st.pop_back();
+  }
+  return ops;
+}
+
+// perfectly balanced tree with n = 2^k tips: pair up level by level
+static std::vector<rdamd_operation_t> balanced_postorder(unsigned n) {
+  std::vector<rdamd_operation_t> ops;
+  std::vector<unsigned> level(n);
+  for (unsigned i = 0; i < n; ++i) level[i] = i;
+  unsigned next_clv = n, next_mat = 0;
+  while (level.size() > 1) {
+    std::vector<unsigned> up;
+    for (size_t i = 0; i + 1 < level.size(); i += 2) {
+      rdamd_operation_t o;
+      o.parent_clv_index = next_clv; o.parent_scaler_index = -1;
+      o.child1_clv_index = level[i]; o.child1_matrix_index = next_mat++; o.child1_scaler_index = -1;
+      o.child2_clv_index = level[i + 1]; o.child2_matrix_index = next_mat++; o.child2_scaler_index = -1;
+      ops.push_back(o);
+      up.push_back(next_clv++);
+    }
+    level.swap(up);
   }
   return ops;
 }
@@ -168,59 +196,49 @@ static int check_compiler(std::mt19937 &rng, int &cases) {
     // shapes: random joins (deep, unbalanced), balanced (deepest stacks), caterpillar (depth 1)
     unsigned n = 3 + rng() % (rep % 10 == 0 ? 1500 : 300);
     std::vector<rdamd_operation_t> ops = random_postorder(n, rng);
-    if (rep % 5 == 1) {   // perfectly balanced: pair up level by level
+    if (rep % 5 == 1) {
       n = 1u << (2 + rng() % 9);
-      ops.clear();
-      std::vector<unsigned> level(n);
-      for (unsigned i = 0; i < n; ++i) level[i] = i;
-      unsigned next_clv = n, next_mat = 0;
-      while (level.size() > 1) {
-        std::vector<unsigned> up;
-        for (size_t i = 0; i + 1 < level.size(); i += 2) {
-          rdamd_operation_t o;
-          o.parent_clv_index = next_clv; o.parent_scaler_index = -1;
-          o.child1_clv_index = level[i]; o.child1_matrix_index = next_mat++; o.child1_scaler_index = -1;
-          o.child2_clv_index = level[i + 1]; o.child2_matrix_index = next_mat++; o.child2_scaler_index = -1;
-          ops.push_back(o);
-          up.push_back(next_clv++);
-        }
-        level.swap(up);
-      }
+      ops = balanced_postorder(n);
     }
-    rdamd::Compiler c;
-    c.ops = ops.data(); c.n_ops = (unsigned)ops.size(); c.tips = n; c.sites = 1000;
-    c.tip_stride = k20 ? 1000 : 2000; c.rate_cats = 4;
-    c.unit = c.rate_cats * (k20 ? 3200u : 128u);
-    c.split_park = k20;
-    c.wide_base = 8u * (2 * n) * c.rate_cats * 16u;
-    for (unsigned i = 0; i < c.n_ops; ++i) c.producer[ops[i].parent_clv_index] = i;
+    // the library's recipe (schedule_plan.hpp), for the shapes rdamd_schedule_create compiles: 20 states,
+    // 4 states with 64-row table slots (kernels with private-segment levels) and with 16-row ones
+    rdamd::ScheduleShape sh;
+    sh.tips = n; sh.sites = 1000; sh.tip_stride = 1000; sh.rate_cats = 4; sh.prob_matrices = 2 * n;
+    sh.k20 = k20; sh.wide_mode = !k20 && rep % 4 < 2;
+    rdamd::ClvMap pseudo_row, pseudo_wide;
     if (!k20 && rep % 2 == 0) {   // some inner nodes become pseudo-tips (their subtrees leave the program)
       unsigned rows = n, wide = 0;
-      for (unsigned i = 0; i + 1 < c.n_ops; ++i)
+      for (unsigned i = 0; i + 1 < ops.size(); ++i)
         if (rng() % 6 == 0) {
-          c.pseudo_row[ops[i].parent_clv_index] = rows++;
-          if (rng() % 2) c.pseudo_wide[ops[i].parent_clv_index] = wide++;
+          pseudo_row[ops[i].parent_clv_index] = rows++;
+          if (rng() % 2) pseudo_wide[ops[i].parent_clv_index] = wide++;
         }
     }
-    // the steps that compute the root operation's inner children carry 0x8000 / 0x10000 (4 states:
-    // the exporting evaluator, rdamd_evaluate_root_children)
-    uint64_t marked[2] = {0, 0};
-    if (!k20) {
-      const rdamd_operation_t &root = ops.back();
-      const unsigned kid[2] = {root.child1_clv_index, root.child2_clv_index};
-      for (int k = 0; k < 2; ++k)
-        if (kid[k] >= n) c.mark_clv[k] = kid[k];
-    }
-    c.need.assign(c.n_ops, 0);
-    c.compute_need(c.n_ops - 1);
-    c.emit(c.n_ops - 1, false, 0);
-    const unsigned first_pass_depth = c.max_depth;
+    rdamd::Program prog;
+    rdamd::ProgramTrace trace;
+    const unsigned lost = rdamd::compile_program(sh, ops, pseudo_row, pseudo_wide, prog, &trace);
+    const rdamd::Compiler &c = trace.c;
+    const unsigned lds_pos = trace.runner_up;
+    const unsigned beyond = k20 ? 0u : (sh.wide_mode ? 1u + rdamd::kFusedSpillLevels : 3u);
+    if (c.place_parks != (!k20 && sh.wide_mode) || c.dma_offsets != c.place_parks) return fail("the recipe's 64-row switches");
+    // what the first pass finds, from the list alone: the stack depth is the root's Sethi-Ullman
+    // number, and every node with two inner children parks once
+    const unsigned first_pass_depth = c.need[c.n_ops - 1];
     unsigned parks = 0;
-    for (unsigned l = 0; l < 16; ++l) parks += c.parks_at[l];
-    // (the two thresholds rdamd_schedule_create uses: kernels with / without private-segment levels)
-    const unsigned beyond = k20 ? 0u : (rep % 4 < 2 ? 1u + rdamd::kFusedSpillLevels : 3u);
-    c.place_parks = !k20 && rep % 4 < 2;   // (what rdamd_schedule_create asks for with 64-row table slots)
-    const unsigned lds_pos = c.place_levels(beyond, rdamd::kFusedSpillLevels - 1u);
+    {
+      std::vector<unsigned> todo{c.n_ops - 1};
+      while (!todo.empty()) {
+        const rdamd_operation_t &o = ops[todo.back()];
+        todo.pop_back();
+        unsigned inner = 0;
+        for (unsigned ch : {o.child1_clv_index, o.child2_clv_index})
+          if (c.is_inner(ch)) { todo.push_back(c.producer.at(ch)); ++inner; }
+        parks += inner == 2;
+      }
+    }
+    // the steps that compute the root operation's inner children carry 0x8000 / 0x10000 (the
+    // exporting evaluator, rdamd_evaluate_root_children)
+    uint64_t marked[2] = {0, 0};
     const bool placed = !c.park_class.empty();
     if (c.max_depth != first_pass_depth) return fail("the second pass changed the stack depth");
     unsigned parks2 = 0, busiest = 0;
@@ -255,6 +273,14 @@ static int check_compiler(std::mt19937 &rng, int &cases) {
     size_t real = 0;
     for (const rdamd::FusedOp &f : c.out) real += (f.flags & 3u) != rdamd::kFusedPark || !k20;
     if (c.pseudo_row.empty() && real != c.n_ops) return fail("operations lost", (int)real, (int)c.n_ops);
+    if (lost != c.n_ops - real) return fail("the recipe's count of unreachable operations", (int)lost, (int)(c.n_ops - real));
+    if (!lost) {   // the program as the schedule keeps it
+      if (prog.steps.size() != c.out.size() || memcmp(prog.steps.data(), c.out.data(), sizeof(rdamd::FusedOp) * c.out.size()))
+        return fail("Program::steps are not the compiler's");
+      if (prog.reg_levels != c.reg_levels || prog.matvecs != c.matvecs) return fail("Program: register levels / matvecs");
+      // in-memory levels the launch allocates: every entry of the replayed stack (+ the LDS slot of placed parks)
+      if (prog.depth != (placed ? 1u + mem_depth : std::max(1u, mem_depth))) return fail("Program::depth", (int)prog.depth, (int)mem_depth);
+    }
     ++cases;
   }
   std::fprintf(stderr, "parks placed one by one: %lu of %lu in the two slots (the two busiest levels: %lu)\n", placed_in_slots,
@@ -438,6 +464,314 @@ static int check_planner(std::mt19937 &rng, int &cases) {
   return 0;
 }
 
+// ---- the schedule planner (csrc/schedule_plan.hpp) ------------------------------------------
+// a tree of the existing generators: random joins, every fifth perfectly balanced
+static std::vector<rdamd_operation_t> plan_tree(std::mt19937 &rng, int rep, unsigned most, unsigned &n) {
+  n = 4 + rng() % (most - 3);
+  if (rep % 5 != 1) return random_postorder(n, rng);
+  n = 4;
+  while (2 * n <= most && rng() % 3) n *= 2;
+  return balanced_postorder(n);
+}
+
+// matrix m of the list's 2n - 2 gets length m + 0.5, in shuffled order
+static void branch_list(std::mt19937 &rng, unsigned n_mat, std::vector<unsigned> &idx, std::vector<double> &len) {
+  idx.resize(n_mat);
+  for (unsigned m = 0; m < n_mat; ++m) idx[m] = m;
+  std::shuffle(idx.begin(), idx.end(), rng);
+  len.resize(n_mat);
+  for (unsigned m = 0; m < n_mat; ++m) len[m] = idx[m] + 0.5;
+}
+
+static int check_validation(std::mt19937 &rng, int &cases) {
+  using rdamd::ScheduleCheck;
+  for (int rep = 0; rep < 150; ++rep) {
+    unsigned n;
+    const std::vector<rdamd_operation_t> ops = plan_tree(rng, rep, 300, n);
+    const unsigned count = (unsigned)ops.size(), n_mat = 2 * n - 2, bufs = n + 3, mats = n_mat + 3;
+    std::vector<unsigned> idx;
+    std::vector<double> len;
+    branch_list(rng, n_mat, idx, len);
+    auto check = [&](const std::vector<rdamd_operation_t> &list) {
+      return rdamd::validate_schedule(n, bufs, mats, list.data(), (unsigned)list.size(), idx.data(), len.data(), n_mat);
+    };
+    {   // the valid list passes; its maps against a direct scan
+      const ScheduleCheck v = check(ops);
+      if (v.kind != ScheduleCheck::kOk || v.matrix_shared) return fail("validation: a valid list was refused", (int)v.kind, (int)v.at);
+      if (v.producer.size() != count || v.consumer.size() != count) return fail("validation: map sizes");
+      for (unsigned i = 0; i < count; ++i) {
+        if (!v.producer.count(ops[i].parent_clv_index) || v.producer.at(ops[i].parent_clv_index) != i) return fail("validation: producer", (int)i);
+        int taker = -1;
+        for (unsigned j = 0; j < count; ++j)
+          if (ops[j].child1_clv_index == ops[i].parent_clv_index || ops[j].child2_clv_index == ops[i].parent_clv_index) taker = (int)j;
+        if (v.consumer[i] != taker || (taker < 0) != (i + 1 == count)) return fail("validation: consumer", (int)i, taker);
+      }
+      if (v.brlen.size() != mats) return fail("validation: branch lengths (size)");
+      for (unsigned m = 0; m < mats; ++m)
+        if (v.brlen[m] != (m < n_mat ? m + 0.5 : 0.0)) return fail("validation: branch length", (int)m);
+      ++cases;
+    }
+    // mutants: each refused at the first operation that, read in order, no longer fits what came before
+    auto refused_at = [&](const std::vector<rdamd_operation_t> &list, unsigned want, const char *what) {
+      const ScheduleCheck v = check(list);
+      if (v.kind != ScheduleCheck::kOperation || v.at != want) return fail(what, (int)v.at, (int)want);
+      ++cases;
+      return 0;
+    };
+    std::vector<unsigned> inner_child;   // operations with an inner child 1 or 2
+    for (unsigned i = 0; i < count; ++i)
+      if (ops[i].child1_clv_index >= n || ops[i].child2_clv_index >= n) inner_child.push_back(i);
+    if (!inner_child.empty()) {
+      const unsigned i = inner_child[rng() % inner_child.size()];
+      const unsigned c = ops[i].child1_clv_index >= n ? ops[i].child1_clv_index : ops[i].child2_clv_index;
+      const unsigned made = c - n;   // (both generators: operation k writes CLV n + k)
+      {   // a child used by two operations: whichever comes second is refused
+        unsigned k = made + 1 + rng() % (count - made - 1);
+        if (k == i) k = k + 1 < count ? k + 1 : made + 1;
+        if (k != i) {
+          std::vector<rdamd_operation_t> bad = ops;
+          bad[k].child1_clv_index = c;
+          if (refused_at(bad, std::max(k, i), "validation: a child used twice")) return 1;
+        }
+      }
+      {   // a child in front of its producer: the two operations change places
+        std::vector<rdamd_operation_t> bad = ops;
+        std::swap(bad[made], bad[i]);
+        if (refused_at(bad, made, "validation: a child that is not yet computed")) return 1;
+      }
+    }
+    if (count >= 2) {   // a parent written twice
+      const unsigned k = 1 + rng() % (count - 1), j = rng() % k;
+      std::vector<rdamd_operation_t> bad = ops;
+      bad[k].parent_clv_index = bad[j].parent_clv_index;
+      if (refused_at(bad, k, "validation: a parent written twice")) return 1;
+    }
+    {   // an index out of range
+      const unsigned k = rng() % count;
+      std::vector<rdamd_operation_t> bad = ops;
+      switch (rep % 4) {
+        case 0: bad[k].child2_clv_index = n + bufs; break;
+        case 1: bad[k].child1_matrix_index = mats; break;
+        case 2: bad[k].parent_clv_index = rng() % n; break;   // (a tip is no destination)
+        default: bad[k].parent_clv_index = n + bufs + rng() % 5; break;
+      }
+      if (refused_at(bad, k, "validation: an index out of range")) return 1;
+    }
+    {   // an empty list
+      if (rdamd::validate_schedule(n, bufs, mats, ops.data(), 0, idx.data(), len.data(), n_mat).kind != ScheduleCheck::kEmpty)
+        return fail("validation: an empty list");
+      ++cases;
+    }
+    {   // the branch list: a length that is negative, NaN or infinite, a matrix the partition does not have
+      const unsigned m = rng() % n_mat;
+      std::vector<unsigned> bad_idx = idx;
+      std::vector<double> bad_len = len;
+      const double inf = std::numeric_limits<double>::infinity();
+      switch (rep % 5) {
+        case 0: bad_len[m] = -1e-300; break;
+        case 1: bad_len[m] = std::numeric_limits<double>::quiet_NaN(); break;
+        case 2: bad_len[m] = inf; break;
+        case 3: bad_len[m] = -inf; break;
+        default: bad_idx[m] = mats + rng() % 3; break;
+      }
+      const ScheduleCheck v = rdamd::validate_schedule(n, bufs, mats, ops.data(), count, bad_idx.data(), bad_len.data(), n_mat);
+      if (v.kind != ScheduleCheck::kBranch || v.at != m) return fail("validation: a bad branch", (int)v.at, (int)m);
+      ++cases;
+    }
+    {   // a detached subtree: a valid post-order list, but the root operation does not reach all of it
+      const unsigned extra = 1 + rng() % 3;   // (the partition has buffers and matrices for three more operations)
+      std::vector<rdamd_operation_t> more(ops.begin(), ops.end() - 1);
+      for (unsigned e = 0; e < extra; ++e) {   // a chain over tips 0, 1, 2 .. in front of the root operation
+        rdamd_operation_t o = ops[0];
+        o.parent_clv_index = n + count + e; o.parent_scaler_index = -1;
+        o.child1_clv_index = e ? n + count + e - 1 : 0; o.child2_clv_index = 1 + e;
+        o.child1_scaler_index = o.child2_scaler_index = -1;
+        o.child1_matrix_index = o.child2_matrix_index = n_mat + e;   // (a shared index: still a valid list)
+        more.push_back(o);
+      }
+      more.push_back(ops.back());
+      const ScheduleCheck v = check(more);
+      if (v.kind != ScheduleCheck::kOk || !v.matrix_shared) return fail("validation: a list with a detached subtree is a valid list");
+      for (int k20 = 0; k20 < 2; ++k20) {
+        rdamd::ScheduleShape sh;
+        sh.tips = n; sh.sites = 100; sh.tip_stride = 100; sh.rate_cats = 2; sh.prob_matrices = mats; sh.k20 = k20 != 0;
+        rdamd::Program prog;
+        const unsigned lost = rdamd::compile_program(sh, more, {}, {}, prog);
+        if (lost != extra) return fail("unreachable operations", (int)lost, (int)extra);
+      }
+      ++cases;
+    }
+  }
+  return 0;
+}
+
+// class counts of every operation's node the way the clade cache finds them (clade_intern): from the
+// children's per-site classes, 0 once a subtree has more than max_classes
+static std::vector<unsigned> class_counts(const std::vector<rdamd_operation_t> &ops, unsigned n, size_t sites,
+                                          const std::vector<uint8_t> &tipcodes, unsigned max_classes) {
+  std::vector<unsigned> count(ops.size(), 0);
+  std::vector<std::vector<uint8_t>> cls(ops.size());
+  std::vector<uint8_t> cmap;
+  for (size_t i = 0; i < ops.size(); ++i) {
+    const unsigned ch[2] = {ops[i].child1_clv_index, ops[i].child2_clv_index};
+    const uint8_t *in[2];
+    unsigned cnt[2];
+    bool small = true;
+    for (int k = 0; k < 2; ++k) {
+      if (ch[k] < n) { in[k] = tipcodes.data() + (size_t)ch[k] * sites; cnt[k] = 16; continue; }
+      in[k] = cls[ch[k] - n].data(); cnt[k] = count[ch[k] - n];   // (operation k writes CLV n + k)
+      if (!cnt[k]) small = false;
+    }
+    if (small) count[i] = rdamd::clade_classes(in[0], cnt[0], in[1], cnt[1], sites, max_classes, cls[i], cmap);
+  }
+  return count;
+}
+
+static int check_block(const rdamd::ScheduleBlock &b, const rdamd::Program &main_prog, const rdamd::Program *plain,
+                       const rdamd::CladeSelection &sel, const std::vector<double> &brlen, bool k20, unsigned n,
+                       const std::vector<rdamd_operation_t> &ops) {
+  using namespace rdamd;
+  const size_t mask_bytes = k20 ? 4 * ((brlen.size() + 31) / 32) : 0;
+  const size_t at[6] = {b.o_prog, b.o_plain, b.o_steps, b.o_groups, b.o_brlen, b.o_tipmask};
+  const size_t len[6] = {sizeof(FusedOp) * (main_prog.steps.size() + 4), plain ? sizeof(FusedOp) * (plain->steps.size() + 4) : 0,
+                         sizeof(CladeStep) * sel.steps.size(), sizeof(CladeGroup) * sel.groups.size(),
+                         sizeof(double) * brlen.size(), mask_bytes};
+  if (b.o_prog != 0 || b.host.size() != b.total || b.total % 64) return fail("block: size");
+  for (int k = 0; k < 6; ++k) {
+    if (at[k] % 64) return fail("block: a piece is not 64-byte aligned", k);
+    if (at[k] + len[k] > (k < 5 ? at[k + 1] : b.total)) return fail("block: a piece runs into the next", k);
+  }
+  auto program_at = [&](size_t off, const Program &pr) {
+    const FusedOp *f = (const FusedOp *)(b.host.data() + off);
+    if (memcmp(f, pr.steps.data(), sizeof(FusedOp) * pr.steps.size())) return fail("block: program");
+    for (size_t k = 0; k < 4; ++k)
+      if (memcmp(f + pr.steps.size() + k, &pr.steps.back(), sizeof(FusedOp))) return fail("block: the four tail steps", (int)k);
+    return 0;
+  };
+  if (program_at(b.o_prog, main_prog) || (plain && program_at(b.o_plain, *plain))) return 1;
+  if (!sel.steps.empty() && memcmp(b.host.data() + b.o_steps, sel.steps.data(), len[2])) return fail("block: clade steps");
+  if (!sel.groups.empty() && memcmp(b.host.data() + b.o_groups, sel.groups.data(), len[3])) return fail("block: clade groups");
+  if (memcmp(b.host.data() + b.o_brlen, brlen.data(), len[4])) return fail("block: branch lengths");
+  std::set<unsigned> tip_branches;
+  for (const rdamd_operation_t &o : ops) {
+    if (o.child1_clv_index < n) tip_branches.insert(o.child1_matrix_index);
+    if (o.child2_clv_index < n) tip_branches.insert(o.child2_matrix_index);
+  }
+  for (size_t m = 0; m < 8 * mask_bytes; ++m) {
+    const uint32_t word = ((const uint32_t *)(b.host.data() + b.o_tipmask))[m >> 5];
+    if (((word >> (m & 31)) & 1u) != tip_branches.count((unsigned)m)) return fail("block: tip mask", (int)m);
+  }
+  return 0;
+}
+
+static int check_clade_selection(std::mt19937 &rng, int &cases) {
+  using namespace rdamd;
+  unsigned long folded_ops = 0, all_ops = 0, wide_tips = 0;
+  for (int rep = 0; rep < 240; ++rep) {
+    unsigned n;
+    std::vector<rdamd_operation_t> ops = plan_tree(rng, rep, 120, n);
+    const unsigned count = (unsigned)ops.size(), n_mat = 2 * n - 2;
+    const bool k20 = rep % 6 == 5, shared = rep % 8 == 3;
+    if (shared) ops[rng() % count].child2_matrix_index = ops[rng() % count].child1_matrix_index;
+    std::vector<unsigned> idx;
+    std::vector<double> len;
+    branch_list(rng, n_mat, idx, len);
+    const ScheduleCheck v = validate_schedule(n, n, n_mat, ops.data(), count, idx.data(), len.data(), n_mat);
+    if (v.kind != ScheduleCheck::kOk || v.matrix_shared != shared) return fail("selection: the list is valid", rep);
+    ScheduleShape sh;
+    sh.tips = n; sh.sites = 200 + rng() % 1801; sh.tip_stride = (sh.sites + 3u) & ~3u; sh.rate_cats = 1 + rng() % 4;
+    sh.prob_matrices = n_mat; sh.k20 = k20;
+    const unsigned limit = rep % 2 ? 16u : 64u;   // what a table slot holds; the cache may count further (64-row tables that do not fit)
+    sh.wide_mode = !k20 && limit == 64;
+    Program plain, folded;
+    if (compile_program(sh, ops, {}, {}, plain)) return fail("selection: the plain program");
+    CladeSelection sel;
+    if (!k20) {
+      // tip codes: 2 to 4 symbols; half the alignments repeat a few columns (where whole clades fold)
+      const unsigned symbols = 2 + rng() % 3, pool = rep % 4 < 2 ? 0 : 3 + rng() % 78;
+      std::vector<uint8_t> columns((size_t)std::max(pool, 1u) * n), tipcodes((size_t)n * sh.sites);
+      for (uint8_t &x : columns) x = (uint8_t)(1u << (rng() % symbols));
+      for (size_t s = 0; s < sh.sites; ++s) {
+        const size_t col = pool ? rng() % pool : 0;
+        for (unsigned t = 0; t < n; ++t) tipcodes[(size_t)t * sh.sites + s] = pool ? columns[col * n + t] : (uint8_t)(1u << (rng() % symbols));
+      }
+      const std::vector<unsigned> n_classes = class_counts(ops, n, sh.sites, tipcodes, rep % 3 == 0 ? 64u : limit);
+      std::vector<unsigned> node_id(count);
+      for (unsigned i = 0; i < count; ++i) node_id[i] = n + 7 * i + 1;
+      sel = select_clades(ops.data(), count, n, v, node_id, n_classes, limit);
+      if (sel.small.size() != count || sel.small[count - 1]) return fail("selection: the root operation is never folded");
+      if (shared && (!sel.groups.empty() || !sel.steps.empty() || sel.n_wide || sel.clade_rows ||
+                     std::count(sel.small.begin(), sel.small.end(), 0) != (std::ptrdiff_t)count))
+        return fail("selection: a shared matrix index folds nothing");
+      if (sel.groups.size() != sel.tip_ops.size()) return fail("selection: one pseudo-tip per group");
+      std::vector<int> seen(count, 0);
+      unsigned rows = 0, wide = 0, at = 0;
+      for (size_t g = 0; g < sel.groups.size(); ++g) {
+        const CladeGroup &grp = sel.groups[g];
+        const unsigned top = sel.tip_ops[g];
+        if (grp.first != at || grp.count == 0 || grp.first + grp.count > sel.steps.size()) return fail("selection: group bounds", (int)g);
+        if (g && top <= sel.tip_ops[g - 1]) return fail("selection: groups in the order of the list", (int)g);
+        if (!sel.small[top] || sel.small[v.consumer[top]]) return fail("selection: a pseudo-tip is small, its consumer is not", (int)top);
+        std::vector<unsigned> op_of(grp.count);
+        for (unsigned k = 0; k < grp.count; ++k) {
+          const CladeStep &st = sel.steps[grp.first + k];
+          const unsigned j = (st.pad - n - 1) / 7;   // (the node id carries the operation)
+          if (j >= count || node_id[j] != st.pad || !sel.small[j] || seen[j]++) return fail("selection: a step is a small operation, once", (int)j);
+          op_of[k] = j;
+          const unsigned ch[2] = {ops[j].child1_clv_index, ops[j].child2_clv_index};
+          const unsigned mt[2] = {ops[j].child1_matrix_index, ops[j].child2_matrix_index};
+          for (int c = 0; c < 2; ++c) {
+            if (ch[c] < n) { if (st.src[c] != mt[c]) return fail("selection: a tip child's source is its matrix", (int)j, c); continue; }
+            const unsigned from = st.src[c] & 0x7fffffffu;   // the whole subtree: every inner child is a step in front
+            if (!(st.src[c] & 0x80000000u) || from >= k || op_of[from] != v.producer.at(ch[c])) return fail("selection: a nested source names an earlier step of the group", (int)j, c);
+          }
+          const rdamd_operation_t &up = ops[v.consumer[j]];
+          if (st.out_mat != (up.child1_clv_index == ops[j].parent_clv_index ? up.child1_matrix_index : up.child2_matrix_index))
+            return fail("selection: the branch above", (int)j);
+          if (st.n_classes != n_classes[j] || st.n_classes == 0 || st.n_classes > limit || st.map_off != 0) return fail("selection: classes", (int)j);
+          if (st.last != (k + 1 == grp.count ? 1u : 0u) || (st.last && j != top)) return fail("selection: `last` sits on the group's final step, the pseudo-tip", (int)j);
+          // inside the group every step but the last hands its row to a later step of the group
+          if (!st.last && !sel.small[v.consumer[j]]) return fail("selection: a nested step's consumer is small", (int)j);
+          const bool wants_wide = st.last && st.n_classes > 16;
+          if (st.wide_slot != (wants_wide ? wide : 0xffffffffu)) return fail("selection: wide slot", (int)j, (int)st.wide_slot);
+          if (wants_wide && (!sel.pseudo_wide.count(ops[j].parent_clv_index) || sel.pseudo_wide.at(ops[j].parent_clv_index) != wide)) return fail("selection: pseudo_wide", (int)j);
+          wide += wants_wide;
+          rows += st.n_classes;
+        }
+        at += grp.count;
+      }
+      if (at != sel.steps.size() || wide != sel.n_wide || sel.pseudo_wide.size() != wide || rows != sel.clade_rows) return fail("selection: totals", (int)rows, (int)sel.clade_rows);
+      const std::vector<rdamd_operation_t> kept = sel.kept(ops.data());
+      size_t next = 0;   // kept: the operations that are not small, in the list's order; with the groups' every operation once
+      for (unsigned i = 0; i < count; ++i) {
+        if ((sel.small[i] != 0) != (seen[i] == 1)) return fail("selection: every small operation is in one group", (int)i);
+        if (sel.small[i]) continue;
+        if (next >= kept.size() || kept[next++].parent_clv_index != ops[i].parent_clv_index) return fail("selection: kept", (int)i);
+      }
+      if (next != kept.size()) return fail("selection: kept (size)");
+      if (!sel.groups.empty()) {   // the folded program: the root expression over tips and pseudo-tips
+        ClvMap pseudo_row;
+        for (size_t g = 0; g < sel.groups.size(); ++g) pseudo_row[ops[sel.tip_ops[g]].parent_clv_index] = n + (unsigned)g;
+        ProgramTrace trace;
+        if (compile_program(sh, kept, pseudo_row, sel.pseudo_wide, folded, &trace)) return fail("selection: operations of the kept list are unreachable");
+        unsigned mem_depth = 0;
+        if (replay(trace.c, trace.runner_up, expected(trace.c, kept, (unsigned)kept.size() - 1), mem_depth)) return 1;
+        if (folded.steps.size() != kept.size()) return fail("selection: one step per kept operation");
+      }
+      folded_ops += count - kept.size(); all_ops += count; wide_tips += sel.n_wide;
+    }
+    const bool is_folded = !sel.groups.empty();
+    const Program &main_prog = is_folded ? folded : plain;
+    const ScheduleBlock b = pack_schedule_block(main_prog, is_folded ? &plain : nullptr, sel.steps, sel.groups, v.brlen, k20, n,
+                                                ops.data(), count);
+    if (check_block(b, main_prog, is_folded ? &plain : nullptr, sel, v.brlen, k20, n, ops)) return 1;
+    ++cases;
+  }
+  std::fprintf(stderr, "clade selection: %lu of %lu operations folded, %lu 64-row pseudo-tips\n", folded_ops, all_ops, wide_tips);
+  if (!folded_ops || folded_ops == all_ops || !wide_tips) return fail("selection: the cases fold nothing, or everything");
+  return 0;
+}
+
 int main() {
   std::mt19937 rng(20240603);
   int cases = 0;
@@ -582,6 +916,7 @@ int main() {
     ++cases;
   }
   if (check_planner(rng, cases)) return 1;
+  if (check_validation(rng, cases) || check_clade_selection(rng, cases)) return 1;
   std::printf("host logic OK %d\n", cases);
   return 0;
 }

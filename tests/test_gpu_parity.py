@@ -533,6 +533,65 @@ def test_fused_schedule_validation():
         p20.schedule(ops, pmi, brl)
 
 
+def test_fused_schedule_refusals_are_worded_and_leave_the_partition_usable():
+    """what the schedule planner (csrc/schedule_plan.hpp) refuses comes back through the C ABI in
+    rdamd_schedule_create's words, without a launch; a schedule created afterwards evaluates to the
+    oracle's value (lock, block pool and clade cache survive a refusal)"""
+    w = synth.workload(5, 8, 4, 1, 62)
+    tree = rd.Tree.from_newick(w["newick"])
+    g, o = pair(tree, w["seqs"], 4, 1)
+    gr = rd.Partition.for_tree(tree, 4, 8, 1, attributes=rd.ATTRIB_SITE_REPEATS)
+    util.load_tips(gr, tree, w["seqs"], rd.MAP_NT)
+    rl = tree.root_location(0).with_ratio(0.4)
+    ops, pmi, brl = tree.generate_operations(rl)
+    assert len(ops) == 4
+    Op = type(ops[0])
+    freqs = [0.31, 0.19, 0.23, 0.27]
+
+    def edited(changes):       # {operation index: {field: value}}
+        out = [Op.from_buffer_copy(op) for op in ops]
+        for i, change in changes.items():
+            for k, val in change.items():
+                setattr(out[i], k, val)
+        return out
+
+    def refused(part, words, *args):
+        with pytest.raises(rd.RdamdError) as err:
+            part.schedule(*args)
+        assert words in str(err.value), str(err.value)
+
+    def reads(op):
+        return op.child1_clv_index, op.child2_clv_index
+
+    # the first operation's result, read a second time by operation 2: by it and by whoever read
+    # it before, or -- where the root operation is its reader -- by operations 1 and 2
+    c = ops[0].parent_clv_index
+    again = {"child1_clv_index": c}
+    twice = {1: again} if c in reads(ops[2]) else {2: again} if c in reads(ops[1]) else {1: again, 2: again}
+    for part in (g, gr):
+        part.profile_enable(True)
+        part.profile_read()
+        not_post_order = "operation 2 is not part of a valid post-order traversal"
+        refused(part, not_post_order, edited({2: {"child2_clv_index": ops[3].parent_clv_index}}), pmi, brl)
+        refused(part, not_post_order, edited(twice), pmi, brl)
+        detached = Op.from_buffer_copy(ops[0])      # one more operation over two tips, in front of the root operation
+        detached.parent_clv_index = max(op.parent_clv_index for op in ops) + 1
+        detached.parent_scaler_index = -1
+        assert all(ch < 5 for ch in reads(detached))
+        refused(part, "1 of 5 operations are not reachable", list(ops[:3]) + [detached, ops[3]], pmi, brl)
+        refused(part, "invalid branch", ops, pmi, -brl)
+        assert all(n == 0 for _, n in part.profile_read().values())      # nothing was launched
+        sched = part.schedule(ops, pmi, brl)
+        got = part.evaluate_batch([sched], [w["subst"]], [freqs], [w["rates"]])[0]
+        want = _oracle_eval(o, tree, rl, w["subst"], freqs, w["rates"])
+        assert util.rel_err(got, want) < LNL_TOL, (got, want)
+        assert part.profile_read()["fused"][1] >= 1
+    p5 = rd.Partition(5, 7, 5, 8, 1, 8, 1, 7)
+    refused(p5, "the fused evaluator handles", ops, pmi, brl)
+    for p in (g, gr, o, p5):
+        p.destroy()
+
+
 def test_c2_full_size_fused_properties(c2_full):
     w, tree, g = c2_full
     rng = np.random.default_rng(99)

@@ -1,9 +1,11 @@
 """Pure host logic of round 3, without a GPU: the subtree pattern-class census behind the
 clade tables (csrc/clade_classes.hpp), the cutting of a 20-state operation list into
-side-by-side pieces (csrc/k20_split.hpp) and the traversal compiler of the fused evaluators
-(csrc/traversal_compiler.hpp: its programs replayed symbolically) and the planner of the CLV
-traversal launches (csrc/clv_plan.hpp: its plans replayed symbolically), checked by
-tests/cpp/host_logic_check.cpp."""
+side-by-side pieces (csrc/k20_split.hpp), the traversal compiler of the fused evaluators
+(csrc/traversal_compiler.hpp) as the schedule planner configures it (csrc/schedule_plan.hpp: the
+programs rdamd_schedule_create hands the kernels, replayed symbolically), the rest of that planner
+(the lists it refuses and where, the clades it folds into pseudo-tips, the layout of a schedule's
+device block) and the planner of the CLV traversal launches (csrc/clv_plan.hpp: its plans replayed
+symbolically), checked by tests/cpp/host_logic_check.cpp."""
 import os
 import subprocess
 
@@ -19,7 +21,7 @@ def test_clade_classes_k20_split_and_traversal_compiler(tmp_path):
                            os.path.join(util.ROOT, "tests", "cpp", "host_logic_check.cpp"), "-o", exe])
     out = subprocess.run([exe], stdout=subprocess.PIPE, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.startswith("host logic OK"), out.stdout
-    assert int(out.stdout.split()[-1]) >= 1802   # (602 of them the planner's)
+    assert int(out.stdout.split()[-1]) >= 3636   # (602 of them the CLV planner's, 1440 the schedule planner's)
 
 
 def test_host_logic_under_address_and_undefined_behaviour_sanitizers(tmp_path):
