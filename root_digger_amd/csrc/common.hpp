@@ -287,9 +287,17 @@ hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const 
                              double *d_mean);
 
 // kernels_root.hip
+// The grid every root reduction is laid out over: one lane per (site, rate) -- the group layout --
+// or per site, in workgroups of 256 lanes, at most 1024 of them (a lane strides beyond that), never 0.
+struct RootShape { bool group; unsigned blocks; };
+RootShape root_lnl_shape(const rdamd_partition *p);
 hipError_t launch_root_lnl(rdamd_partition *p, unsigned clv_index, int scaler_index,
                            const unsigned *d_freqs_indices, double *d_persite,
                            double *d_out);
+// many root CLVs of one partition in one launch (bit-identical to launch_root_lnl each)
+hipError_t launch_root_lnl_batch(rdamd_partition *p, unsigned count, const unsigned *d_clv_rel,
+                                 const int *d_scaler_idx, const unsigned *d_fidx,
+                                 double *d_partials, double *d_out);
 // the whole root-only evaluation (P-matrices, root op, reduction) as one launch
 hipError_t launch_root_single(rdamd_partition *p, const LevelOp &op, const double *len1,
                               const double *len2, unsigned n_positions,
@@ -306,6 +314,9 @@ struct RootSingleArgs {
   unsigned abl;                 // timing experiments (profiles/root_interference.py): 1 = no exponentiation
 #endif
 };
+// n_positions >= 1 lengths per child and R parameter indices, as the kernels want them
+RootSingleArgs root_single_args(const double *len1, const double *len2, unsigned n_positions,
+                                const unsigned *params_indices, unsigned R);
 // one row of root_multi_dna_kernel: everything root_single_dna_kernel takes as arguments
 struct RootItem {
   DeviceView v;
@@ -317,14 +328,8 @@ struct RootItem {
   double *partials;
   unsigned *counter;
   double *result;      // [kRootMaxPositions]
-  unsigned blocks, pad;
+  unsigned blocks, pad;   // blocks: root_lnl_shape's
 };
-unsigned root_single_blocks(const rdamd_partition *p);
 hipError_t launch_root_multi(const RootItem *d_items, unsigned n_items, unsigned R, unsigned max_positions,
                              unsigned max_blocks, hipStream_t stream);
-// many root CLVs of one partition in one launch (bit-identical to launch_root_lnl each)
-unsigned root_lnl_blocks(const rdamd_partition *p);
-hipError_t launch_root_lnl_batch(rdamd_partition *p, unsigned count, const unsigned *d_clv_rel,
-                                 const int *d_scaler_idx, const unsigned *d_fidx,
-                                 double *d_partials, double *d_out);
 }  // namespace rdamd

@@ -9,6 +9,8 @@
 // (per-lane strided sums -> wave shuffle tree -> LDS -> one finishing
 // workgroup), so a repeated call returns the bit-identical value the
 // reference's test demands (test/src/model.cpp:73); no floating-point atomics.
+#include <algorithm>
+
 #include "common.hpp"
 #include "expm_k4.hpp"
 
@@ -16,16 +18,38 @@ namespace rdamd {
 
 constexpr unsigned kRootBlocks = 1024;
 
-__device__ inline double block_sum_256(double v, double *lds) {
-  // wave tree
+// the shuffle tree over a wave: lane 0 ends up with the sum
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
+
+// the four wave sums of a 256-lane block, in their fixed order
+__device__ __forceinline__ double fold4(double w0, double w1, double w2, double w3) {
+  return ((w0 + w1) + w2) + w3;
+}
+
+__device__ inline double block_sum_256(double v, double *lds) {
+  v = wave_sum(v);
   const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (lane == 0) lds[w] = v;
   __syncthreads();
   double r = 0.0;
-  if (threadIdx.x == 0) r = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+  if (threadIdx.x == 0) r = fold4(lds[0], lds[1], lds[2], lds[3]);
   return r;
+}
+
+// what a site adds to lnL: pattern weight x [ log(term) + rescalings x log(2^-256) ]
+// (sc: where the site's count of rescalings is, null without a scaler.  Pointers, so that the
+// reductions below load count and weight behind the logarithm, not in front of it.)
+__device__ __forceinline__ double site_lnl(double term, const unsigned *sc, const unsigned *weight) {
+  double l = log(term);
+  if (sc) {
+    const unsigned n = *sc;
+    if (n) l += (double)n * kLogScaleThreshold;
+  }
+  return l * (double)*weight;
 }
 
 // sum_k c[k] * f[k] with a pinned evaluation order (one fma chain), so the
@@ -44,15 +68,37 @@ __device__ __forceinline__ double dot_freq_k20_tile(const double *tile, unsigned
   return tr;
 }
 
+// Which root CLV a workgroup reduces.  The single launch has the one its pointer arguments name
+// and may store the per-site values.  A batched launch reduces MANY root CLVs of one partition
+// (blockIdx.y = which; clv_rel: CLV indices minus `tips`): the kernel, hence the grid shape in x,
+// the per-lane order and the block tree, is the single launch's, so every value is bit-identical
+// to a separate rdamd_compute_root_loglikelihood call.
+template <bool BATCH> struct RootRow;
+template <> struct RootRow<false> { double *persite; };
+template <> struct RootRow<true> { const unsigned *clv_rel; const int *scaler_idx; size_t clv_doubles; };
+
+// (in a batch clv, scaler and partials arrive as the partition's buffers and leave as the row's;
+// the pointer types are template parameters because the kernels' are __restrict__-qualified)
+template <bool BATCH, class Clv, class Scaler, class Partials>
+__device__ __forceinline__ void root_row_select(const RootRow<BATCH> &row, unsigned S, Clv &clv, Scaler &scaler,
+                                                Partials &partials) {
+  if constexpr (BATCH) {
+    clv += (size_t)row.clv_rel[blockIdx.y] * row.clv_doubles;
+    const int sci = row.scaler_idx[blockIdx.y];
+    scaler = sci >= 0 ? scaler + (size_t)sci * S : nullptr;
+    partials += (size_t)blockIdx.y * gridDim.x;
+  }
+}
+
 // one lane per (site, rate); R in {1,2,4,8,16}
-template <int R>
+template <int R, bool BATCH>
 __global__ void __launch_bounds__(256)
 root_lnl_group_kernel(const double *__restrict__ clv, const unsigned *__restrict__ scaler,
                       const double *__restrict__ freqs, const unsigned *__restrict__ fidx,
                       const double *__restrict__ rate_w, const unsigned *__restrict__ pw,
-                      unsigned S, unsigned K, double *__restrict__ persite,
-                      double *__restrict__ partials) {
+                      unsigned S, unsigned K, const RootRow<BATCH> row, double *__restrict__ partials) {
   __shared__ double lds[4];
+  root_row_select(row, S, clv, scaler, partials);
   const size_t total = (size_t)S * R;
   const size_t stride = (size_t)gridDim.x * 256;
   double acc = 0.0;
@@ -67,13 +113,8 @@ root_lnl_group_kernel(const double *__restrict__ clv, const unsigned *__restrict
 #pragma unroll
     for (int q = 0; q < R; ++q) term += __shfl(tr, base + q);
     if (r == 0) {
-      double l = log(term);
-      if (scaler) {
-        unsigned sc = scaler[s];
-        if (sc) l += (double)sc * kLogScaleThreshold;
-      }
-      l *= (double)pw[s];
-      if (persite) persite[s] = l;
+      const double l = site_lnl(term, scaler ? scaler + s : nullptr, pw + s);
+      if constexpr (!BATCH) if (row.persite) row.persite[s] = l;
       acc += l;
     }
   }
@@ -82,13 +123,15 @@ root_lnl_group_kernel(const double *__restrict__ clv, const unsigned *__restrict
 }
 
 // one lane per site (any R, K)
+template <bool BATCH>
 __global__ void __launch_bounds__(256)
 root_lnl_site_kernel(const double *__restrict__ clv, const unsigned *__restrict__ scaler,
                      const double *__restrict__ freqs, const unsigned *__restrict__ fidx,
                      const double *__restrict__ rate_w, const unsigned *__restrict__ pw,
-                     unsigned S, unsigned R, unsigned K, unsigned tiles, double *__restrict__ persite,
+                     unsigned S, unsigned R, unsigned K, unsigned tiles, const RootRow<BATCH> row,
                      double *__restrict__ partials) {
   __shared__ double lds[4];
+  root_row_select(row, S, clv, scaler, partials);
   double acc = 0.0;
   for (unsigned s = blockIdx.x * 256 + threadIdx.x; s < S; s += gridDim.x * 256) {
     const double *c = clv + (size_t)s * R * K;
@@ -100,93 +143,12 @@ root_lnl_site_kernel(const double *__restrict__ clv, const unsigned *__restrict_
                               : dot_freq(c + (size_t)r * K, f, K);
       term += tr * rate_w[r];
     }
-    double l = log(term);
-    if (scaler) {
-      unsigned sc = scaler[s];
-      if (sc) l += (double)sc * kLogScaleThreshold;
-    }
-    l *= (double)pw[s];
-    if (persite) persite[s] = l;
+    const double l = site_lnl(term, scaler ? scaler + s : nullptr, pw + s);
+    if constexpr (!BATCH) if (row.persite) row.persite[s] = l;
     acc += l;
   }
   double b = block_sum_256(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = b;
-}
-
-// The same reduction for MANY root CLVs of one partition in one launch
-// (blockIdx.y = which): the grid shape in x, the per-lane order and the block
-// tree are those of the single-root kernels, so every value is bit-identical
-// to a separate rdamd_compute_root_loglikelihood call.
-template <int R>
-__global__ void __launch_bounds__(256)
-root_lnl_group_batch_kernel(const double *__restrict__ clv_base, const unsigned *__restrict__ scaler_base,
-                            const unsigned *__restrict__ clv_rel, const int *__restrict__ scaler_idx,
-                            const double *__restrict__ freqs, const unsigned *__restrict__ fidx,
-                            const double *__restrict__ rate_w, const unsigned *__restrict__ pw,
-                            unsigned S, unsigned K, double *__restrict__ partials) {
-  __shared__ double lds[4];
-  const unsigned which = blockIdx.y;
-  const double *clv = clv_base + (size_t)clv_rel[which] * S * R * K;
-  const int sci = scaler_idx[which];
-  const unsigned *scaler = sci >= 0 ? scaler_base + (size_t)sci * S : nullptr;
-  const size_t total = (size_t)S * R;
-  const size_t stride = (size_t)gridDim.x * 256;
-  double acc = 0.0;
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
-    const unsigned s = (unsigned)(idx / R), r = (unsigned)(idx % R);
-    const double *c = clv + idx * K;
-    const double *f = freqs + (size_t)fidx[r] * K;
-    double tr = dot_freq(c, f, K) * rate_w[r];
-    double term = 0.0;
-    const int base = (int)(threadIdx.x & 63) & ~(R - 1);
-#pragma unroll
-    for (int q = 0; q < R; ++q) term += __shfl(tr, base + q);
-    if (r == 0) {
-      double l = log(term);
-      if (scaler) {
-        unsigned sc = scaler[s];
-        if (sc) l += (double)sc * kLogScaleThreshold;
-      }
-      l *= (double)pw[s];
-      acc += l;
-    }
-  }
-  double b = block_sum_256(acc, lds);
-  if (threadIdx.x == 0) partials[(size_t)which * gridDim.x + blockIdx.x] = b;
-}
-
-__global__ void __launch_bounds__(256)
-root_lnl_site_batch_kernel(const double *__restrict__ clv_base, const unsigned *__restrict__ scaler_base,
-                           const unsigned *__restrict__ clv_rel, const int *__restrict__ scaler_idx,
-                           const double *__restrict__ freqs, const unsigned *__restrict__ fidx,
-                           const double *__restrict__ rate_w, const unsigned *__restrict__ pw,
-                           unsigned S, unsigned R, unsigned K, unsigned tiles, size_t clv_doubles,
-                           double *__restrict__ partials) {
-  __shared__ double lds[4];
-  const unsigned which = blockIdx.y;
-  const double *clv = clv_base + (size_t)clv_rel[which] * clv_doubles;
-  const int sci = scaler_idx[which];
-  const unsigned *scaler = sci >= 0 ? scaler_base + (size_t)sci * S : nullptr;
-  double acc = 0.0;
-  for (unsigned s = blockIdx.x * 256 + threadIdx.x; s < S; s += gridDim.x * 256) {
-    const double *c = clv + (size_t)s * R * K;
-    double term = 0.0;
-    for (unsigned r = 0; r < R; ++r) {
-      const double *f = freqs + (size_t)fidx[r] * K;
-      const double tr = tiles ? dot_freq_k20_tile(clv + ((size_t)r * tiles + (s >> 4)) * 320, s & 15u, f)
-                              : dot_freq(c + (size_t)r * K, f, K);
-      term += tr * rate_w[r];
-    }
-    double l = log(term);
-    if (scaler) {
-      unsigned sc = scaler[s];
-      if (sc) l += (double)sc * kLogScaleThreshold;
-    }
-    l *= (double)pw[s];
-    acc += l;
-  }
-  double b = block_sum_256(acc, lds);
-  if (threadIdx.x == 0) partials[(size_t)which * gridDim.x + blockIdx.x] = b;
 }
 
 // fixed-order finish: 256 lanes stride over the partials, then the block tree
@@ -211,7 +173,7 @@ finish_sum_kernel(const double *__restrict__ partials, unsigned n, double *__res
 // P-matrices per position are exponentiated inside the kernel (every block
 // repeats the few hundred flops; expm_k4 is the code of pmatrix_k4_kernel, so
 // the bits are the same), tip tables are built from them in LDS, the block
-// that finishes last folds the partial sums in finish_sum_kernel's order, and
+// that finishes last folds the partial sums as finish_sum_kernel does, and
 // the result lands in pinned host memory.  A root-only evaluation is
 // launch-latency, not bandwidth: one launch + one stream wait instead of three
 // copies, three launches and a copy back.
@@ -338,7 +300,7 @@ root_single_body(const DeviceView &v, const LevelOp &op, const RootSingleArgs &r
       const unsigned sc0 = (lsc ? lsc[s] : 0u) + (rsc ? rsc[s] : 0u);
       const double *f = freqs + (size_t)pidx_of(r) * 4;
       const double wgt = rate_w[r];
-      const double weight = (double)pw[s];
+      const unsigned weight = pw[s];
       const int base = (int)lane & ~(R - 1);
       double t1[4], t2[4], o[4];
       {
@@ -369,27 +331,21 @@ root_single_body(const DeviceView &v, const LevelOp &op, const RootSingleArgs &r
       double term = 0.0;
 #pragma unroll
       for (int q2 = 0; q2 < R; ++q2) term += __shfl(tr, base + q2);
-      if (r == 0) {
-        double l = log(term);
-        if (sc) l += (double)sc * kLogScaleThreshold;
-        acc += l * weight;
-      }
+      if (r == 0) acc += site_lnl(term, &sc, &weight);
       if (last) {
         if (r == 0) psc[s] = sc;
         pc[idx * 2] = make_double2(o[0], o[1]);
         pc[idx * 2 + 1] = make_double2(o[2], o[3]);
       }
     }
-    // this wave's share of block_sum_256: the wave tree; the four wave sums of a virtual block
-    // are combined -- ((w0 + w1) + w2) + w3, block_sum_256's order -- in the final fold
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    // this wave's share of block_sum_256; the four wave sums of a virtual block meet in the final fold
+    acc = wave_sum(acc);
     if (lane == 0) partials[((size_t)a * nblocks + bid) * 4 + w] = acc;
     }
   }
-  // the wave that arrives last folds the partials (finish_sum_kernel's order: lane t of a
-  // 256-lane block adds the block sums t, t + 256, ..., then block_sum_256 over the lanes --
-  // one wave plays the block's four in turn)
+  // the wave that arrives last folds the partials as finish_sum_kernel does (lane t of a 256-lane
+  // block adds the block sums t, t + 256, ..., then block_sum_256 over the lanes), one wave
+  // playing the block's four in turn
   __threadfence();
   unsigned ticket = 0;
   if (lane == 0) ticket = atomicAdd(counter, 1u);
@@ -398,17 +354,15 @@ root_single_body(const DeviceView &v, const LevelOp &op, const RootSingleArgs &r
   __threadfence();
   for (unsigned a = 0; a < NA; ++a) {
     const volatile double *p = partials + (size_t)a * nblocks * 4;
-    double wave_sum[4];
+    double ws[4];
 #pragma unroll
     for (unsigned vw = 0; vw < 4; ++vw) {
       double sum = 0.0;
       for (unsigned i = vw * 64 + lane; i < nblocks; i += 256)
-        sum += ((p[i * 4] + p[i * 4 + 1]) + p[i * 4 + 2]) + p[i * 4 + 3];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
-      wave_sum[vw] = sum;
+        sum += fold4(p[i * 4], p[i * 4 + 1], p[i * 4 + 2], p[i * 4 + 3]);
+      ws[vw] = wave_sum(sum);
     }
-    if (lane == 0) result[a] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+    if (lane == 0) result[a] = fold4(ws[0], ws[1], ws[2], ws[3]);
   }
   if (lane == 0) *counter = 0u;   // ready for the next launch on this stream
 }
@@ -442,73 +396,60 @@ root_multi_dna_kernel(const RootItem *__restrict__ items) {
                       it.partials, it.counter, it.result, blockIdx.x, n_phys, it.blocks);
 }
 
-hipError_t launch_root_lnl(rdamd_partition *p, unsigned clv_index, int scaler_index,
-                           const unsigned *d_fidx, double *d_persite, double *d_out) {
-  const unsigned S = p->sites, R = p->rate_cats, K = p->states;
-  const double *clv = p->d_clv + (size_t)(clv_index - p->tips) * p->clv_doubles();
-  const unsigned *sc = scaler_index >= 0 ? p->d_scaler + (size_t)scaler_index * S : nullptr;
-  const unsigned tiles = p->mfma_layout ? p->clv_tiles() : 0u;
-  unsigned blocks;
-  // (a CLV in the 20-state operand layout goes through the one-lane-per-site kernel)
+// (a CLV in the 20-state operand layout goes through the one-lane-per-site kernel)
+RootShape root_lnl_shape(const rdamd_partition *p) {
+  const unsigned R = p->rate_cats;
   const bool group = !p->mfma_layout && (R == 1 || R == 2 || R == 4 || R == 8 || R == 16);
-  if (group) {
-    size_t total = (size_t)S * R;
-    blocks = (unsigned)((total + 255) / 256);
-  } else {
-    blocks = (S + 255) / 256;
+  const size_t lanes = group ? (size_t)p->sites * R : p->sites;
+  return {group, (unsigned)std::min<size_t>(std::max<size_t>((lanes + 255) / 256, 1), kRootBlocks)};
+}
+
+template <bool BATCH>
+static auto root_group_kernel(unsigned R) -> decltype(&root_lnl_group_kernel<1, BATCH>) {
+  switch (R) {
+    case 1: return root_lnl_group_kernel<1, BATCH>;
+    case 2: return root_lnl_group_kernel<2, BATCH>;
+    case 4: return root_lnl_group_kernel<4, BATCH>;
+    case 8: return root_lnl_group_kernel<8, BATCH>;
+    default: return root_lnl_group_kernel<16, BATCH>;
   }
-  if (blocks > kRootBlocks) blocks = kRootBlocks;
-  if (blocks == 0) blocks = 1;
-#define RDAMD_ROOT_ARGS clv, sc, p->d_freqs, d_fidx, p->d_rate_weights, p->d_pattern_weights
-  if (group) {
-    switch (R) {
-      case 1: root_lnl_group_kernel<1><<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, K, d_persite, p->d_partials); break;
-      case 2: root_lnl_group_kernel<2><<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, K, d_persite, p->d_partials); break;
-      case 4: root_lnl_group_kernel<4><<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, K, d_persite, p->d_partials); break;
-      case 8: root_lnl_group_kernel<8><<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, K, d_persite, p->d_partials); break;
-      default: root_lnl_group_kernel<16><<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, K, d_persite, p->d_partials); break;
-    }
-  } else {
-    root_lnl_site_kernel<<<blocks, 256, 0, p->stream>>>(RDAMD_ROOT_ARGS, S, R, K, tiles, d_persite, p->d_partials);
-  }
-#undef RDAMD_ROOT_ARGS
+}
+
+// `count` rows of root_lnl_shape(p).blocks partial sums each, then one finishing workgroup per row
+template <bool BATCH>
+static hipError_t launch_root_rows(rdamd_partition *p, unsigned count, const double *clv, const unsigned *scaler,
+                                   const RootRow<BATCH> &row, const unsigned *d_fidx, double *d_partials,
+                                   double *d_out) {
+  const unsigned S = p->sites, R = p->rate_cats, K = p->states;
+  const RootShape shape = root_lnl_shape(p);
+  const dim3 grid(shape.blocks, count);
+  if (shape.group)
+    root_group_kernel<BATCH>(R)<<<grid, 256, 0, p->stream>>>(clv, scaler, p->d_freqs, d_fidx, p->d_rate_weights,
+                                                             p->d_pattern_weights, S, K, row, d_partials);
+  else
+    root_lnl_site_kernel<BATCH><<<grid, 256, 0, p->stream>>>(clv, scaler, p->d_freqs, d_fidx, p->d_rate_weights,
+                                                             p->d_pattern_weights, S, R, K,
+                                                             p->mfma_layout ? p->clv_tiles() : 0u, row, d_partials);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  finish_sum_kernel<<<1, 256, 0, p->stream>>>(p->d_partials, blocks, d_out);
+  finish_sum_kernel<<<count, 256, 0, p->stream>>>(d_partials, shape.blocks, d_out);
   return hipGetLastError();
 }
 
-unsigned root_lnl_blocks(const rdamd_partition *p) {
-  const unsigned S = p->sites, R = p->rate_cats;
-  const bool group = !p->mfma_layout && (R == 1 || R == 2 || R == 4 || R == 8 || R == 16);
-  unsigned blocks = group ? (unsigned)(((size_t)S * R + 255) / 256) : (S + 255) / 256;
-  if (blocks > kRootBlocks) blocks = kRootBlocks;
-  return blocks ? blocks : 1;
+hipError_t launch_root_lnl(rdamd_partition *p, unsigned clv_index, int scaler_index,
+                           const unsigned *d_fidx, double *d_persite, double *d_out) {
+  const double *clv = p->d_clv + (size_t)(clv_index - p->tips) * p->clv_doubles();
+  const unsigned *sc = scaler_index >= 0 ? p->d_scaler + (size_t)scaler_index * p->sites : nullptr;
+  return launch_root_rows(p, 1, clv, sc, RootRow<false>{d_persite}, d_fidx, p->d_partials, d_out);
 }
 
-// d_clv_rel: CLV indices minus `tips`; d_partials: count * root_lnl_blocks(p) doubles
+// d_clv_rel: CLV indices minus `tips`; d_partials: count * root_lnl_shape(p).blocks doubles
 hipError_t launch_root_lnl_batch(rdamd_partition *p, unsigned count, const unsigned *d_clv_rel,
                                  const int *d_scaler_idx, const unsigned *d_fidx,
                                  double *d_partials, double *d_out) {
   if (!count) return hipSuccess;
-  const unsigned S = p->sites, R = p->rate_cats, K = p->states;
-  const unsigned blocks = root_lnl_blocks(p);
-  const dim3 grid(blocks, count);
-  const unsigned tiles = p->mfma_layout ? p->clv_tiles() : 0u;
-#define RDAMD_RB_ARGS p->d_clv, p->d_scaler, d_clv_rel, d_scaler_idx, p->d_freqs, d_fidx, p->d_rate_weights, p->d_pattern_weights
-  switch (p->mfma_layout ? 0u : R) {
-    case 1: root_lnl_group_batch_kernel<1><<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, K, d_partials); break;
-    case 2: root_lnl_group_batch_kernel<2><<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, K, d_partials); break;
-    case 4: root_lnl_group_batch_kernel<4><<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, K, d_partials); break;
-    case 8: root_lnl_group_batch_kernel<8><<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, K, d_partials); break;
-    case 16: root_lnl_group_batch_kernel<16><<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, K, d_partials); break;
-    default: root_lnl_site_batch_kernel<<<grid, 256, 0, p->stream>>>(RDAMD_RB_ARGS, S, R, K, tiles, p->clv_doubles(), d_partials); break;
-  }
-#undef RDAMD_RB_ARGS
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  finish_sum_kernel<<<count, 256, 0, p->stream>>>(d_partials, blocks, d_out);
-  return hipGetLastError();
+  return launch_root_rows(p, count, p->d_clv, p->d_scaler, RootRow<true>{d_clv_rel, d_scaler_idx, p->clv_doubles()},
+                          d_fidx, d_partials, d_out);
 }
 
 // Workgroups (= waves) a root step is launched with.  Its arithmetic is laid out over
@@ -538,27 +479,31 @@ static hipError_t launch_root_single_r(rdamd_partition *p, const DeviceView &v, 
   return hipGetLastError();
 }
 
+// (unused positions repeat the last one: same state left behind)
+RootSingleArgs root_single_args(const double *len1, const double *len2, unsigned n_positions,
+                                const unsigned *params_indices, unsigned R) {
+  RootSingleArgs ra{};
+  for (unsigned a = 0; a < kRootMaxPositions; ++a) {
+    ra.len1[a] = len1[std::min(a, n_positions - 1)];
+    ra.len2[a] = len2[std::min(a, n_positions - 1)];
+  }
+  for (unsigned r = 0; r < 8; ++r) ra.params_idx[r] = r < R ? params_indices[r] : 0u;
+  ra.n_positions = n_positions;
+  return ra;
+}
+
 // lengths / parameter indices travel as kernel arguments; `result` must be
 // device-visible (the partition's pinned host block)
 hipError_t launch_root_single(rdamd_partition *p, const LevelOp &op, const double *len1,
                               const double *len2, unsigned n_positions,
                               const unsigned *params_indices, unsigned *d_counter, double *result) {
-  const unsigned S = p->sites, R = p->rate_cats;
+  const unsigned R = p->rate_cats;
   if (n_positions == 0 || n_positions > root_single_max_positions(R) || R > 8) return hipErrorInvalidValue;
-  RootSingleArgs ra;
-  for (unsigned a = 0; a < kRootMaxPositions; ++a) {
-    ra.len1[a] = len1[a < n_positions ? a : n_positions - 1];
-    ra.len2[a] = len2[a < n_positions ? a : n_positions - 1];
-  }
-  for (unsigned r = 0; r < 8; ++r) ra.params_idx[r] = r < R ? params_indices[r] : 0u;
-  ra.n_positions = n_positions;
-  size_t total = (size_t)S * R;
-  unsigned blocks = (unsigned)((total + 255) / 256);
-  if (blocks > kRootBlocks) blocks = kRootBlocks;   // same shape as launch_root_lnl
-  if (blocks == 0) blocks = 1;
+  RootSingleArgs ra = root_single_args(len1, len2, n_positions, params_indices, R);
 #ifdef RDAMD_ABLATION
   ra.abl = getenv("RDAMD_ROOT_NOEXPM") ? 1u : 0u;
 #endif
+  const unsigned blocks = root_lnl_shape(p).blocks;   // (the callers' fast_root_shape: the group layout)
   const DeviceView v = p->view();
   switch (R) {
     case 1: return launch_root_single_r<1>(p, v, op, ra, blocks, d_counter, result);
@@ -567,13 +512,6 @@ hipError_t launch_root_single(rdamd_partition *p, const LevelOp &op, const doubl
     case 8: return launch_root_single_r<8>(p, v, op, ra, blocks, d_counter, result);
     default: return hipErrorInvalidValue;
   }
-}
-
-unsigned root_single_blocks(const rdamd_partition *p) {
-  size_t total = (size_t)p->sites * p->rate_cats;
-  unsigned blocks = (unsigned)((total + 255) / 256);
-  if (blocks > kRootBlocks) blocks = kRootBlocks;   // same shape as launch_root_lnl
-  return blocks ? blocks : 1u;
 }
 
 hipError_t launch_root_multi(const RootItem *d_items, unsigned n_items, unsigned R, unsigned max_positions,

@@ -204,6 +204,10 @@ static const unsigned *bad_rate_index(const rdamd_partition *p, const unsigned *
   return nullptr;
 }
 static bool length_ok(double l) { return l >= 0.0 && std::isfinite(l); }
+// a root CLV and its scaler as the root calls take them: an inner CLV; a scale buffer or none (< 0)
+static bool root_index_ok(const rdamd_partition *p, unsigned clv_index, int scaler_index) {
+  return clv_index >= p->tips && clv_index < p->tips + p->clv_buffers && scaler_index < (int)p->scale_buffers;
+}
 // tip tables made for an older set of state codes are rebuilt before a kernel reads them
 static hipError_t flush_tiptab(rdamd_partition *p) {
   if (!p->tiptab_stale) return hipSuccess;
@@ -217,6 +221,26 @@ static bool fast_root_shape(const rdamd_partition *p, const rdamd_operation_t &r
   const unsigned R = p->rate_cats;
   return p->states == 4 && p->ncodes_cap == 16 && (R == 1 || R == 2 || R == 4 || R == 8) &&
          root_op.parent_scaler_index >= 0;
+}
+
+// What the two lnL calls do before their launch: parameters flushed, scratch for the frequency
+// indices and `extra` bytes more, the indices uploaded (d_fi: the first take of `sc`) ...
+static hipError_t stage_root_lnl(rdamd_partition *p, const unsigned *freqs_indices, size_t extra, Scratch &sc,
+                                 unsigned *&d_fi) {
+  const size_t fi_bytes = sizeof(unsigned) * p->rate_cats;
+  hipError_t e = flush_q(p);
+  if (e == hipSuccess) e = ensure_scratch(p, extra + fi_bytes);
+  if (e != hipSuccess) return e;
+  d_fi = (unsigned *)sc.take(fi_bytes);
+  return upload(p, d_fi, freqs_indices, fi_bytes);
+}
+// ... and around it: a `root` span of the event timer, then the host waits for the stream
+template <class Launch>
+static hipError_t run_root_lnl(rdamd_partition *p, Launch launch) {
+  p->prof_begin(2);
+  const hipError_t e = launch();
+  p->prof_end();
+  return e == hipSuccess ? hipStreamSynchronize(p->stream) : e;
 }
 
 #ifdef RDAMD_ABLATION
@@ -281,21 +305,17 @@ static bool fill_root_item(rdamd_partition *p, rdamd_partition *lead, unsigned i
   }
   rdamd_operation_t o;
   RDAMD_HIP_TRY(op_phys(p, op, &o), false);
-  memset(&it, 0, sizeof it);
-  for (unsigned a = 0; a < kRootMaxPositions; ++a) {   // (unused positions repeat the last one: same state left behind)
-    const unsigned src = std::min(a, n_positions - 1);
-    it.ra.len1[a] = len1[src];
-    it.ra.len2[a] = len2[src];
-    if (!length_ok(it.ra.len1[a]) || !length_ok(it.ra.len2[a])) {
+  for (unsigned a = 0; a < n_positions; ++a)
+    if (!length_ok(len1[a]) || !length_ok(len2[a])) {
       set_error(9, "rdamd_root_loglikelihood_fused_multi: item %u: invalid branch length", i);
       return false;
     }
-  }
   if (bad_rate_index(p, params_indices)) {
     set_error(7, "rdamd_root_loglikelihood_fused_multi: item %u: params index out of range", i);
     return false;
   }
-  for (unsigned r = 0; r < 8; ++r) it.ra.params_idx[r] = r < p->rate_cats ? params_indices[r] : 0u;
+  memset(&it, 0, sizeof it);
+  it.ra = root_single_args(len1, len2, n_positions, params_indices, p->rate_cats);
   RDAMD_HIP_TRY(flush_q(p), false);
   RDAMD_HIP_TRY(flush_tiptab(p), false);
   // whatever this partition's own stream still has queued (parameter uploads just now) must
@@ -307,8 +327,7 @@ static bool fill_root_item(rdamd_partition *p, rdamd_partition *lead, unsigned i
   it.pw = p->d_pattern_weights; it.codemask = p->d_codemask;
   it.partials = p->d_partials; it.counter = p->d_counter;
   it.result = result;   // (pinned host memory: the folding wave writes it there, no copy launch)
-  it.blocks = root_single_blocks(p);
-  it.ra.n_positions = n_positions;
+  it.blocks = root_lnl_shape(p).blocks;   // (fast_root_shape: the group layout)
   return true;
 }
 
@@ -828,8 +847,7 @@ double rdamd_compute_root_loglikelihood(rdamd_partition_t *p, unsigned int clv_i
                                         double *persite_lnl) {
   clear_error();
   const double nan = std::nan("");
-  if (clv_index < p->tips || clv_index >= p->tips + p->clv_buffers ||
-      scaler_index >= (int)p->scale_buffers) {
+  if (!root_index_ok(p, clv_index, scaler_index)) {
     set_error(11, "rdamd_compute_root_loglikelihood: index out of range (clv %u, scaler %d)",
               clv_index, scaler_index);
     return nan;
@@ -841,20 +859,15 @@ double rdamd_compute_root_loglikelihood(rdamd_partition_t *p, unsigned int clv_i
   if (p->sites == 0) return 0.0;   // an empty alignment has likelihood 1
   RDAMD_HIP_TRY(clv_phys(p, clv_index, &clv_index), nan);
   RDAMD_HIP_TRY(scaler_phys(p, scaler_index, &scaler_index), nan);
-  RDAMD_HIP_TRY(flush_q(p), nan);
-  RDAMD_HIP_TRY(ensure_scratch(p, 1024 + sizeof(unsigned) * p->rate_cats), nan);
   Scratch sc{p};
-  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * p->rate_cats);
-  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * p->rate_cats), nan);
+  unsigned *d_fi;
+  RDAMD_HIP_TRY(stage_root_lnl(p, freqs_indices, 1024, sc, d_fi), nan);
   if (persite_lnl && !p->d_persite)
     RDAMD_HIP_TRY(hipMalloc(&p->d_persite, std::max<size_t>(8, sizeof(double) * p->sites)), nan);
-  p->prof_begin(2);
   // the finishing workgroup writes straight into the pinned host block
-  hipError_t le = launch_root_lnl(p, clv_index, scaler_index, d_fi,
-                                  persite_lnl ? p->d_persite : nullptr, p->h_result);
-  p->prof_end();
-  RDAMD_HIP_TRY(le, nan);
-  RDAMD_HIP_TRY(hipStreamSynchronize(p->stream), nan);
+  RDAMD_HIP_TRY(run_root_lnl(p, [&] {
+    return launch_root_lnl(p, clv_index, scaler_index, d_fi, persite_lnl ? p->d_persite : nullptr, p->h_result);
+  }), nan);
   if (persite_lnl)
     RDAMD_HIP_TRY(hipMemcpy(persite_lnl, p->d_persite, sizeof(double) * p->sites,
                             hipMemcpyDeviceToHost), nan);
@@ -868,8 +881,7 @@ int rdamd_compute_root_loglikelihoods(rdamd_partition_t *p, unsigned int count,
   if (count == 0) return RDAMD_SUCCESS;
   std::vector<unsigned> rel(count);
   for (unsigned i = 0; i < count; ++i) {
-    if (clv_indices[i] < p->tips || clv_indices[i] >= p->tips + p->clv_buffers ||
-        scaler_indices[i] >= (int)p->scale_buffers) {
+    if (!root_index_ok(p, clv_indices[i], scaler_indices[i])) {
       set_error(11, "rdamd_compute_root_loglikelihoods: index out of range (entry %u)", i);
       return RDAMD_FAILURE;
     }
@@ -894,25 +906,19 @@ int rdamd_compute_root_loglikelihoods(rdamd_partition_t *p, unsigned int count,
     std::fill(lnl_out, lnl_out + count, 0.0);
     return RDAMD_SUCCESS;
   }
-  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
-  const unsigned blocks = root_lnl_blocks(p);
-  const size_t need = 4096 + sizeof(unsigned) * p->rate_cats + (size_t)count * (8 + 8) +
-                      sizeof(double) * ((size_t)count * blocks + count);
-  RDAMD_HIP_TRY(ensure_scratch(p, need), RDAMD_FAILURE);
+  const unsigned blocks = root_lnl_shape(p).blocks;
   Scratch sc{p};
-  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * p->rate_cats);
+  unsigned *d_fi;
+  RDAMD_HIP_TRY(stage_root_lnl(p, freqs_indices, 4096 + (size_t)count * (8 + 8) +
+                               sizeof(double) * ((size_t)count * blocks + count), sc, d_fi), RDAMD_FAILURE);
   unsigned *d_rel = (unsigned *)sc.take(sizeof(unsigned) * count);
   int *d_sci = (int *)sc.take(sizeof(int) * count);
   double *d_partials = (double *)sc.take(sizeof(double) * (size_t)count * blocks);
   double *d_out = (double *)sc.take(sizeof(double) * count);
-  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * p->rate_cats), RDAMD_FAILURE);
   RDAMD_HIP_TRY(upload(p, d_rel, rel.data(), sizeof(unsigned) * count), RDAMD_FAILURE);
   RDAMD_HIP_TRY(upload(p, d_sci, scaler_indices, sizeof(int) * count), RDAMD_FAILURE);
-  p->prof_begin(2);
-  hipError_t le = launch_root_lnl_batch(p, count, d_rel, d_sci, d_fi, d_partials, d_out);
-  p->prof_end();
-  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipStreamSynchronize(p->stream), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(run_root_lnl(p, [&] { return launch_root_lnl_batch(p, count, d_rel, d_sci, d_fi, d_partials, d_out); }),
+                RDAMD_FAILURE);
   RDAMD_HIP_TRY(hipMemcpy(lnl_out, d_out, sizeof(double) * count, hipMemcpyDeviceToHost),
                 RDAMD_FAILURE);
   return RDAMD_SUCCESS;
@@ -1164,7 +1170,7 @@ int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int
               p->api_states);
     return RDAMD_FAILURE;
   }
-  if (clv_index < p->tips || clv_index >= p->tips + p->clv_buffers || scaler_index >= (int)p->scale_buffers) {
+  if (!root_index_ok(p, clv_index, scaler_index)) {
     set_error(11, "rdamd_site_rate_posteriors: index out of range (clv %u, scaler %d)", clv_index, scaler_index);
     return RDAMD_FAILURE;
   }

@@ -289,6 +289,88 @@ def test_fused_root_positions_do_not_depend_on_their_launch(R):
     assert g.compute_root_loglikelihood(op.parent_clv_index, op.parent_scaler_index) == single[5]
 
 
+@pytest.mark.parametrize("S,R", [(66000, 4),      # one lane per (site, rate): 264 000 lanes
+                                 (262200, 3)])    # one lane per site
+def test_root_reductions_agree_past_the_grid_cap(S, R):
+    """The root reductions run at most 1024 workgroups of 256 lanes (csrc/kernels_root.hip): past
+    262 144 lanes a lane takes several sites, and its stride, not the workgroup index, decides
+    which sites meet in a partial sum.  Every route to a value must still give the same bits:
+    the batched call and the single one for every root CLV of the all-directions schedule, the
+    one-launch root step and the three-call sequence (R = 4), and the per-site values must sum to
+    the value returned with them."""
+    w = synth.workload(5, S, 4, R, 900 + R)
+    tree = rd.Tree.from_newick(w["newick"])
+    d = tree.generate_directional_operations()
+    b = tree.branch_count()      # (room for the tree's own operation lists as well: Partition.for_tree)
+    sizes = dict(tips=5, clv_buffers=max(d["clv_buffers"], b), states=4, sites=S, rate_matrices=1,
+                 prob_matrices=max(d["prob_matrices"], b), rate_cats=R, scale_buffers=max(d["scale_buffers"], b))
+    g, o = rd.Partition(**sizes), OraclePartition(**sizes)
+    weights = np.random.default_rng(S).integers(1, 4, size=S).astype(np.uint32)
+    util.load_tips(g, tree, w["seqs"], rd.MAP_NT, weights)
+    util.load_tips(o, tree, w["seqs"], ORC_MAP_NT, weights)
+    set_model((g, o), w["subst"], g.empirical_frequencies(), w["rates"])
+    for p in (g, o):
+        p.update_prob_matrices(d["matrix_indices"], d["branch_lengths"])
+        p.update_clvs(d["ops"])
+    many = g.compute_root_loglikelihoods(d["root_clv"], d["root_scaler"])
+    assert len(many) == tree.root_count()
+    for rid in range(tree.root_count()):
+        clv, sc = int(d["root_clv"][rid]), int(d["root_scaler"][rid])
+        one = g.compute_root_loglikelihood(clv, sc)
+        assert many[rid] == one, rid
+        assert util.rel_err(one, o.compute_root_loglikelihood(clv, sc)) < LNL_TOL, rid
+    again, persite = g.compute_root_loglikelihood(clv, sc, persite=True)
+    assert again == one
+    assert abs(math.fsum(persite) - one) <= 1e-13 * abs(one)
+    if R == 4:
+        rl = tree.root_location(2).with_ratio(0.42)
+        util.compute_lh(g, tree, rl)
+        op, pmi, _ = tree.generate_derivative_operations(rl)
+        l1, l2 = rl.saved_brlen * 0.3, rl.saved_brlen * 0.7
+        fused = g.root_loglikelihood_fused(op, [l1], [l2])[0]
+        g.update_prob_matrices(pmi, [l1, l2])
+        g.update_clvs([op])
+        assert g.compute_root_loglikelihood(op.parent_clv_index, op.parent_scaler_index) == fused
+    g.destroy()
+    o.destroy()
+
+
+def test_fused_multi_rows_of_unequal_size():
+    """One launch of root_multi_dna_kernel over two partitions of very different size: 40 sites x 4
+    rates are ONE virtual block whose fourth virtual wave has no lane with work, and the row gets
+    fewer physical waves than the launch has per row; 3 000 sites are 47 virtual blocks, 16 virtual
+    waves to a physical one.  Every row must give what rdamd_root_loglikelihood_fused gives on
+    that partition alone, bit for bit, and leave the root CLV and scaler of the last position."""
+    rows = []
+    for S, seed in ((40, 601), (3000, 602)):
+        w = synth.workload(12, S, 4, 4, seed)
+        tree = rd.Tree.from_newick(w["newick"])
+        g = rd.Partition.for_tree(tree, 4, S, 4)
+        util.load_tips(g, tree, w["seqs"], rd.MAP_NT)
+        set_model((g,), w["subst"], g.empirical_frequencies(), w["rates"])
+        rl = tree.root_location(7).with_ratio(0.42)
+        util.compute_lh(g, tree, rl)
+        op, _, _ = tree.generate_derivative_operations(rl)
+        alphas = [0.42, 1e-8, 0.0, 1.0 - 1e-8, 1.0, 0.125, 0.125 + 1e-8, 0.875]
+        rows.append((g, op, [rl.saved_brlen * a for a in alphas], [rl.saved_brlen * (1 - a) for a in alphas]))
+        g.profile_enable(True)
+    parts, ops = [r[0] for r in rows], [r[1] for r in rows]
+    for n in (1, 5, 8):
+        for g in parts:
+            g.profile_read()
+        got = rd.root_loglikelihood_fused_multi(parts, ops, [r[2][:n] for r in rows], [r[3][:n] for r in rows])
+        # (one launch, on the first partition's stream: this was no item-by-item fallback)
+        assert [g.profile_read()["root"][1] for g in parts] == [1, 0]
+        for (g, op, l1, l2), values in zip(rows, got):
+            clv, sc = g.get_clv(op.parent_clv_index), g.get_scaler(op.parent_scaler_index)
+            assert np.array_equal(values, g.root_loglikelihood_fused(op, l1[:n], l2[:n])), (g.sites, n)
+            g.root_loglikelihood_fused(op, l1[n - 1:n], l2[n - 1:n])
+            assert np.array_equal(clv, g.get_clv(op.parent_clv_index)), (g.sites, n)
+            assert np.array_equal(sc, g.get_scaler(op.parent_scaler_index)), (g.sites, n)
+    for g in parts:
+        g.destroy()
+
+
 def test_error_paths():
     tree = rd.Tree.from_file(os.path.join(util.DATA, "single.tree"))
     g = rd.Partition.for_tree(tree, 4, 4, 1)
