@@ -153,7 +153,17 @@ const double *rdamd_partition_frequencies(const rdamd_partition_t *p,
  * The hot path
  * --------------------------------------------------------------------- */
 
-/* replaces corax_update_prob_matrices, src/model.cpp:367, :432, :842.
+/* params_indices / freqs_indices, here and in every call below that takes one: `rate_cats` entries;
+ * entry r names the rate matrix (params_indices) or the frequency set (freqs_indices) of rate
+ * category r, one of the partition's `rate_matrices` sets as rdamd_set_subst_params /
+ * rdamd_set_frequencies filled them.  An entry >= rate_matrices is refused (error 7).  The two are
+ * independent: the frequency indices of a root call need not be the indices the P-matrices were
+ * built with.  rdamd_root_loglikelihood_fused and rdamd_root_loglikelihood_fused_multi take ONE
+ * vector and read both through it.  model_t (rdamd_model_*) and rd_amd create partitions with one
+ * rate matrix and always pass index 0, as the reference does; rdamd_evaluate_batch carries one
+ * parameter set per job and reads neither.
+ *
+ * replaces corax_update_prob_matrices, src/model.cpp:367, :432, :842.
  * P[m][r] = exp(Q * rate_r * t_m) computed on the device for the whole list in
  * one launch. */
 int rdamd_update_prob_matrices(rdamd_partition_t  *p,
@@ -182,7 +192,11 @@ double rdamd_compute_root_loglikelihood(rdamd_partition_t  *p,
  * (src/model.cpp:432-445): two P-matrices + one root op + reduction in a
  * single launch, for `n_alpha` root positions on the same edge at once
  * (compute_dlh, src/model.cpp:481-519, needs two).  The root CLV/scaler of the
- * LAST position is left in the partition exactly as the unfused calls would.
+ * LAST position is left in the partition as the unfused calls would leave it: the
+ * two P-matrices and the scaler bit for bit, the root CLV the one the returned value
+ * was reduced from (an entry may differ from the traversal kernel's in its last bits:
+ * the two kernels contract their products differently).  Category r reads rate matrix
+ * AND frequency set params_indices[r].
  * lengths1/lengths2: child1/child2 branch length per position. */
 int rdamd_root_loglikelihood_fused(rdamd_partition_t       *p,
                                    const rdamd_operation_t *root_op,

@@ -934,6 +934,10 @@ int rdamd_root_loglikelihood_fused(rdamd_partition_t *p, const rdamd_operation_t
     std::fill(lnl_out, lnl_out + n_alpha, 0.0);
     return RDAMD_SUCCESS;
   }
+  if (bad_rate_index(p, params_indices)) {   // (ahead of the fallback: its refusal would name another call)
+    set_error(7, "rdamd_root_loglikelihood_fused: params index out of range");
+    return RDAMD_FAILURE;
+  }
   if (!fast_root_shape(p, *root_op)) {
     // generic shapes: the three calls queued back to back on the partition stream
     for (unsigned a = 0; a < n_alpha; ++a) {
@@ -951,10 +955,6 @@ int rdamd_root_loglikelihood_fused(rdamd_partition_t *p, const rdamd_operation_t
   }
   if (!op_in_range(p, *root_op)) {
     set_error(10, "rdamd_root_loglikelihood_fused: index out of range");
-    return RDAMD_FAILURE;
-  }
-  if (bad_rate_index(p, params_indices)) {
-    set_error(7, "rdamd_root_loglikelihood_fused: params index out of range");
     return RDAMD_FAILURE;
   }
   rdamd_operation_t phys_root;

@@ -120,5 +120,34 @@ def find_root(tree, near_tips, far_tips, alpha):
     raise KeyError("no root location matches the golden split")
 
 
+def odd_cells(rng, seqs, odd, share=0.2):
+    """the same sequences with about `share` of the cells replaced by a character of `odd` (gaps,
+    ambiguity codes); no column ends up without a single plain character"""
+    names = list(seqs)
+    cells = np.array([list(seqs[k]) for k in names])
+    hit = rng.random(cells.shape) < share
+    hit[rng.integers(len(names), size=cells.shape[1]), np.arange(cells.shape[1])] = False
+    cells[hit] = rng.choice(list(odd), size=int(hit.sum()))
+    return {k: "".join(row) for k, row in zip(names, cells)}
+
+
+def mixture_params(rng, states, rate_matrices):
+    """`rate_matrices` independent (subst, freqs) draws, each as synth.workload draws its one set:
+    exchange rates U(1e-4, 1) (the reference's random_params), frequencies Dirichlet(10, ..., 10)"""
+    subst = [rng.uniform(1e-4, 1.0, states * states - states) for _ in range(rate_matrices)]
+    freqs = [rng.dirichlet(np.ones(states) * 10) for _ in range(rate_matrices)]
+    return subst, freqs
+
+
+def set_mixture(parts, subst, freqs, rates, weights):
+    """parameter set m of every partition := (subst[m], freqs[m]); the categories' rates and weights"""
+    for p in parts:
+        for m, (s, f) in enumerate(zip(subst, freqs)):
+            p.set_subst_params(m, s)
+            p.set_frequencies(m, f)
+        p.set_category_rates(rates)
+        p.set_category_weights(weights)
+
+
 def rel_err(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-300)
