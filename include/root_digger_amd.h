@@ -490,6 +490,10 @@ char *rdamd_tree_newick(const rdamd_tree_t *t, int annotations);
  * labelled N<k> instead of its own label (new here: the tree that goes with the node order of
  * rdamd_marginal_ancestral_nodes; root the tree with rdamd_tree_root_by first); malloc'd */
 char *rdamd_tree_newick_ancestral(const rdamd_tree_t *t, unsigned int n_nodes, const unsigned int *node_clv);
+/* the same string with lengths[n_nodes][2] on the branches: lengths[k][c] above child c of the node
+ * whose CLV is node_clv[k] (rdamd_model_optimize_branch_lengths); inner labels as above; malloc'd */
+char *rdamd_tree_newick_branch_lengths(const rdamd_tree_t *t, unsigned int n_nodes, const unsigned int *node_clv,
+                                       const double *lengths);
 int   rdamd_tree_annotate_branch(rdamd_tree_t *t, const rdamd_root_location_t *rl,
                                  const char *key, const char *value); /* :731 */
 /* annotate_branch(rl, key, left_value, right_value), src/tree.cpp:737-760 */
@@ -983,6 +987,81 @@ int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl,
                           const uint64_t *counts, const double *values, unsigned int *n_nodes,
                           unsigned int *node_clv, int *node_parent, unsigned int *node_children,
                           double *post_out, double *cat_out, double *mean_rate_out);
+
+/* ------------------------------------------------------------------------
+ * Analytic branch-length derivatives and optimised lengths at a chosen root.  NEW relative to the
+ * reference, whose only derivative is the forward difference of compute_dlh (one parameter: the
+ * root's position).
+ *
+ * The tree is rooted as the post-order list `ops` says, under the rules of
+ * rdamd_marginal_ancestral.  Nodes are ordered as rdamd_marginal_ancestral_nodes orders them.
+ * Branch (k, c) is the branch above child c in {0, 1} of node k.  Its length t is what
+ * rdamd_update_prob_matrices was given for that child's matrix index.
+ *
+ * For site s, rate category r with rate rho_r, weight w_r and rate matrix Q_r:
+ *   Q_r   the rate matrix of the set params_indices[r], normalised, as the P-matrix step uses it
+ *   L, P, U and pi are as in the ancestral section above
+ *   t[i] = U_u[i] (P_b L_b)[i]       the parent's outer vector masked by the sibling
+ *   y = P_a L_a,  z = Q_r y,  z2 = Q_r z
+ *   f0(s) = sum_r w_r t.y            the site likelihood, the same on every branch up to the
+ *                                    per-site scaling factors
+ *   f1(s) = sum_r w_r rho_r t.z
+ *   f2(s) = sum_r w_r rho_r^2 t.z2
+ *   d1[k][c] = sum_s weight_s f1/f0                        = d lnL / dt
+ *   d2[k][c] = sum_s weight_s (f2/f0 - (f1/f0)^2)          = d2 lnL / dt2
+ * The 2^256 rule on U and the CLVs' scalers act per site over all rates, so they cancel in f1/f0
+ * and f2/f0.  No scaler is read.  Tip children have branches too.
+ *
+ * Identity: with the root on a branch of length T at ratio alpha,
+ *   d lnL / d alpha = T (d1 of the root child that gets alpha T - d1 of the other).
+ * ---------------------------------------------------------------------- */
+/* d1_out[n_ops][2] and d2_out[n_ops][2] (d2_out may be NULL).  Precondition, as for
+ * rdamd_marginal_ancestral: rdamd_update_prob_matrices with these params_indices and
+ * rdamd_update_clvs on exactly this list; nothing in the partition is written.  One launch of the
+ * pre-order program for the whole list (a (site, rate) pair per lane with 1, 2, 4 or 8 rate
+ * categories, a plain kernel for any other count) and one small launch that adds the partial sums.
+ * The sums over sites are made in one fixed order without floating-point atomics: two calls with
+ * the same inputs return the same bits.  Zero sites: zeros and success.  Refused as there: error 63
+ * for 20-state partitions and RDAMD_ATTRIB_SPARSE_CLVS, error 64 for a list that is not a complete
+ * post-order traversal ending in the root operation, 10 / 7 for indices out of range.  Error 65: a
+ * site's likelihood f0 is 0 or not finite; the message says how many sites, nothing is returned. */
+int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                             const unsigned int *params_indices, const unsigned int *freqs_indices,
+                             double *d1_out, double *d2_out);
+/* device time of the two launches of this thread's last rdamd_branch_derivatives call,
+ * milliseconds between two HIP events (0 after a failed call); for measurements */
+double rdamd_branch_last_ms(void);
+/* The same for one root of a model.  Parameters in the checkpoint's layout exactly as
+ * rdamd_model_ancestral takes them.  Outputs, any of which may be NULL: *n_nodes, node_clv,
+ * node_parent, node_children as there; lengths_out[n][2]: the schedule's current length of branch
+ * (k, c); d1_out[n][2], d2_out[n][2]: summed over partitions in partition order; *lnl_out: the
+ * log-likelihood at that root.  The model's parameters, its rooting and the conditional
+ * likelihoods of that rooting are as before when the call returns.  Refused (error 61) for a model
+ * that sums over a site group. */
+int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t *rl,
+                                   const uint64_t *counts, const double *values, unsigned int *n_nodes,
+                                   unsigned int *node_clv, int *node_parent, unsigned int *node_children,
+                                   double *lengths_out, double *d1_out, double *d2_out, double *lnl_out);
+/* Maximises lnL over all 2n - 2 branch lengths of the tree rooted at rl, in [min_len, max_len], at
+ * fixed model parameters (counts / values as above) and fixed root.  Nothing is applied to the
+ * model or its tree: the lengths are an output (lengths_out[n][2], nodes as above), with d1_out /
+ * d2_out at those lengths; on return the model is bit for bit what it was.  Each evaluation at
+ * lengths x is rdamd_update_prob_matrices on the schedule's matrix indices with x, a materialising
+ * traversal, the root lnL, and rdamd_branch_derivatives per partition.
+ * The method is a projected L-BFGS (memory 8) whose initial metric is the diagonal Newton one:
+ * a branch is free unless it sits at a bound with the gradient pointing out; curvature
+ * c_b = -d2_b where d2_b < 0, else |d1_b| / max(x_b, min_len) (1 where that is 0); it stops with
+ * *converged = 1 when the predicted gain sum_free d1_b^2 / (2 c_b) is below atol, with
+ * *converged = 0 after max_iters iterations or when no step of a backtracking line search
+ * (Armijo, 1e-4, at most 40 halvings) is accepted.  *iterations, *evaluations: counts;
+ * *lnl_before, *lnl_after: lnL at the schedule's lengths and at lengths_out.  Any output may be
+ * NULL.  Refused (error 61) for a model that sums over a site group. */
+int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_location_t *rl,
+                                        const uint64_t *counts, const double *values, double min_len,
+                                        double max_len, double atol, unsigned int max_iters,
+                                        double *lengths_out, double *d1_out, double *d2_out,
+                                        double *lnl_before, double *lnl_after, unsigned int *iterations,
+                                        unsigned int *evaluations, int *converged);
 
 /* Column that draw d (0 <= d < N) of bootstrap replicate b resamples, N < 2^32 columns.
  * Stateless and counter-based (all arithmetic mod 2^64):

@@ -302,6 +302,13 @@ _sig("rdamd_ancestral_last_ms", C.c_double)
 _sig("rdamd_model_partition_shape", C.c_int, _vp, _u, _pu, _pu, _pu)
 _sig("rdamd_model_ancestral", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd, _pd)
 _sig("rdamd_tree_newick_ancestral", _vp, _vp, _u, _pu)
+_sig("rdamd_tree_newick_branch_lengths", _vp, _vp, _u, _pu, _pd)
+_sig("rdamd_branch_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd)
+_sig("rdamd_branch_last_ms", C.c_double)
+_sig("rdamd_model_branch_derivatives", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd,
+     _pd, _pd)
+_sig("rdamd_model_optimize_branch_lengths", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, C.c_double, C.c_double,
+     C.c_double, _u, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pi)
 _sig("rdamd_rell_tests", C.c_int, _pd, _u, _u, _pu, _u, C.c_uint64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _pd)
 _sig("rdamd_rell_last_tests_ms", C.c_double)
 _pu64 = C.POINTER(C.c_uint64)
@@ -573,6 +580,15 @@ class Tree:
         nc = np.ascontiguousarray(node_clv, dtype=np.uint32)
         return _take_string(lib.rdamd_tree_newick_ancestral(self._h, nc.size, _uptr(nc)))
 
+    def newick_branch_lengths(self, node_clv, lengths):
+        """the tree as it is rooted now with lengths[k][c] above child c of the inner node node_clv[k],
+        inner nodes labelled N<k> (rdamd_tree_newick_branch_lengths)"""
+        nc = np.ascontiguousarray(node_clv, dtype=np.uint32)
+        ln = np.ascontiguousarray(lengths, dtype=np.float64)
+        if ln.shape != (nc.size, 2):
+            raise ValueError("lengths must be [len(node_clv)][2]")
+        return _take_string(lib.rdamd_tree_newick_branch_lengths(self._h, nc.size, _uptr(nc), _dptr(ln)))
+
     def annotate_branch(self, rl, key, value, right_value=None):
         right = value if right_value is None else right_value
         if lib.rdamd_tree_annotate_branch_lr(self._h, C.byref(rl), key.encode(),
@@ -768,6 +784,19 @@ class Partition:
         if lib.rdamd_marginal_ancestral(self._h, ops, len(ops), _uptr(fi), _dptr(out)) != 1:
             _fail("marginal_ancestral")
         return out
+
+    def branch_derivatives(self, ops, params_indices=None, freqs_indices=None):
+        """(d1[len(ops)][2], d2[len(ops)][2]): first and second derivative of lnL in the length of the
+        branch above child c of node k, nodes as ancestral_nodes(ops) orders them
+        (rdamd_branch_derivatives).  Call update_prob_matrices and update_clvs on this list first."""
+        ops = _op_array(ops)
+        pi = self.params_indices if params_indices is None else np.ascontiguousarray(params_indices, dtype=np.uint32)
+        fi = pi if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        d1 = np.zeros((len(ops), 2), dtype=np.float64)
+        d2 = np.zeros((len(ops), 2), dtype=np.float64)
+        if lib.rdamd_branch_derivatives(self._h, ops, len(ops), _uptr(pi), _uptr(fi), _dptr(d1), _dptr(d2)) != 1:
+            _fail("branch_derivatives")
+        return d1, d2
 
     def site_rate_posteriors(self, clv_index, scaler_index=SCALE_BUFFER_NONE, freqs_indices=None):
         """(cat[sites][R], mean_rate[sites]): posterior of every rate category and posterior mean rate of
@@ -1094,6 +1123,11 @@ def ancestral_workspace_slots(ops, tips):
 def ancestral_last_ms():
     """device milliseconds of the pre-order launch of this thread's last marginal_ancestral call"""
     return float(lib.rdamd_ancestral_last_ms())
+
+
+def branch_last_ms():
+    """device milliseconds of the launches of this thread's last branch_derivatives call"""
+    return float(lib.rdamd_branch_last_ms())
 
 
 def rell_last_resample_ms():
@@ -1587,6 +1621,48 @@ class Model:
             cuts = np.cumsum([0] + [sh[0] * sh[2] for sh in shapes])
             cat = [cat[cuts[i]:cuts[i + 1]].reshape(sh[0], sh[2]) for i, sh in enumerate(shapes)]
         return clv, parent, children, post, cat, mean
+
+    def branch_derivatives(self, rl, params=None):
+        """Derivatives of lnL in every branch length at root rl (rdamd_model_branch_derivatives) ->
+        (node_clv[n], node_parent[n], node_children[n][2], lengths[n][2], d1[n][2], d2[n][2], lnl):
+        nodes as ancestral_nodes orders them, branch (k, c) above child c of node k, summed over the
+        partitions.  params as Model.ancestral takes them."""
+        n = self._tree.tip_count() - 1
+        clv = np.zeros(n, dtype=np.uint32)
+        parent = np.zeros(n, dtype=np.int32)
+        children = np.zeros((n, 2), dtype=np.uint32)
+        lengths, d1, d2 = (np.zeros((n, 2), dtype=np.float64) for _ in range(3))
+        counts = values = None
+        if params is not None:
+            counts, values = _flatten_params(list(params))
+        nn, lnl = C.c_uint(0), C.c_double(0.0)
+        self._ok(lib.rdamd_model_branch_derivatives(self._h, C.byref(rl),
+                                                    counts.ctypes.data_as(_pu64) if counts is not None else None,
+                                                    _dptr(values) if values is not None else None, C.byref(nn),
+                                                    _uptr(clv), parent.ctypes.data_as(_pi), _uptr(children),
+                                                    _dptr(lengths), _dptr(d1), _dptr(d2), C.byref(lnl)),
+                 "branch_derivatives")
+        assert nn.value == n
+        return clv, parent, children, lengths, d1, d2, lnl.value
+
+    def optimize_branch_lengths(self, rl, params=None, min_len=1e-6, max_len=100.0, atol=1e-8, max_iters=200):
+        """The branch lengths in [min_len, max_len] that maximise lnL at root rl and fixed parameters
+        (rdamd_model_optimize_branch_lengths) -> dict with lengths[n][2], d1, d2 (at those lengths),
+        lnl_before, lnl_after, iterations, evaluations, converged.  Nothing is applied to the model."""
+        n = self._tree.tip_count() - 1
+        lengths, d1, d2 = (np.zeros((n, 2), dtype=np.float64) for _ in range(3))
+        counts = values = None
+        if params is not None:
+            counts, values = _flatten_params(list(params))
+        before, after = C.c_double(0.0), C.c_double(0.0)
+        its, evals, conv = C.c_uint(0), C.c_uint(0), C.c_int(0)
+        self._ok(lib.rdamd_model_optimize_branch_lengths(
+            self._h, C.byref(rl), counts.ctypes.data_as(_pu64) if counts is not None else None,
+            _dptr(values) if values is not None else None, min_len, max_len, atol, max_iters, _dptr(lengths),
+            _dptr(d1), _dptr(d2), C.byref(before), C.byref(after), C.byref(its), C.byref(evals), C.byref(conv)),
+            "optimize_branch_lengths")
+        return {"lengths": lengths, "d1": d1, "d2": d2, "lnl_before": before.value, "lnl_after": after.value,
+                "iterations": its.value, "evaluations": evals.value, "converged": bool(conv.value)}
 
     def partition_second_passes(self, p):
         """batches of the model's own partition p that needed the evaluator's second pass so far"""

@@ -286,6 +286,16 @@ hipError_t launch_outer_program(rdamd_partition *p, const OuterOp *d_prog, unsig
 hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,
                              double *d_mean);
 
+// kernels_brlen.hip: first and second derivatives of lnL in every branch length, over the same program
+// workgroups of the launch (a function of sites and rate categories alone): one partial per workgroup and entry
+unsigned brlen_blocks(const rdamd_partition *p);
+// d_work as launch_outer_program's; d_partials: [brlen_blocks][nops][4]; d_out: [nops][4] = d1, d2 of
+// child 0, d1, d2 of child 1 of program operation k; *d_bad_sites (zeroed by the caller) counts the
+// sites whose likelihood is 0 or not finite
+hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_pidx, const unsigned *d_fidx, double *d_work, double *d_partials,
+                                unsigned *d_bad_sites, double *d_out);
+
 // kernels_root.hip
 // The grid every root reduction is laid out over: one lane per (site, rate) -- the group layout --
 // or per site, in workgroups of 256 lanes, at most 1024 of them (a lane strides beyond that), never 0.

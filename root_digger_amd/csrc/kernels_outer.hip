@@ -20,6 +20,7 @@
 // posterior of an inner child is formed where its outer vector is, its CLV being in registers
 // already.  The partition is only read.
 #include "common.hpp"
+#include "outer_lanes.hpp"
 #include "outer_plan.hpp"
 
 namespace rdamd {
@@ -42,20 +43,6 @@ struct OuterArgs {
   const OuterOp *prog;
   unsigned nops, slots;
 };
-
-// lanes of the wave whose SITE (R adjacent lanes) is small in every rate (kernels_clv.hip)
-template <int R>
-__device__ __forceinline__ bool site_small(bool lane_small, unsigned lane) {
-  constexpr unsigned long long kGroupMask = R == 1 ? ~0ull : R == 2 ? 0x5555555555555555ull
-                                          : R == 4 ? 0x1111111111111111ull : 0x0101010101010101ull;
-  unsigned long long m = __builtin_amdgcn_ballot_w64(lane_small);
-#pragma unroll
-  for (int off = 1; off < R; off <<= 1) m &= m >> off;
-  m &= kGroupMask;
-#pragma unroll
-  for (int off = 1; off < R; off <<= 1) m |= m << off;
-  return ((m >> lane) & 1ull) != 0;
-}
 
 // ---------------------------------------------------------------------------
 // 4-state path (binary data embedded): one lane per (site, rate), R in {1, 2, 4, 8}, tip codes

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <hip/hip_runtime.h>
 #include "common.hpp"
+#include "brlen_opt.hpp"
 #include "checkpoint.hpp"
 #include "lockstep.hpp"
 
@@ -535,6 +536,102 @@ void model_t::ancestral(const root_location_t &rl, const std::vector<partition_p
   }
   saved.restore(*this);
   saved.restore_rooting(*this);
+}
+
+// Branch-length derivatives at one root, and (bounds given) the lengths that maximise lnL there.
+// One evaluation at lengths x: update_pmatrices on the schedule's matrix indices with x, a
+// materialising traversal, the root lnL, and rdamd_branch_derivatives per partition, summed in
+// partition order.  Saves and restores what ancestral does.
+model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                                                  const branch_bounds_t *bounds) {
+  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
+    throw std::invalid_argument("branch_lengths: this model sums over a site group and holds one block of the "
+                                "columns; derivatives of a site-sharded model are not supported");
+  const size_t P = _partitions.size();
+  if (params) {
+    if (params->size() != P) throw std::invalid_argument("branch_lengths: a parameter set needs one entry per partition");
+    for (size_t p = 0; p < P; ++p) {
+      const auto &pp = (*params)[p];
+      const size_t K = rdamd_partition_states(_partitions[p]);
+      if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
+          (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
+        throw std::invalid_argument("branch_lengths: the parameters do not fit partition " + std::to_string(p));
+    }
+  }
+  if (bounds && !(bounds->min_len > 0.0 && bounds->min_len < bounds->max_len && std::isfinite(bounds->max_len) &&
+                  bounds->atol > 0.0))
+    throw std::invalid_argument("branch_lengths: 0 < min_len < max_len < inf and atol > 0 are required");
+  branch_lengths_t out;
+  const saved_parameters_t saved(*this);
+  try {
+    if (params) set_model_params(*params);
+    auto sched = _tree.generate_operations(rl);
+    const auto &ops = std::get<0>(sched);
+    const auto &pmi = std::get<1>(sched);
+    const auto &brl = std::get<2>(sched);
+    const unsigned n_ops = (unsigned)ops.size();
+    out.node_clv.resize(n_ops);
+    out.node_parent.resize(n_ops);
+    out.node_children.resize(2 * (size_t)n_ops);
+    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, out.node_clv.data(), out.node_parent.data(),
+                                       out.node_children.data()) != RDAMD_SUCCESS)
+      fail("marginal_ancestral_nodes");
+    // branch (k, c) -> its place in the schedule's matrix list
+    std::unordered_map<unsigned, size_t> place;
+    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
+    std::vector<size_t> at(2 * (size_t)n_ops);
+    std::vector<double> x(at.size());
+    for (unsigned k = 0; k < n_ops; ++k) {
+      const rdamd_operation_t &o = ops[n_ops - 1 - k];
+      at[2 * k] = place.at(o.child1_matrix_index);
+      at[2 * k + 1] = place.at(o.child2_matrix_index);
+      x[2 * k] = brl[at[2 * k]];
+      x[2 * k + 1] = brl[at[2 * k + 1]];
+    }
+    std::vector<double> lens(brl), part_d1(at.size()), part_d2(at.size());
+    const auto eval = [&](const std::vector<double> &len, double *f, std::vector<double> &g, std::vector<double> &h) {
+      for (size_t b = 0; b < at.size(); ++b) lens[at[b]] = len[b];
+      update_pmatrices(pmi, lens);
+      ++_n_full;
+      std::fill(g.begin(), g.end(), 0.0);
+      std::fill(h.begin(), h.end(), 0.0);
+      double lh = 0.0;
+      for (size_t p = 0; p < P; ++p) {
+        rdamd_partition_t *part = _partitions[p];
+        rdamd_update_clvs(part, ops.data(), n_ops);
+        if (rdamd_errno()) fail("update_clvs");
+        lh += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
+                                               _param_indicies[p].data(), nullptr);
+        if (rdamd_errno()) fail("compute_root_loglikelihood");
+        if (rdamd_branch_derivatives(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
+                                     part_d1.data(), part_d2.data()) != RDAMD_SUCCESS)
+          throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+        for (size_t b = 0; b < at.size(); ++b) { g[b] += part_d1[b]; h[b] += part_d2[b]; }
+      }
+      *f = lh;
+    };
+    if (bounds) {
+      rdamd::BrlenOptResult r = rdamd::optimize_branch_lengths(x, bounds->min_len, bounds->max_len, bounds->atol,
+                                                               bounds->max_iters, eval);
+      out.lengths = std::move(r.x); out.d1 = std::move(r.g); out.d2 = std::move(r.h);
+      out.lnl_before = r.f_before; out.lnl_after = r.f_after;
+      out.iterations = r.iterations; out.evaluations = r.evaluations; out.converged = r.converged;
+    } else {
+      out.d1.resize(x.size());
+      out.d2.resize(x.size());
+      eval(x, &out.lnl_before, out.d1, out.d2);
+      out.lnl_after = out.lnl_before;
+      out.lengths = x;
+      out.evaluations = 1;
+    }
+  } catch (...) {
+    saved.restore(*this);
+    saved.restore_rooting(*this);
+    throw;
+  }
+  saved.restore(*this);
+  saved.restore_rooting(*this);
+  return out;
 }
 
 // compute_lh for the searches, between optimize_params and the root-only steps: the same

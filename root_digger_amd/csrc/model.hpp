@@ -148,6 +148,24 @@ public:
                  std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
                  std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate);
 
+  // First and second derivatives of lnL in every branch length at one root, and the lengths that
+  // maximise lnL there (include/root_digger_amd.h, rdamd_model_branch_derivatives /
+  // rdamd_model_optimize_branch_lengths; the method: brlen_opt.hpp).  Nodes as ancestral orders them,
+  // branch (k, c) above child c of node k.  Nothing is applied to the model or its tree; saves and
+  // restores like site_lnls.
+  struct branch_lengths_t {
+    std::vector<unsigned> node_clv, node_children;
+    std::vector<int> node_parent;
+    std::vector<double> lengths, d1, d2;   // [nodes][2]
+    double lnl_before = 0.0, lnl_after = 0.0;
+    unsigned iterations = 0, evaluations = 0;
+    bool converged = false;
+  };
+  struct branch_bounds_t { double min_len, max_len, atol; unsigned max_iters; };
+  // bounds == nullptr: the derivatives at the schedule's own lengths (lnl_before = lnl_after)
+  branch_lengths_t branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                                  const branch_bounds_t *bounds);
+
   // batched objective: lnL of (root, parameter set) pairs, all partitions,
   // through rdamd_evaluate_batch (one fused launch per partition)
   std::vector<double> compute_lh_batch(const std::vector<root_location_t> &roots,

@@ -422,6 +422,69 @@ int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl, con
   })
 }
 
+// one root's parameters in the checkpoint's layout (counts[n_partitions][4], values)
+static std::vector<rdamd::partition_parameters_t> one_root_params(const rdamd_model_t *m, const uint64_t *counts,
+                                                                  const double *values) {
+  std::vector<rdamd::partition_parameters_t> params(m->model->partition_count());
+  for (rdamd::partition_parameters_t &pp : params)
+    for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
+      v->assign(values, values + *counts);
+      values += *counts++;
+    }
+  return params;
+}
+static void copy_branch_result(const rdamd::model_t::branch_lengths_t &r, unsigned int *n_nodes, unsigned int *node_clv,
+                               int *node_parent, unsigned int *node_children, double *lengths_out, double *d1_out,
+                               double *d2_out) {
+  if (n_nodes) *n_nodes = (unsigned)r.node_clv.size();
+  if (node_clv) std::copy(r.node_clv.begin(), r.node_clv.end(), node_clv);
+  if (node_parent) std::copy(r.node_parent.begin(), r.node_parent.end(), node_parent);
+  if (node_children) std::copy(r.node_children.begin(), r.node_children.end(), node_children);
+  if (lengths_out) std::copy(r.lengths.begin(), r.lengths.end(), lengths_out);
+  if (d1_out) std::copy(r.d1.begin(), r.d1.end(), d1_out);
+  if (d2_out) std::copy(r.d2.begin(), r.d2.end(), d2_out);
+}
+int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                                   const double *values, unsigned int *n_nodes, unsigned int *node_clv,
+                                   int *node_parent, unsigned int *node_children, double *lengths_out,
+                                   double *d1_out, double *d2_out, double *lnl_out) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_branch_derivatives")) return RDAMD_FAILURE;
+    if ((counts == nullptr) != (values == nullptr))
+      throw std::invalid_argument("rdamd_model_branch_derivatives: counts and values come together");
+    if (!rl) throw std::invalid_argument("rdamd_model_branch_derivatives: null argument");
+    std::vector<rdamd::partition_parameters_t> params;
+    if (counts) params = one_root_params(m, counts, values);
+    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params : nullptr, nullptr);
+    copy_branch_result(r, n_nodes, node_clv, node_parent, node_children, lengths_out, d1_out, d2_out);
+    if (lnl_out) *lnl_out = r.lnl_before;
+    return RDAMD_SUCCESS;
+  })
+}
+int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                                        const double *values, double min_len, double max_len, double atol,
+                                        unsigned int max_iters, double *lengths_out, double *d1_out, double *d2_out,
+                                        double *lnl_before, double *lnl_after, unsigned int *iterations,
+                                        unsigned int *evaluations, int *converged) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_optimize_branch_lengths")) return RDAMD_FAILURE;
+    if ((counts == nullptr) != (values == nullptr))
+      throw std::invalid_argument("rdamd_model_optimize_branch_lengths: counts and values come together");
+    if (!rl) throw std::invalid_argument("rdamd_model_optimize_branch_lengths: null argument");
+    std::vector<rdamd::partition_parameters_t> params;
+    if (counts) params = one_root_params(m, counts, values);
+    const rdamd::model_t::branch_bounds_t bounds{min_len, max_len, atol, max_iters};
+    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params : nullptr, &bounds);
+    copy_branch_result(r, nullptr, nullptr, nullptr, nullptr, lengths_out, d1_out, d2_out);
+    if (lnl_before) *lnl_before = r.lnl_before;
+    if (lnl_after) *lnl_after = r.lnl_after;
+    if (iterations) *iterations = r.iterations;
+    if (evaluations) *evaluations = r.evaluations;
+    if (converged) *converged = r.converged ? 1 : 0;
+    return RDAMD_SUCCESS;
+  })
+}
+
 namespace {
 void fill_model(const rdamd::model_info_t &mi, rdamd_partition_info_t *out) {
   std::snprintf(out->subst_str, sizeof out->subst_str, "%s", mi.subst_str.c_str());

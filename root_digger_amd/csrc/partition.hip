@@ -1162,6 +1162,92 @@ unsigned int rdamd_marginal_ancestral_workspace_slots(const rdamd_operation_t *o
   return plan.slots;
 }
 
+// ---- branch-length derivatives (kernels_brlen.hip) ----------------------------------------------
+namespace {
+thread_local double g_branch_ms = 0.0;
+}
+double rdamd_branch_last_ms(void) { return g_branch_ms; }
+
+int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                             const unsigned int *params_indices, const unsigned int *freqs_indices,
+                             double *d1_out, double *d2_out) {
+  clear_error();
+  g_branch_ms = 0.0;
+  if (outer_refused(p, "rdamd_branch_derivatives")) return RDAMD_FAILURE;
+  if (!ops || !params_indices || !freqs_indices || !d1_out) {
+    set_error(64, "rdamd_branch_derivatives: null argument");
+    return RDAMD_FAILURE;
+  }
+  for (unsigned i = 0; i < n_ops; ++i)
+    if (!op_in_range(p, ops[i])) {
+      set_error(10, "rdamd_branch_derivatives: operation %u has an index out of range", i);
+      return RDAMD_FAILURE;
+    }
+  const OuterPlan plan = plan_outer_program(ops, n_ops, p->tips);
+  if (plan.bad_op >= 0) {
+    set_error(64, "rdamd_branch_derivatives: not a complete post-order traversal ending in the root operation: "
+                  "operation %d: %s", plan.bad_op, plan.why);
+    return RDAMD_FAILURE;
+  }
+  if (bad_rate_index(p, params_indices)) {
+    set_error(7, "rdamd_branch_derivatives: params index out of range");
+    return RDAMD_FAILURE;
+  }
+  if (bad_rate_index(p, freqs_indices)) {
+    set_error(7, "rdamd_branch_derivatives: freqs index out of range");
+    return RDAMD_FAILURE;
+  }
+  const size_t entries = (size_t)n_ops * 4;
+  std::fill(d1_out, d1_out + 2 * (size_t)n_ops, 0.0);
+  if (d2_out) std::fill(d2_out, d2_out + 2 * (size_t)n_ops, 0.0);
+  if (p->sites == 0) return RDAMD_SUCCESS;
+  const unsigned R = p->rate_cats;
+  const size_t prog_bytes = sizeof(OuterOp) * plan.prog.size();
+  OuterScratch mem;   // (post: the partials, cat: the sums, mean: the count of sites without a likelihood)
+  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(ensure_scratch(p, prog_bytes + 2 * sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.work, std::max<size_t>(8, sizeof(double) * outer_workspace_doubles(p, plan.slots))),
+                RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.post, sizeof(double) * entries * brlen_blocks(p)), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.cat, sizeof(double) * entries), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMalloc(&mem.mean, sizeof(double)), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t0), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t1), RDAMD_FAILURE);
+  Scratch sc{p};
+  OuterOp *d_prog = (OuterOp *)sc.take(prog_bytes);
+  unsigned *d_pi = (unsigned *)sc.take(sizeof(unsigned) * R);
+  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
+  unsigned *d_bad = reinterpret_cast<unsigned *>(mem.mean);
+  RDAMD_HIP_TRY(upload(p, d_prog, plan.prog.data(), prog_bytes), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(upload(p, d_pi, params_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(double), p->stream), RDAMD_FAILURE);
+  p->prof_begin(5);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t0, p->stream), RDAMD_FAILURE);
+  const hipError_t le = launch_brlen_program(p, d_prog, n_ops, plan.slots, d_pi, d_fi, mem.work, mem.post, d_bad, mem.cat);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t1, p->stream), RDAMD_FAILURE);
+  p->prof_end();
+  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
+  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
+  unsigned bad = 0;
+  RDAMD_HIP_TRY(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (bad) {
+    set_error(65, "rdamd_branch_derivatives: %u of %u sites have a likelihood that is 0 or not finite; no derivative "
+                  "is returned", bad, p->sites);
+    return RDAMD_FAILURE;
+  }
+  std::vector<double> sums(entries);
+  RDAMD_HIP_TRY(hipMemcpy(sums.data(), mem.cat, sizeof(double) * entries, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, mem.t0, mem.t1) == hipSuccess) g_branch_ms = ms;
+  for (size_t k = 0; k < n_ops; ++k)
+    for (size_t c = 0; c < 2; ++c) {
+      d1_out[2 * k + c] = sums[4 * k + 2 * c];
+      if (d2_out) d2_out[2 * k + c] = sums[4 * k + 2 * c + 1];
+    }
+  return RDAMD_SUCCESS;
+}
+
 int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int scaler_index,
                                const unsigned int *freqs_indices, double *cat_out, double *mean_rate_out) {
   clear_error();

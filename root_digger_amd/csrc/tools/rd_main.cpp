@@ -37,6 +37,12 @@
 // N0 (the root), N1, ... as in the rows; with --site-rates <prefix>.siterates.tsv, the posterior mean
 // rate and the rate-category posteriors of every column.
 //
+// --branch-lengths [--brlen-min 1e-6] [--brlen-max 100] (new here, with --exhaustive): after the search
+// rank 0 takes the best record's root and parameters from the checkpoint and maximises lnL over all
+// 2n - 2 branch lengths of the tree rooted there (rdamd_model_optimize_branch_lengths; nothing is fed
+// back into the search): <prefix>.brlen.tsv, one row per branch with the input and the optimised length
+// and both derivatives at the optimum; <prefix>.brlen.tree, the rooted tree with the optimised lengths.
+//
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
 #include <chrono>
@@ -75,6 +81,9 @@ struct options_t {
   bool rell_given = false, rell_seed_given = false, site_lh = false, root_tests = false, au = false;
   // what the best root implies: ancestral states (.ancestral.tsv, .ancestral.tree), site rates (.siterates.tsv)
   bool ancestral = false, site_rates = false;
+  // the ML branch lengths at the best root (.brlen.tsv, .brlen.tree) and their box
+  bool branch_lengths = false;
+  double brlen_min = 1e-6, brlen_max = 100.0;
   uint64_t rell_seed = 0;
 };
 
@@ -99,7 +108,9 @@ void usage() {
       "  --root-tests   (with --rell: KH, SH and weighted-SH p-values of every root, <prefix>.roottests.tsv)\n"
       "  --au   (with --rell: AU test of every root from B replicates at each of ten scales, <prefix>.au.tsv)\n"
       "  --ancestral   (with --exhaustive: ancestral state posteriors at the best root, <prefix>.ancestral.tsv / .tree)\n"
-      "  --site-rates   (with --exhaustive: posterior mean rate of every column at the best root, <prefix>.siterates.tsv)");
+      "  --site-rates   (with --exhaustive: posterior mean rate of every column at the best root, <prefix>.siterates.tsv)\n"
+      "  --branch-lengths [--brlen-min <X>] [--brlen-max <X>]   (with --exhaustive: ML branch lengths at the best root,\n"
+      "                <prefix>.brlen.tsv / .tree)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -126,7 +137,8 @@ options_t parse(int argc, char **argv) {
       {"rell", required_argument, 0, 0},         {"rell-seed", required_argument, 0, 0},
       {"site-lh", no_argument, 0, 0},            {"root-tests", no_argument, 0, 0},
       {"au", no_argument, 0, 0},                 {"ancestral", no_argument, 0, 0},
-      {"site-rates", no_argument, 0, 0},
+      {"site-rates", no_argument, 0, 0},         {"branch-lengths", no_argument, 0, 0},
+      {"brlen-min", required_argument, 0, 0},    {"brlen-max", required_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -177,6 +189,9 @@ options_t parse(int argc, char **argv) {
     else if (name == "au") o.au = true;
     else if (name == "ancestral") o.ancestral = true;
     else if (name == "site-rates") o.site_rates = true;
+    else if (name == "branch-lengths") o.branch_lengths = true;
+    else if (name == "brlen-min") o.brlen_min = std::atof(v);
+    else if (name == "brlen-max") o.brlen_max = std::atof(v);
     else if (name == "site-reduce") {
       const std::string s = v;
       if (s != "rccl" && s != "rccl-allreduce" && s != "host") die("--site-reduce takes rccl, rccl-allreduce or host");
@@ -215,13 +230,15 @@ static int run(int argc, char **argv) {
   // the candidates' records and parameters are read back from the checkpoint; a site group's
   // member holds one block of the columns
   const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : o.ancestral ? "--ancestral"
-                            : o.site_rates ? "--site-rates" : nullptr;
+                            : o.site_rates ? "--site-rates" : o.branch_lengths ? "--branch-lengths" : nullptr;
   const bool site_support = o.rell_given || o.site_lh;   // the site lnLs of every candidate are wanted
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
   if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
   if (o.root_tests && o.rell < 2) die("--root-tests: --rell must give at least 2 replicates");
   if (o.au && !o.rell_given) die("--au: the test is made from --rell <B> replicates at every scale");
   if (o.au && o.rell < 2) die("--au: --rell must give at least 2 replicates");
+  if (o.branch_lengths && !(o.brlen_min > 0.0 && o.brlen_min < o.brlen_max && std::isfinite(o.brlen_max)))
+    die("--branch-lengths: 0 < --brlen-min < --brlen-max is required");
   if (support_opt) {
     const std::string opt = support_opt;
     if (o.rell_given && (o.rell < 1 || o.rell > 0x7fffffffl)) die("--rell: the number of replicates must be at least 1");
@@ -651,18 +668,24 @@ static int run(int argc, char **argv) {
       }
     }
   }
-  // ---- what the best root implies: ancestral states and site rates at its own parameters
-  if (o.ancestral || o.site_rates) {
+  // the parameters of the record `best` was taken from, in the checkpoint's layout
+  const auto best_record_params = [&](std::vector<uint64_t> &counts, std::vector<double> &values) {
     unsigned k = 0;
     for (unsigned i = 1; i < n_results; ++i)
-      if (llh[i] > llh[k]) k = i;   // the record `best` was taken from
+      if (llh[i] > llh[k]) k = i;
     uint64_t id = 0, nv = 0;
     double l = 0, a = 0;
     unsigned np = 0;
     need(rdamd_checkpoint_result(ckp, k, &id, &l, &a, &np, &nv), "checkpoint result");
-    std::vector<uint64_t> counts(4 * (size_t)np);
-    std::vector<double> values(nv + 1);
+    counts.assign(4 * (size_t)np, 0);
+    values.assign(nv + 1, 0.0);
     need(rdamd_checkpoint_result_params(ckp, k, counts.data(), values.data()), "checkpoint result_params");
+  };
+  // ---- what the best root implies: ancestral states and site rates at its own parameters
+  if (o.ancestral || o.site_rates) {
+    std::vector<uint64_t> counts;
+    std::vector<double> values;
+    best_record_params(counts, values);
     unsigned P = 0, columns = 0;
     need(rdamd_model_site_patterns(model, &P, &columns, nullptr, nullptr), "site_patterns");
     std::vector<unsigned> pattern_of(columns);
@@ -747,6 +770,58 @@ static int run(int argc, char **argv) {
       files += (files.empty() ? "" : " ") + o.prefix + ".siterates.tsv";
     }
     if (!o.silent) std::cout << "Ancestral reconstruction at root " << best.id << " written to: " << files << std::endl;
+  }
+  // ---- the ML branch lengths at the best root and its own parameters
+  if (o.branch_lengths) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> counts;
+    std::vector<double> values;
+    best_record_params(counts, values);
+    unsigned n_nodes = rdamd_tree_tip_count(tree) - 1;
+    std::vector<unsigned> node_clv(n_nodes), node_children(2 * (size_t)n_nodes);
+    std::vector<double> input(2 * (size_t)n_nodes), lengths(input.size()), d1(input.size()), d2(input.size());
+    need(rdamd_model_branch_derivatives(model, &best, counts.data(), values.data(), &n_nodes, node_clv.data(), nullptr,
+                                        node_children.data(), input.data(), nullptr, nullptr, nullptr),
+         "branch_derivatives");
+    double before = 0.0, after = 0.0;
+    unsigned iterations = 0, evaluations = 0;
+    int converged = 0;
+    need(rdamd_model_optimize_branch_lengths(model, &best, counts.data(), values.data(), o.brlen_min, o.brlen_max, 1e-8,
+                                             200, lengths.data(), d1.data(), d2.data(), &before, &after, &iterations,
+                                             &evaluations, &converged),
+         "optimize_branch_lengths");
+    std::FILE *f = std::fopen((o.prefix + ".brlen.tsv").c_str(), "w");
+    if (!f) die("could not write " + o.prefix + ".brlen.tsv");
+    std::fprintf(f, "node\tchild\tname\tinput_length\tlength\td1\td2\tat_bound\n");
+    for (unsigned v = 0; v < n_nodes; ++v)
+      for (unsigned c = 0; c < 2; ++c) {
+        const size_t b = 2 * (size_t)v + c;
+        std::string name;
+        const auto inner = std::find(node_clv.begin(), node_clv.end(), node_children[b]);
+        if (inner != node_clv.end()) name = "N" + std::to_string(inner - node_clv.begin());
+        else name = rdamd_tree_tip_label(tree, node_children[b]);
+        const char *bound = lengths[b] <= o.brlen_min ? "min" : lengths[b] >= o.brlen_max ? "max" : "no";
+        std::fprintf(f, "N%u\t%u\t%s\t%.10f\t%.10f\t%.6e\t%.6e\t%s\n", v, c, name.c_str(), input[b], lengths[b], d1[b],
+                     d2[b], bound);
+      }
+    std::fclose(f);
+    rdamd_tree_t *rooted = rdamd_tree_from_file(o.tree.c_str());
+    if (!rooted) die(rdamd_errmsg());
+    rdamd_root_location_t rl;
+    need(rdamd_tree_root_location(rooted, (unsigned)best.id, &rl), "root_location");
+    rl.brlen_ratio = best.brlen_ratio;
+    need(rdamd_tree_root_by(rooted, &rl), "root_by");
+    char *nw = rdamd_tree_newick_branch_lengths(rooted, n_nodes, node_clv.data(), lengths.data());
+    if (!nw) die(rdamd_errmsg());
+    std::ofstream(o.prefix + ".brlen.tree") << nw;
+    std::free(nw);
+    rdamd_tree_destroy(rooted);
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    char line[512];
+    std::snprintf(line, sizeof line, "Branch lengths at root %llu: lnL before %.6f, after %.6f, iterations %u, evaluations %u, "
+                  "converged %d, %.3f s; written to: %s.brlen.tsv %s.brlen.tree", (unsigned long long)best.id, before, after,
+                  iterations, evaluations, converged, seconds, o.prefix.c_str(), o.prefix.c_str());
+    std::cout << line << std::endl;
   }
   rdamd_tree_t *out = rdamd_tree_from_file(o.tree.c_str());
   std::string final_tree;

@@ -497,8 +497,23 @@ bool rooted_tree_t::branch_length_sanity_check() const {
 }
 
 // src/tree.cpp:443-492 (label:length with six decimals + NHX annotations)
-std::string rooted_tree_t::newick(bool annotations, const std::unordered_map<unsigned int, std::string> *inner_names) const {
-  // (inner_names: the label of an inner node whose CLV index it holds, instead of the input's own)
+std::string rooted_tree_t::newick(bool annotations, const std::unordered_map<unsigned int, std::string> *inner_names,
+                                  const std::unordered_map<unsigned int, std::pair<double, double>> *child_lengths) const {
+  // (inner_names: the label of an inner node whose CLV index it holds, instead of the input's own;
+  // child_lengths: the lengths above the two children of the node whose CLV index it holds, in the
+  // order of its operation, instead of the tree's own -- ten decimals, they may be near 1e-6)
+  auto length_of = [&](int parent, int ordinal, int n) {
+    char buf[64];
+    if (child_lengths) {
+      const auto it = child_lengths->find(_clv[parent]);
+      if (it != child_lengths->end()) {
+        snprintf(buf, sizeof(buf), "%.10f", ordinal == 0 ? it->second.first : it->second.second);
+        return std::string(buf);
+      }
+    }
+    snprintf(buf, sizeof(buf), "%f", _length[n]);
+    return std::string(buf);
+  };
   auto label = [&](int n) -> const std::string & {
     if (inner_names && _next[n] >= 0) {
       const auto it = inner_names->find(_clv[n]);
@@ -506,10 +521,8 @@ std::string rooted_tree_t::newick(bool annotations, const std::unordered_map<uns
     }
     return _label[n];
   };
-  auto serialize = [&](int n) {
-    char buf[64];
-    snprintf(buf, sizeof(buf), "%f", _length[n]);
-    std::string s = label(n) + ":" + buf;
+  auto serialize = [&](int n, int parent, int ordinal) {
+    std::string s = label(n) + ":" + length_of(parent, ordinal, n);
     if (annotations) {
       auto it = _annotations.find(n);
       if (it != _annotations.end() && !it->second.empty()) {
@@ -520,20 +533,20 @@ std::string rooted_tree_t::newick(bool annotations, const std::unordered_map<uns
     }
     return s;
   };
-  std::function<std::string(int)> sub = [&](int n) -> std::string {
-    if (_next[n] < 0) return serialize(n);
+  std::function<std::string(int, int, int)> sub = [&](int n, int parent, int ordinal) -> std::string {
+    if (_next[n] < 0) return serialize(n, parent, ordinal);
     std::string s = "(";
-    bool first = true;
+    int child = 0;
     for (int k = _next[n]; k != n; k = _next[k]) {
-      if (!first) s += ",";
-      s += sub(_back[k]);
-      first = false;
+      if (child) s += ",";
+      s += sub(_back[k], n, child++);
     }
-    return s + ")" + serialize(n);
+    return s + ")" + serialize(n, parent, ordinal);
   };
   int root = _vroot;
-  std::string s = "(" + sub(_back[root]);
-  for (int k = _next[root]; k != root; k = _next[k]) s += "," + sub(_back[k]);
+  std::string s = "(" + sub(_back[root], root, 0);
+  int child = 1;
+  for (int k = _next[root]; k != root; k = _next[k]) s += "," + sub(_back[k], root, child++);
   return s + ")" + label(root) + ";";
 }
 

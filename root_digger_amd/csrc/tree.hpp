@@ -85,7 +85,8 @@ public:
   // src/tree.cpp:443-492.  inner_names (not in the reference): CLV index -> label of that inner
   // node in this string, instead of the input's own (the tree file of the ancestral states)
   std::string newick(bool annotations = true,
-                     const std::unordered_map<unsigned int, std::string> *inner_names = nullptr) const;
+                     const std::unordered_map<unsigned int, std::string> *inner_names = nullptr,
+                     const std::unordered_map<unsigned int, std::pair<double, double>> *child_lengths = nullptr) const;
   void annotate_branch(const root_location_t &rl, const std::string &key,
                        const std::string &value) { annotate_branch(rl, key, value, value); }
   void annotate_branch(const root_location_t &rl, const std::string &key,

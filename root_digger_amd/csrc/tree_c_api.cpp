@@ -190,6 +190,18 @@ char *rdamd_tree_newick_ancestral(const rdamd_tree_t *t, unsigned int n_nodes, c
     return dup(t->tree.newick(false, &names));
   })
 }
+char *rdamd_tree_newick_branch_lengths(const rdamd_tree_t *t, unsigned int n_nodes, const unsigned int *node_clv,
+                                       const double *lengths) {
+  GUARD({
+    std::unordered_map<unsigned int, std::string> names;
+    std::unordered_map<unsigned int, std::pair<double, double>> child_lengths;
+    for (unsigned k = 0; k < n_nodes; ++k) {
+      names[node_clv[k]] = "N" + std::to_string(k);
+      child_lengths[node_clv[k]] = {lengths[2 * k], lengths[2 * k + 1]};
+    }
+    return dup(t->tree.newick(false, &names, &child_lengths));
+  })
+}
 int rdamd_tree_annotate_branch(rdamd_tree_t *t, const rdamd_root_location_t *rl,
                                const char *key, const char *value) {
   GUARD({ t->tree.annotate_branch(to_cpp(rl), key, value); return RDAMD_SUCCESS; })
