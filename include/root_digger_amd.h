@@ -97,7 +97,13 @@ uint64_t rdamd_partition_clv_bytes(const rdamd_partition_t *p);
 
 /* replaces corax_set_tip_states, src/model.cpp:310.  `map` is a 256-entry
  * char -> state-bitmask table (rdamd_map_nt / rdamd_map_bin or the caller's).
- * Returns RDAMD_FAILURE on a character the map does not know. */
+ * Returns RDAMD_FAILURE on a character the map does not know (error 4; also a mask with bits
+ * beyond the partition's states).  A partition that is not 4-state (or binary) numbers the distinct
+ * masks it is given and holds at most 64 of them, over all its tips and for its whole life: the
+ * sequence that would bring a 65th is refused (error 5).  A refused call (errors 3, 4, 5) leaves the
+ * partition as it was: the tip keeps its sequence, the table its masks, on the host and on the
+ * device, and schedules compiled before stay valid.  (A HIP error while the accepted sequence is
+ * copied to the device leaves the host's copy as it was; the device is then in doubt.) */
 int rdamd_set_tip_states(rdamd_partition_t *p, unsigned int tip_index,
                          const uint64_t *map, const char *sequence);
 /* replaces corax_set_pattern_weights, src/model.cpp:324 */

@@ -178,6 +178,17 @@ hipError_t launch_pmatrix(rdamd_partition *p, const unsigned *d_params_indices,
         count, R, p->d_pmat, p->d_tiptab, p->d_codemask, p->ncodes_cap);
   } else {
     size_t lds = (4 * (size_t)K * K + K) * sizeof(double);
+    {   // 46 states and up pass the 64 KB a kernel may ask for by default (64 states: 131 584 B of the CU's 160 KB)
+      static std::mutex lds_mu;
+      static size_t lds_allowed = 64 * 1024;
+      std::lock_guard<std::mutex> guard(lds_mu);
+      if (lds > lds_allowed) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&pmatrix_generic_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        lds_allowed = lds;
+      }
+    }
     pmatrix_generic_kernel<<<count * R, 256, lds, p->stream>>>(
         p->d_q, p->d_rates, d_params_indices, d_matrix_indices, d_branch_lengths,
         R, K, p->d_pmat, p->d_tiptab, p->d_codemask, p->ncodes_cap, p->mfma_layout ? 1u : 0u);

@@ -14,6 +14,7 @@
 #include "clv_plan.hpp"
 #include "common.hpp"
 #include "outer_plan.hpp"
+#include "tip_encode.hpp"
 
 namespace rdamd {
 
@@ -580,37 +581,35 @@ int rdamd_set_tip_states(rdamd_partition_t *p, unsigned int tip_index,
     return RDAMD_FAILURE;
   }
   const size_t S = p->sites;
-  uint8_t *row = p->tipcodes.data() + (size_t)tip_index * S;
-  const uint64_t full = p->api_states == 64 ? ~0ull : ((1ull << p->api_states) - 1);
-  bool new_code = false;
-  for (size_t s = 0; s < S; ++s) {
-    uint64_t st = map[(unsigned char)sequence[s]];
-    if (!st || (st & ~full)) {
-      set_error(4, "rdamd_set_tip_states: character '%c' (site %zu) has no valid state "
-                   "in the map", sequence[s], s);
-      return RDAMD_FAILURE;
-    }
-    if (p->states == 4) {
-      row[s] = (uint8_t)st;
-    } else {
-      unsigned c = 0;
-      for (; c < p->ncodes; ++c)
-        if (p->codemask[c] == st) break;
-      if (c == p->ncodes) {
-        if (p->ncodes >= p->ncodes_cap) {
-          set_error(5, "rdamd_set_tip_states: more than %u distinct state codes",
-                    p->ncodes_cap);
-          return RDAMD_FAILURE;
-        }
-        p->codemask[p->ncodes++] = st;
-        new_code = true;
-      }
-      row[s] = (uint8_t)c;
-    }
+  // the whole sequence first, against a copy of the code table (tip_encode.hpp): a refused call
+  // leaves host and device as they were
+  rdamd::TipEncoding enc = rdamd::encode_tip_row(map, sequence, S, p->api_states, p->states == 4, p->codemask,
+                                                 p->ncodes, p->ncodes_cap);
+  if (enc.error == 4) {
+    set_error(4, "rdamd_set_tip_states: character '%c' (site %zu) has no valid state "
+                 "in the map", sequence[enc.site], enc.site);
+    return RDAMD_FAILURE;
   }
-  if (new_code) {
-    RDAMD_HIP_TRY(upload(p, p->d_codemask, p->codemask.data(), 256 * sizeof(uint64_t)),
-                  RDAMD_FAILURE);
+  if (enc.error == 5) {
+    set_error(5, "rdamd_set_tip_states: more than %u distinct state codes",
+              p->ncodes_cap);
+    return RDAMD_FAILURE;
+  }
+  // the device first, from the temporaries: should a copy fail, the host keeps the old sequence and
+  // the old table (device entries past ncodes are not read, and the next new mask overwrites them)
+  if (enc.new_code)
+    RDAMD_HIP_TRY(upload(p, p->d_codemask, enc.codemask.data(), 256 * sizeof(uint64_t)), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(upload(p, p->d_tipcodes + (size_t)tip_index * p->tip_stride(), enc.row.data(), S), RDAMD_FAILURE);
+  if (p->d_tipcodes16) {   // the same row as LDS row offsets (kernels_fused.hip)
+    std::vector<uint8_t> row16(S);
+    for (size_t s = 0; s < S; ++s) row16[s] = (uint8_t)(enc.row[s] << 4);
+    RDAMD_HIP_TRY(upload(p, p->d_tipcodes16 + (size_t)tip_index * p->tip_stride(), row16.data(), S), RDAMD_FAILURE);
+  }
+  // ... then the host, all at once
+  std::copy(enc.row.begin(), enc.row.end(), p->tipcodes.begin() + (size_t)tip_index * S);
+  if (enc.new_code) {
+    p->codemask.swap(enc.codemask);
+    p->ncodes = enc.ncodes;
     p->tiptab_stale = true;
   }
   // class codes of subtrees were worked out from the old characters: forget them (schedules
@@ -629,12 +628,6 @@ int rdamd_set_tip_states(rdamd_partition_t *p, unsigned int tip_index,
     (void)hipFree(p->d_codes_wide);
     p->d_codes_wide = nullptr;
     p->wide_rows = p->wide_rows_cap = 0;
-  }
-  RDAMD_HIP_TRY(upload(p, p->d_tipcodes + (size_t)tip_index * p->tip_stride(), row, S), RDAMD_FAILURE);
-  if (p->d_tipcodes16) {   // the same row as LDS row offsets (kernels_fused.hip)
-    std::vector<uint8_t> row16(S);
-    for (size_t s = 0; s < S; ++s) row16[s] = (uint8_t)(row[s] << 4);
-    RDAMD_HIP_TRY(upload(p, p->d_tipcodes16 + (size_t)tip_index * p->tip_stride(), row16.data(), S), RDAMD_FAILURE);
   }
   return RDAMD_SUCCESS;
 }

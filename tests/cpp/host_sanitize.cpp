@@ -11,6 +11,7 @@
 #include "checkpoint.hpp"
 #include "model.hpp"
 #include "partition_info.hpp"
+#include "tip_encode.hpp"
 #include "tree.hpp"
 
 // the one symbol these files take from the HIP side of the library
@@ -72,6 +73,32 @@ int main(int argc, char **argv) {
     threw = false;
     try { parse_partition_info(bad); } catch (const std::exception &) { threw = true; }
     CHECK(threw);
+  }
+
+  // ---- tip sequences against the table of state masks (rdamd_set_tip_states' host half)
+  {
+    uint64_t map[256] = {};
+    for (unsigned j = 0; j < 64; ++j) map['0' + j] = 1ull << j;          // '0' .. 'o': the 64 plain states
+    map['~'] = ~0ull;
+    map['|'] = (1ull << 63) | 1;
+    std::vector<uint64_t> table(256, 0);
+    std::string all;
+    for (unsigned j = 0; j < 63; ++j) all.push_back((char)('0' + j));
+    TipEncoding t = encode_tip_row(map, (all + "~").c_str(), 64, 64, false, table, 0, 64);
+    CHECK(t.error == 0 && t.new_code && t.ncodes == 64 && t.row[63] == 63 && t.codemask[63] == ~0ull);
+    CHECK(table[0] == 0);                                                  // the caller's table is a copy's source only
+    TipEncoding full = encode_tip_row(map, (all + "|").c_str(), 64, 64, false, t.codemask, t.ncodes, 64);
+    CHECK(full.error == 5 && full.site == 63);
+    TipEncoding bad = encode_tip_row(map, "01!2", 4, 64, false, t.codemask, t.ncodes, 64);
+    CHECK(bad.error == 4 && bad.site == 2);
+    TipEncoding wide = encode_tip_row(map, "0~", 2, 20, false, table, 0, 64);   // a mask beyond 20 states
+    CHECK(wide.error == 4 && wide.site == 1);
+    TipEncoding cut = encode_tip_row(map, "01", 5, 64, false, table, 0, 64);      // a sequence that ends early
+    CHECK(cut.error == 4 && cut.site == 2);
+    TipEncoding dna = encode_tip_row(nt_map, "ACGTN-", 6, 4, true, table, 16, 16);
+    CHECK(dna.error == 0 && !dna.new_code && dna.row[4] == 15 && dna.ncodes == 16);
+    TipEncoding none = encode_tip_row(map, "", 0, 64, false, table, 0, 64);
+    CHECK(none.error == 0 && none.row.empty());
   }
 
   // ---- checkpoint: write, tear, clean, reread

@@ -1,7 +1,7 @@
 """Pins the CPU oracle (oracle/rd_oracle.c) where a partition holds SEVERAL rate matrices and every
 rate category names its own: params_indices for the P-matrices, freqs_indices -- a different vector --
 for the root frequencies.  The GPU tests of tests/test_gpu_rate_matrices.py take the oracle as their
-reference there, so it is compared first with a restatement written here: Q per matrix as
+reference there, so it is compared first with the restatement of tests/util.py: Q per matrix as
 synth.build_q builds it, scipy.linalg.expm per (branch, category), plain Felsenstein pruning per
 category in NumPy (no rescaling: seven tips) and
     lnL = sum_s w_s log sum_r omega_r pi[fidx[r]] . root[s][r].
@@ -9,40 +9,16 @@ Limits as in tests/test_oracle_golden.py against SciPy: P 1e-13 absolute, lnL 1e
 Runs without a GPU."""
 import numpy as np
 import pytest
-from scipy.linalg import expm
 
 import root_digger_amd as rd
 from root_digger_amd import synth
 from oracle_lib import OraclePartition, ORC_MAP_NT, orc_gamma_cats
 import util
+from util import restated_pmatrices, restated_site_lnls
 
 P_TOL = 1e-13
 TOL = 1e-10          # relative, per-site lnL and the total
 R = 4
-
-
-def restated_pmatrices(subst, freqs, pidx, rates, lengths):
-    """[branch][category][K][K]"""
-    q = [synth.build_q(s, f) for s, f in zip(subst, freqs)]
-    return np.array([[expm(q[pidx[r]] * rates[r] * t) for r in range(len(rates))] for t in lengths])
-
-
-def restated_site_lnls(tree, ops, pmat_of, seqs, cmap, K, freqs, fidx, cat_weights, pattern_weights):
-    """pmat_of: matrix index -> [R][K][K].  -> per-site lnL (pattern weight applied)"""
-    S = len(next(iter(seqs.values())))
-    clv = {}
-    for label, seq in seqs.items():
-        bits = np.array([[(cmap[ord(ch)] >> j) & 1 for j in range(K)] for ch in seq], dtype=np.float64)
-        clv[tree.tip_index(label)] = np.broadcast_to(bits[:, None, :], (S, R, K))
-    for op in ops:
-        a = np.einsum("rij,srj->sri", pmat_of[op.child1_matrix_index], clv[op.child1_clv_index])
-        b = np.einsum("rij,srj->sri", pmat_of[op.child2_matrix_index], clv[op.child2_clv_index])
-        clv[op.parent_clv_index] = a * b
-    root = clv[ops[len(ops) - 1].parent_clv_index]
-    site = np.zeros(S)
-    for r in range(R):
-        site += cat_weights[r] * root[:, r, :] @ np.asarray(freqs[fidx[r]])
-    return pattern_weights * np.log(site)
 
 
 @pytest.mark.parametrize("K,M,pidx,fidx", [(4, 3, [2, 0, 2, 1], [1, 1, 0, 2]),
