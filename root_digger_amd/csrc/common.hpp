@@ -273,23 +273,24 @@ void clv_k20_traversal_cut(const rdamd_partition *p, unsigned count, unsigned *p
 hipError_t launch_clv_k20_traversal(rdamd_partition *p, const LevelOp *d_ops, const ListPieces &pieces);
 size_t k20_mfma_copy_doubles();               // doubles per (matrix, rate) in d_pmat_mfma
 
-// kernels_outer.hip: the pre-order pass (outer vectors, ancestral state and site-rate posteriors)
+// kernels_preorder.hip: the pre-order pass (outer vectors; from them ancestral state posteriors, and the
+// derivatives of lnL in every branch length) and the site-rate posteriors
 struct OuterOp;   // outer_plan.hpp
-// does the one-lane-per-(site, rate) kernel take the partition (else the generic one)?
+// does the one-lane-per-(site, rate) walk take the partition (else the generic one)?
 bool outer_fast_shape(const rdamd_partition *p);
 // doubles of workspace a program with `slots` slots needs on this partition
 size_t outer_workspace_doubles(const rdamd_partition *p, unsigned slots);
-// the whole program in one launch; d_post: [nops][sites][api_states]
+// workgroups of a walk's launch (a function of sites and rate categories alone)
+unsigned preorder_blocks(const rdamd_partition *p);
+// posteriors: the whole program in one launch; d_post: [nops][sites][api_states]
 hipError_t launch_outer_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
                                 const unsigned *d_fidx, double *d_work, double *d_post);
 // d_cat [sites][R] and d_mean [sites] (either may be null) from the CLV in device buffer clv_phys_index
 hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,
                              double *d_mean);
 
-// kernels_brlen.hip: first and second derivatives of lnL in every branch length, over the same program
-// workgroups of the launch (a function of sites and rate categories alone): one partial per workgroup and entry
-unsigned brlen_blocks(const rdamd_partition *p);
-// d_work as launch_outer_program's; d_partials: [brlen_blocks][nops][4]; d_out: [nops][4] = d1, d2 of
+// first and second derivatives of lnL in every branch length, over the same program: d_work as
+// launch_outer_program's; d_partials: [preorder_blocks][nops][4]; d_out: [nops][4] = d1, d2 of
 // child 0, d1, d2 of child 1 of program operation k; *d_bad_sites (zeroed by the caller) counts the
 // sites whose likelihood is 0 or not finite
 hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,

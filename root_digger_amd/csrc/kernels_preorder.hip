@@ -1,0 +1,637 @@
+// The pre-order pass: OUTER vectors, and what two analyses make of them -- marginal ancestral
+// state posteriors, and the first and second derivative of lnL in every branch length.  Also the
+// site-rate posteriors, which need the root CLV alone.
+//
+// New here -- the reference computes no ancestral states and has one derivative, the forward
+// difference of its compute_dlh (src/model.cpp), for the root's position alone; this pass extends
+// the traversal the reference makes with corax_update_clvs by the complementary one.
+// For the tree rooted as the operation list says, site s and rate category r (rate rho_r, weight
+// w_r, rate matrix Q_r):
+//   L_v[i]  the CLV of node v (rdamd_update_clvs; a tip's is its 0/1 code vector)
+//   U_v[j]  P(data outside the subtree of v, state j at v):  U_root = pi, and for an operation with
+//           parent u and children a, b
+//             t[i]   = U_u[i] (P_b L_b)[i]       the parent's outer vector masked by the sibling
+//             U_a[j] = sum_i t[i] P_a[i][j]      (U_b: a and b swapped)
+// with the 2^256 rule of the CLVs on the outer vectors: a site whose
+// entries are below 2^-256 in EVERY rate is multiplied by 2^256.  The rule acts per site over all
+// rates, and so do the CLVs' own scalers: both cancel in everything the consumers form, no count
+// is kept and no scaler is read.
+//
+// The WALK is written once per lane shape (preorder_dna_walk, preorder_generic_walk): the whole
+// program (outer_plan.hpp: the operation list read backwards) in ONE launch.  As in
+// clv_dna_traversal_kernel every dependency is site-local and each lane owns its site for the
+// whole program.  The outer vector of the child whose operation comes next stays in the lane's
+// registers, any other waits in a workspace slot (host-side liveness analysis).  The partition is
+// only read.
+//
+// A CONSUMER is a functor the walk calls at fixed places.  There are two:
+//   posteriors   post[v][s][j] = sum_r w_r U_v[j] L_v[j], normalised over j: the root's from pi
+//                before the loop, an inner child's where its outer vector is formed, its CLV
+//                being in registers already.
+//   derivatives  y = P_a L_a,  z = Q_r y,  z2 = Q_r z
+//                f0 = sum_r w_r t.y   f1 = sum_r w_r rho_r t.z   f2 = sum_r w_r rho_r^2 t.z2
+//                d1[a] = sum_s weight_s f1/f0    d2[a] = sum_s weight_s (f2/f0 - (f1/f0)^2)
+//                for BOTH children of every operation: tip children have branches too.  The sums
+//                over sites are made in one fixed order: inside the wave by a butterfly of
+//                exchanges, the four waves of a workgroup in wave order, one partial per
+//                (workgroup, branch) in a workspace, and a second kernel that adds the partials by
+//                increasing workgroup.  No floating-point atomics; equal inputs give equal bits.
+// A consumer names its arguments (Args), the LDS it wants beside the walk's (Lds; empty: none is
+// allocated) and whether it is told of tip children (kTipBranches) and sums over the workgroup
+// (kBlockSums, generic walk); its hooks are begin, op_begin, branch, (branch_done,) outer, op_end
+// and end, in the order the walk reaches them.
+#include "common.hpp"
+#include "outer_plan.hpp"
+
+namespace rdamd {
+
+namespace {
+
+// what the walk reads and the one thing it writes, the workspace
+struct WalkArgs {
+  const double *clv;          // the partition's inner CLVs, [buffer][site][rate][4]
+  size_t clv_stride;          // doubles per buffer
+  const uint8_t *tipcodes;
+  unsigned tip_stride;
+  const uint64_t *codemask;
+  const double *pmat;         // [matrix][rate][4][4], rows = parent state
+  const double *freqs;        // [rate matrix][4]
+  const unsigned *fidx;       // rate -> frequency set
+  const double *rate_w;
+  unsigned tips, sites;
+  double *work;               // [slots (+ 4, generic walk)][site][rate][4]
+  const OuterOp *prog;
+  unsigned nops, slots;
+};
+
+struct PosteriorArgs {
+  double *post;               // [node][site][api_states]
+  unsigned api_states;
+};
+
+struct DerivativeArgs {
+  const double *q;            // [rate matrix][4][4], normalised
+  const unsigned *pidx;       // rate -> rate matrix
+  const double *rates;
+  const unsigned *pattern_w;
+  double *partials;           // [workgroup][nops][4]: d1, d2 of child 0, d1, d2 of child 1
+  unsigned *bad_sites;        // sites whose likelihood is 0 or not finite
+};
+
+struct NoLds {};
+
+// ---------------------------------------------------------------------------
+// The lane map of the 4-state walk: one lane per (site, rate) pair, the R lanes of a site adjacent
+// in the wave, R in {1, 2, 4, 8}
+// ---------------------------------------------------------------------------
+// a rate's matrix in LDS starts this many doubles after the previous one (kernels_clv.hip)
+constexpr unsigned kRateStride = 18;
+
+// lanes of the wave whose SITE (R adjacent lanes) is small in every rate (kernels_clv.hip)
+template <int R>
+__device__ __forceinline__ bool site_small(bool lane_small, unsigned lane) {
+  constexpr unsigned long long kGroupMask = R == 1 ? ~0ull : R == 2 ? 0x5555555555555555ull
+                                          : R == 4 ? 0x1111111111111111ull : 0x0101010101010101ull;
+  unsigned long long m = __builtin_amdgcn_ballot_w64(lane_small);
+#pragma unroll
+  for (int off = 1; off < R; off <<= 1) m &= m >> off;
+  m &= kGroupMask;
+#pragma unroll
+  for (int off = 1; off < R; off <<= 1) m |= m << off;
+  return ((m >> lane) & 1ull) != 0;
+}
+
+// sum over the R lanes of the site (every lane gets it)
+template <int R>
+__device__ __forceinline__ double rate_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < R; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// sum over the lanes of the wave that hold the same rate (lane % R), in one fixed order (every lane gets it)
+template <int R>
+__device__ __forceinline__ double site_sum(double v) {
+#pragma unroll
+  for (int off = R; off < 64; off <<= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+struct DnaLane {
+  unsigned tid, lane, idx, cidx, s, r;   // cidx: idx clamped, so that every lane takes part in the exchanges
+  bool active;
+  double pi[4], w;
+};
+
+__device__ __forceinline__ void load_clv(const WalkArgs &a, const DnaLane &ln, unsigned clv, double (&x)[4]) {
+  if (clv < a.tips) {   // (16-code alphabet: a tip code is its own state mask)
+    const unsigned code = a.tipcodes[(size_t)clv * a.tip_stride + ln.s];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = (code >> k) & 1u ? 1.0 : 0.0;
+  } else {
+    const double2 *p = reinterpret_cast<const double2 *>(a.clv + (size_t)(clv - a.tips) * a.clv_stride) + (size_t)ln.cidx * 2;
+    const double2 lo = p[0], hi = p[1];
+    x[0] = lo.x; x[1] = lo.y; x[2] = hi.x; x[3] = hi.y;
+  }
+}
+
+// the lane-per-site walk's: any code table, one rate at a time
+__device__ __forceinline__ void load_clv(const WalkArgs &a, unsigned R, unsigned s, unsigned clv, unsigned r, double (&x)[4]) {
+  if (clv < a.tips) {
+    const uint64_t mask = a.codemask[a.tipcodes[(size_t)clv * a.tip_stride + s]];
+    for (int k = 0; k < 4; ++k) x[k] = (mask >> k) & 1u ? 1.0 : 0.0;
+  } else {
+    const double *p = a.clv + (size_t)(clv - a.tips) * a.clv_stride + ((size_t)s * R + r) * 4;
+    for (int k = 0; k < 4; ++k) x[k] = p[k];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// 4-state walk (binary data embedded).  Both children's P-matrices are staged in LDS one operation
+// ahead: thread t fetches one double, one barrier per operation.
+// ---------------------------------------------------------------------------
+template <int R, class Consumer>
+__global__ void __launch_bounds__(256)
+preorder_dna_walk(WalkArgs a, typename Consumer::Args ca) {
+  constexpr unsigned kMatDoubles = 2 * R * 16;   // both children's matrices of one operation: <= 256
+  __shared__ double smat[2][2][R * kRateStride];
+  __shared__ typename Consumer::Lds lds;
+  Consumer con(ca, lds);
+  DnaLane ln;
+  ln.tid = threadIdx.x; ln.lane = ln.tid & 63;
+  const unsigned tid = ln.tid;
+  const unsigned total = a.sites * R;                // < 2^26 (outer_fast_shape)
+  ln.idx = blockIdx.x * 256 + tid;
+  ln.active = ln.idx < total;
+  ln.cidx = ln.active ? ln.idx : total - 1;
+  ln.s = ln.cidx / R; ln.r = ln.cidx % R;
+  const unsigned r = ln.r;
+  const size_t slot_doubles = (size_t)total * 4;
+  {
+    const double *f = a.freqs + (size_t)a.fidx[r] * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ln.pi[k] = f[k];
+  }
+  ln.w = a.rate_w[r];
+
+  const unsigned mc = tid / (R * 16), me = tid % (R * 16);
+  auto mat_fetch = [&](unsigned k) {
+    if (tid >= kMatDoubles || k >= a.nops) return 0.0;
+    return a.pmat[(size_t)a.prog[k].child_mat[mc] * (R * 16) + me];
+  };
+  auto mat_put = [&](unsigned buf, double v) {
+    if (tid < kMatDoubles) smat[buf][mc][(me / 16) * kRateStride + (me % 16)] = v;
+  };
+
+  con.begin(a, ln);
+  mat_put(0, mat_fetch(0));
+  __syncthreads();
+
+  double u[4] = {0, 0, 0, 0};   // the outer vector the next operation reads from registers
+  for (unsigned k = 0; k < a.nops; ++k) {
+    const OuterOp op = a.prog[k];
+    const unsigned buf = k & 1u;
+    const double next_m = mat_fetch(k + 1);
+    con.op_begin(a, ln, k);
+    double up[4];
+    if (op.parent_src == kOuterFromSlot) {
+      const double2 *p = reinterpret_cast<const double2 *>(a.work + (size_t)op.parent_slot * slot_doubles) + (size_t)ln.cidx * 2;
+      const double2 lo = p[0], hi = p[1];
+      up[0] = lo.x; up[1] = lo.y; up[2] = hi.x; up[3] = hi.y;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) up[i] = op.parent_src == kOuterFromPi ? ln.pi[i] : u[i];
+    }
+    double l[2][4], pl[2][4];
+    load_clv(a, ln, op.child_clv[0], l[0]);
+    load_clv(a, ln, op.child_clv[1], l[1]);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const double *m = &smat[buf][c][r * kRateStride];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        pl[c][i] = m[i * 4 + 0] * l[c][0] + m[i * 4 + 1] * l[c][1] + m[i * 4 + 2] * l[c][2] + m[i * 4 + 3] * l[c][3];
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (!op.inner[c] && !Consumer::kTipBranches) continue;   // (wave-uniform)
+      const double *m = &smat[buf][c][r * kRateStride];
+      double t[4], uc[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];   // the parent's vector masked by the sibling
+      con.branch(ln, c, t, pl[c]);
+      if (!op.inner[c]) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) uc[j] = t[0] * m[j] + t[1] * m[4 + j] + t[2] * m[8 + j] + t[3] * m[12 + j];
+      // entries are non-negative: uc < 2^-256 is a comparison of high words
+      const unsigned hmax = max(max((unsigned)__double2hiint(uc[0]), (unsigned)__double2hiint(uc[1])),
+                                max((unsigned)__double2hiint(uc[2]), (unsigned)__double2hiint(uc[3])));
+      if (site_small<R>(hmax < 0x2FF00000u, ln.lane)) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) uc[j] *= kScaleFactor;
+      }
+      con.outer(a, ln, op.node[c], uc, l[c]);
+      if (op.keep[c] == kOuterKeepReg) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) u[j] = uc[j];
+      } else if (op.keep[c] == kOuterKeepSlot && ln.active) {
+        double2 *p = reinterpret_cast<double2 *>(a.work + (size_t)op.slot[c] * slot_doubles) + (size_t)ln.idx * 2;
+        p[0] = make_double2(uc[0], uc[1]);
+        p[1] = make_double2(uc[2], uc[3]);
+      }
+    }
+    con.op_end(ln, k);
+    mat_put(buf ^ 1u, next_m);
+    __syncthreads();
+  }
+  con.end(a, ln);
+}
+
+// ---------------------------------------------------------------------------
+// Generic walk (4 states, any R, any code table): one lane per site, looping over rates.  The
+// same program; what the fast walk keeps in registers lives in four more workspace buffers: two
+// that alternate as "the registers" and one per child for a vector nobody reads later (it is
+// still needed for the second pass: the rescale rule looks at all rates of the site first).
+// Two points the walk settles for both consumers: an idle lane stays to the end, computing
+// nothing, for the barriers of a consumer that sums over the workgroup; and a small site is
+// rescaled by one multiply pass over its stored vector BEFORE the consumer reads it (the factor
+// is a power of two: the product is the same number wherever it is formed).
+// ---------------------------------------------------------------------------
+template <class Consumer>
+__global__ void __launch_bounds__(256)
+preorder_generic_walk(WalkArgs a, typename Consumer::Args ca, unsigned R) {
+  __shared__ typename Consumer::Lds lds;
+  Consumer con(ca, lds);
+  const unsigned S = a.sites;
+  const unsigned tid = threadIdx.x;
+  const unsigned s = blockIdx.x * 256 + tid;
+  const bool active = s < S;
+  const size_t buf_doubles = (size_t)S * R * 4;
+  con.begin(a, R, s, active);
+  for (unsigned k = 0; k < a.nops; ++k) {
+    const OuterOp op = a.prog[k];
+    con.op_begin(a, k, tid);
+    if (active) {
+      const double *src = op.parent_src == kOuterFromSlot ? a.work + (size_t)op.parent_slot * buf_doubles
+                        : op.parent_src == kOuterFromReg ? a.work + (size_t)(a.slots + (k & 1u)) * buf_doubles : nullptr;
+      double *dst[2];
+      for (int c = 0; c < 2; ++c)
+        dst[c] = a.work + (size_t)(op.keep[c] == kOuterKeepSlot ? op.slot[c]
+                                   : op.keep[c] == kOuterKeepReg ? a.slots + ((k + 1) & 1u) : a.slots + 2u + (unsigned)c) * buf_doubles;
+      bool small[2] = {true, true};
+      for (unsigned r = 0; r < R; ++r) {   // (a freed slot may be written by this very operation: read rate r first)
+        const size_t at = ((size_t)s * R + r) * 4;
+        double up[4], l[2][4], pl[2][4];
+        const double *f = src ? src + at : a.freqs + (size_t)a.fidx[r] * 4;
+        for (int i = 0; i < 4; ++i) up[i] = f[i];
+        for (int c = 0; c < 2; ++c) {
+          load_clv(a, R, s, op.child_clv[c], r, l[c]);
+          const double *m = a.pmat + ((size_t)op.child_mat[c] * R + r) * 16;
+          for (int i = 0; i < 4; ++i)
+            pl[c][i] = m[i * 4 + 0] * l[c][0] + m[i * 4 + 1] * l[c][1] + m[i * 4 + 2] * l[c][2] + m[i * 4 + 3] * l[c][3];
+        }
+        for (int c = 0; c < 2; ++c) {
+          if (!op.inner[c] && !Consumer::kTipBranches) continue;
+          double t[4];
+          for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];
+          con.branch(a, c, r, t, pl[c]);
+          if (!op.inner[c]) continue;
+          const double *m = a.pmat + ((size_t)op.child_mat[c] * R + r) * 16;
+          for (int j = 0; j < 4; ++j) {
+            const double uc = t[0] * m[j] + t[1] * m[4 + j] + t[2] * m[8 + j] + t[3] * m[12 + j];
+            dst[c][at + j] = uc;
+            small[c] = small[c] && uc < kScaleThreshold;
+          }
+        }
+      }
+      for (int c = 0; c < 2; ++c) {
+        con.branch_done(c);
+        if (!op.inner[c]) continue;
+        double *uc = dst[c] + (size_t)s * R * 4;
+        if (small[c])
+          for (unsigned e = 0; e < R * 4; ++e) uc[e] *= kScaleFactor;
+        con.outer(a, R, s, op.node[c], op.child_clv[c], uc);
+      }
+    }
+    con.op_end(k, tid);
+    if (Consumer::kBlockSums) __syncthreads();
+  }
+  con.end(a, active, tid);
+}
+
+// ---------------------------------------------------------------------------
+// Consumer: marginal ancestral state posteriors
+// ---------------------------------------------------------------------------
+template <int R>
+struct PosteriorDna {
+  using Args = PosteriorArgs;
+  using Lds = NoLds;
+  static constexpr bool kTipBranches = false;
+  const Args c;
+  __device__ __forceinline__ PosteriorDna(const Args &c, Lds &) : c(c) {}
+
+  __device__ __forceinline__ void write_post(const WalkArgs &a, const DnaLane &ln, unsigned node, const double (&u)[4],
+                                             const double (&l)[4]) const {
+    double q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = rate_sum<R>(ln.w * u[k] * l[k]);
+    const double den = (q[0] + q[1]) + (q[2] + q[3]);
+    if (ln.active && ln.r == 0) {
+      double *o = c.post + ((size_t)node * a.sites + ln.s) * c.api_states;
+      reinterpret_cast<double2 *>(o)[0] = make_double2(q[0] / den, q[1] / den);
+      if (c.api_states == 4) reinterpret_cast<double2 *>(o)[1] = make_double2(q[2] / den, q[3] / den);
+    }
+  }
+  __device__ __forceinline__ void begin(const WalkArgs &a, const DnaLane &ln) const {   // the root: U = pi
+    double l[4];
+    load_clv(a, ln, a.prog[0].parent_clv, l);
+    write_post(a, ln, 0, ln.pi, l);
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &, const DnaLane &, unsigned) const {}
+  __device__ __forceinline__ void branch(const DnaLane &, int, const double (&)[4], const double (&)[4]) const {}
+  __device__ __forceinline__ void outer(const WalkArgs &a, const DnaLane &ln, unsigned node, const double (&uc)[4],
+                                        const double (&l)[4]) const {
+    write_post(a, ln, node, uc, l);
+  }
+  __device__ __forceinline__ void op_end(const DnaLane &, unsigned) const {}
+  __device__ __forceinline__ void end(const WalkArgs &, const DnaLane &) const {}
+};
+
+struct PosteriorGeneric {
+  using Args = PosteriorArgs;
+  using Lds = NoLds;
+  static constexpr bool kTipBranches = false, kBlockSums = false;
+  const Args c;
+  __device__ __forceinline__ PosteriorGeneric(const Args &c, Lds &) : c(c) {}
+
+  __device__ __forceinline__ void write_post(const WalkArgs &a, unsigned s, unsigned node, const double (&q)[4]) const {
+    const double den = (q[0] + q[1]) + (q[2] + q[3]);
+    double *o = c.post + ((size_t)node * a.sites + s) * c.api_states;
+    for (unsigned k = 0; k < c.api_states; ++k) o[k] = q[k] / den;
+  }
+  __device__ __forceinline__ void begin(const WalkArgs &a, unsigned R, unsigned s, bool active) const {
+    if (!active) return;
+    double q[4] = {0, 0, 0, 0}, l[4];
+    for (unsigned r = 0; r < R; ++r) {
+      const double *f = a.freqs + (size_t)a.fidx[r] * 4;
+      load_clv(a, R, s, a.prog[0].parent_clv, r, l);
+      for (int k = 0; k < 4; ++k) q[k] += a.rate_w[r] * f[k] * l[k];
+    }
+    write_post(a, s, 0, q);
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned, unsigned) const {}
+  __device__ __forceinline__ void branch(const WalkArgs &, int, unsigned, const double (&)[4], const double (&)[4]) const {}
+  __device__ __forceinline__ void branch_done(int) const {}
+  // u: the site's outer vector, [rate][4]
+  __device__ __forceinline__ void outer(const WalkArgs &a, unsigned R, unsigned s, unsigned node, unsigned clv,
+                                        const double *u) const {
+    double q[4] = {0, 0, 0, 0}, l[4];
+    for (unsigned r = 0; r < R; ++r) {
+      load_clv(a, R, s, clv, r, l);
+      for (int j = 0; j < 4; ++j) q[j] += a.rate_w[r] * u[r * 4 + j] * l[j];
+    }
+    write_post(a, s, node, q);
+  }
+  __device__ __forceinline__ void op_end(unsigned, unsigned) const {}
+  __device__ __forceinline__ void end(const WalkArgs &, bool, unsigned) const {}
+};
+
+// ---------------------------------------------------------------------------
+// Consumer: first and second derivative of lnL in every branch length
+// ---------------------------------------------------------------------------
+// the two site terms of a branch from the sums over rates; false: the site has no likelihood
+__device__ __forceinline__ bool site_terms(double f0, double f1, double f2, double weight, double *d1, double *d2) {
+  if (!(f0 > 0.0) || !isfinite(f0) || !isfinite(f1) || !isfinite(f2)) { *d1 = 0.0; *d2 = 0.0; return false; }
+  const double g = f1 / f0;
+  *d1 = weight * g;
+  *d2 = weight * (f2 / f0 - g * g);
+  return true;
+}
+
+// The four waves' sums of operation k wait in wsum[k & 1] (written before the operation's barrier)
+// and are added in wave order after it, by the first four threads of the workgroup.
+__device__ __forceinline__ void flush_block_sums(const double (&wsum)[4][4], double *partials, unsigned nops, unsigned k,
+                                                 unsigned tid) {
+  if (tid < 4)
+    partials[((size_t)blockIdx.x * nops + k) * 4 + tid] = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
+}
+
+// Q_r y, Q_r^2 y and the three products with t
+__device__ __forceinline__ void branch_products(const double *qm, const double (&t)[4], const double (&y)[4], double *p0,
+                                                double *p1, double *p2) {
+  double z[4], z2[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) z[i] = qm[i * 4 + 0] * y[0] + qm[i * 4 + 1] * y[1] + qm[i * 4 + 2] * y[2] + qm[i * 4 + 3] * y[3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) z2[i] = qm[i * 4 + 0] * z[0] + qm[i * 4 + 1] * z[1] + qm[i * 4 + 2] * z[2] + qm[i * 4 + 3] * z[3];
+  *p0 = t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3];
+  *p1 = t[0] * z[0] + t[1] * z[1] + t[2] * z[2] + t[3] * z[3];
+  *p2 = t[0] * z2[0] + t[1] * z2[1] + t[2] * z2[2] + t[3] * z2[3];
+}
+
+template <int R>
+struct DerivativeDna {
+  using Args = DerivativeArgs;
+  struct Lds {
+    alignas(16) double sq[R * kRateStride];   // the R rate matrices, staged once (aligned for 128-bit reads)
+    alignas(16) double wsum[2][4][4];
+  };
+  static constexpr bool kTipBranches = true;
+  const Args c;
+  Lds &lds;
+  double w1, w2, weight;
+  double term[4];   // d1, d2 of child 0, d1, d2 of child 1: this site's, this operation's
+  bool site_bad = false;
+  __device__ __forceinline__ DerivativeDna(const Args &c, Lds &lds) : c(c), lds(lds) {}
+
+  __device__ __forceinline__ void begin(const WalkArgs &, const DnaLane &ln) {
+    const double rho = c.rates[ln.r];
+    w1 = ln.w * rho; w2 = w1 * rho;
+    weight = (double)c.pattern_w[ln.s];
+    const unsigned tid = ln.tid;
+    if (tid < R * 16) lds.sq[(tid / 16) * kRateStride + (tid % 16)] = c.q[(size_t)c.pidx[tid / 16] * 16 + (tid % 16)];
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &a, const DnaLane &ln, unsigned k) const {
+    if (k > 0) flush_block_sums(lds.wsum[(k & 1u) ^ 1u], c.partials, a.nops, k - 1, ln.tid);
+  }
+  __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4]) {
+    double p0, p1, p2;
+    branch_products(&lds.sq[ln.r * kRateStride], t, y, &p0, &p1, &p2);
+    const double f0 = rate_sum<R>(ln.w * p0), f1 = rate_sum<R>(w1 * p1), f2 = rate_sum<R>(w2 * p2);
+    if (!site_terms(f0, f1, f2, weight, &term[2 * ch], &term[2 * ch + 1])) site_bad = true;
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, const DnaLane &, unsigned, const double (&)[4],
+                                        const double (&)[4]) const {}
+  // The R lanes of a site hold the same four terms: lane r of the site stands for term r (+ R, ...),
+  // so one butterfly over the sites of the wave sums R terms at once.
+  __device__ __forceinline__ void op_end(const DnaLane &ln, unsigned k) const {
+    constexpr int V = R >= 4 ? 1 : 4 / R;
+    double val[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const unsigned q = ln.r + (unsigned)v * R;
+      const double x = q == 0 ? term[0] : q == 1 ? term[1] : q == 2 ? term[2] : q == 3 ? term[3] : 0.0;
+      val[v] = site_sum<R>(ln.active ? x : 0.0);
+    }
+    if (ln.lane < (R < 4 ? R : 4)) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) lds.wsum[k & 1u][ln.tid >> 6][ln.lane + v * R] = val[v];
+    }
+  }
+  __device__ __forceinline__ void end(const WalkArgs &a, const DnaLane &ln) const {
+    if (a.nops > 0) flush_block_sums(lds.wsum[(a.nops - 1) & 1u], c.partials, a.nops, a.nops - 1, ln.tid);
+    if (ln.active && ln.r == 0 && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
+struct DerivativeGeneric {
+  using Args = DerivativeArgs;
+  struct Lds { alignas(16) double wsum[2][4][4]; };
+  static constexpr bool kTipBranches = true, kBlockSums = true;
+  const Args c;
+  Lds &lds;
+  double weight;
+  double f[2][3];   // f0, f1, f2 of both children, summed over the rates so far
+  double term[4];   // (an idle lane adds zeros)
+  bool site_bad = false;
+  __device__ __forceinline__ DerivativeGeneric(const Args &c, Lds &lds) : c(c), lds(lds) {}
+
+  __device__ __forceinline__ void begin(const WalkArgs &, unsigned, unsigned s, bool active) {
+    weight = active ? (double)c.pattern_w[s] : 0.0;
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &a, unsigned k, unsigned tid) {
+    if (k > 0) flush_block_sums(lds.wsum[(k & 1u) ^ 1u], c.partials, a.nops, k - 1, tid);
+    for (int i = 0; i < 4; ++i) term[i] = 0.0;
+    for (int i = 0; i < 6; ++i) f[i / 3][i % 3] = 0.0;
+  }
+  __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4]) {
+    const double w = a.rate_w[r], rho = c.rates[r];
+    double p0, p1, p2;
+    branch_products(c.q + (size_t)c.pidx[r] * 16, t, y, &p0, &p1, &p2);
+    f[ch][0] += w * p0;
+    f[ch][1] += w * rho * p1;
+    f[ch][2] += w * rho * rho * p2;
+  }
+  __device__ __forceinline__ void branch_done(int ch) {
+    if (!site_terms(f[ch][0], f[ch][1], f[ch][2], weight, &term[2 * ch], &term[2 * ch + 1])) site_bad = true;
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, unsigned, unsigned, unsigned, unsigned, const double *) const {}
+  __device__ __forceinline__ void op_end(unsigned k, unsigned tid) const {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double v = site_sum<1>(term[q]);
+      if ((tid & 63) == 0) lds.wsum[k & 1u][tid >> 6][q] = v;
+    }
+  }
+  __device__ __forceinline__ void end(const WalkArgs &a, bool active, unsigned tid) const {
+    if (a.nops > 0) flush_block_sums(lds.wsum[(a.nops - 1) & 1u], c.partials, a.nops, a.nops - 1, tid);
+    if (active && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
+// out[e] = the partials of entry e (operation, term) added by increasing workgroup
+__global__ void __launch_bounds__(256)
+brlen_sum_kernel(const double *__restrict__ partials, unsigned blocks, unsigned entries, double *__restrict__ out) {
+  const unsigned e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= entries) return;
+  double acc = 0.0;
+  for (unsigned b = 0; b < blocks; ++b) acc += partials[(size_t)b * entries + e];
+  out[e] = acc;
+}
+
+// posterior of every rate category and the posterior mean rate of every site, from the root CLV
+// (any state count; one lane per site).  Per-site scalers cancel in the normalisation.
+__global__ void __launch_bounds__(256)
+site_rates_kernel(const double *__restrict__ clv, const double *__restrict__ freqs, const unsigned *__restrict__ fidx,
+                  const double *__restrict__ rate_w, const double *__restrict__ rates, unsigned S, unsigned R,
+                  unsigned K, double *__restrict__ cat, double *__restrict__ mean) {
+  const unsigned s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= S) return;
+  auto term = [&](unsigned r) {
+    const double *c = clv + ((size_t)s * R + r) * K, *f = freqs + (size_t)fidx[r] * K;
+    double t = 0.0;
+    for (unsigned i = 0; i < K; ++i) t += f[i] * c[i];
+    return rate_w[r] * t;
+  };
+  double den = 0.0, m = 0.0;
+  for (unsigned r = 0; r < R; ++r) den += term(r);
+  for (unsigned r = 0; r < R; ++r) {
+    const double pr = term(r) / den;
+    if (cat) cat[(size_t)s * R + r] = pr;
+    m += pr * rates[r];
+  }
+  if (mean) mean[s] = m;
+}
+
+// one walk over the partition for a consumer pair (the fast walk's and the generic walk's)
+template <template <int> class Dna, class Generic>
+hipError_t launch_walk(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots, const unsigned *d_fidx,
+                       double *d_work, const typename Generic::Args &ca) {
+  WalkArgs a;
+  a.clv = p->d_clv; a.clv_stride = p->clv_doubles();
+  a.tipcodes = p->d_tipcodes; a.tip_stride = p->tip_stride(); a.codemask = p->d_codemask;
+  a.pmat = p->d_pmat; a.freqs = p->d_freqs; a.fidx = d_fidx; a.rate_w = p->d_rate_weights;
+  a.tips = p->tips; a.sites = p->sites;
+  a.work = d_work; a.prog = d_prog; a.nops = nops; a.slots = slots;
+  const unsigned R = p->rate_cats, grid = preorder_blocks(p);
+  if (!outer_fast_shape(p)) {
+    preorder_generic_walk<Generic><<<grid, 256, 0, p->stream>>>(a, ca, R);
+  } else {
+    switch (R) {
+      case 1: preorder_dna_walk<1, Dna<1>><<<grid, 256, 0, p->stream>>>(a, ca); break;
+      case 2: preorder_dna_walk<2, Dna<2>><<<grid, 256, 0, p->stream>>>(a, ca); break;
+      case 4: preorder_dna_walk<4, Dna<4>><<<grid, 256, 0, p->stream>>>(a, ca); break;
+      default: preorder_dna_walk<8, Dna<8>><<<grid, 256, 0, p->stream>>>(a, ca); break;
+    }
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// the shapes preorder_dna_walk takes (kernels_clv.hip's dna_fast_ok: 32-bit lane indices, one CLV under 2 GB)
+bool outer_fast_shape(const rdamd_partition *p) {
+  const unsigned R = p->rate_cats;
+  return p->states == 4 && p->ncodes_cap == 16 && (R == 1 || R == 2 || R == 4 || R == 8) &&
+         (size_t)p->sites * R < ((size_t)1 << 26);
+}
+
+size_t outer_workspace_doubles(const rdamd_partition *p, unsigned slots) {
+  const size_t buffers = outer_fast_shape(p) ? slots : (size_t)slots + 4;
+  return buffers * p->sites * p->rate_cats * 4;
+}
+
+unsigned preorder_blocks(const rdamd_partition *p) {
+  const size_t lanes = outer_fast_shape(p) ? (size_t)p->sites * p->rate_cats : (size_t)p->sites;
+  return (unsigned)((lanes + 255) / 256);
+}
+
+hipError_t launch_outer_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_fidx, double *d_work, double *d_post) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const PosteriorArgs ca{d_post, p->api_states};
+  return launch_walk<PosteriorDna, PosteriorGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca);
+}
+
+hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_pidx, const unsigned *d_fidx, double *d_work, double *d_partials,
+                                unsigned *d_bad_sites, double *d_out) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const DerivativeArgs ca{p->d_q, d_pidx, p->d_rates, p->d_pattern_weights, d_partials, d_bad_sites};
+  const hipError_t e = launch_walk<DerivativeDna, DerivativeGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca);
+  if (e != hipSuccess) return e;
+  const unsigned entries = nops * 4;
+  brlen_sum_kernel<<<(entries + 255) / 256, 256, 0, p->stream>>>(d_partials, preorder_blocks(p), entries, d_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,
+                             double *d_mean) {
+  if (p->sites == 0) return hipSuccess;
+  const double *clv = p->d_clv + (size_t)(clv_phys_index - p->tips) * p->clv_doubles();
+  site_rates_kernel<<<(p->sites + 255) / 256, 256, 0, p->stream>>>(clv, p->d_freqs, d_fidx, p->d_rate_weights, p->d_rates,
+                                                                    p->sites, p->rate_cats, p->states, d_cat, d_mean);
+  return hipGetLastError();
+}
+
+}  // namespace rdamd

@@ -413,41 +413,70 @@ struct model_t::saved_parameters_t {
   }
 };
 
+// The analyses at a root (site_lnls, ancestral, branch_lengths) need every column on this rank.
+void model_t::refuse_site_group(const char *who, const char *unsupported) const {
+  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
+    throw std::invalid_argument(std::string(who) + ": this model sums over a site group and holds one block of the "
+                                "columns; " + unsupported);
+}
+
+// A parameter set has one entry per partition and each entry fits its partition; `which` names the
+// set in the message ("" or " of root i").
+void model_t::require_fit(const std::vector<partition_parameters_t> &set, const char *who, const std::string &which) const {
+  const size_t P = _partitions.size();
+  if (set.size() != P) throw std::invalid_argument(std::string(who) + ": a parameter set needs one entry per partition");
+  for (size_t p = 0; p < P; ++p) {
+    const auto &pp = set[p];
+    const size_t K = rdamd_partition_states(_partitions[p]);
+    if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
+        (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
+      throw std::invalid_argument(std::string(who) + ": the parameters" + which + " do not fit partition " + std::to_string(p));
+  }
+}
+
+// Runs body and puts back the parameters, the rooting and the CLVs of that rooting, whether body
+// returns or throws; restore_more (what else the caller changed) runs before them.  Not a
+// destructor's work: restore_rooting runs compute_lh, which can throw.
+template <class Restore, class Body>
+void model_t::with_saved_parameters(bool rooting_back_on_failure, Restore restore_more, Body body) {
+  const saved_parameters_t saved(*this);
+  try {
+    body();
+  } catch (...) {
+    restore_more();
+    saved.restore(*this);
+    if (rooting_back_on_failure) saved.restore_rooting(*this);
+    throw;
+  }
+  restore_more();
+  saved.restore(*this);
+  saved.restore_rooting(*this);
+}
+
 // The path compute_lh takes, with the root kernel's per-site output switched on.  That output is
 // weight x lnL; the partitions carry unit weights for the duration of the call (exact, and a
 // pattern of weight 0 keeps its lnL), so the rows are unweighted.
 void model_t::site_lnls(const std::vector<root_location_t> &rls,
                         const std::vector<std::vector<partition_parameters_t>> *params, double *out) {
-  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
-    throw std::invalid_argument("site_lnls: this model sums over a site group and holds one block of the "
-                                "columns; per-site output of a site-sharded model is not supported");
+  refuse_site_group("site_lnls", "per-site output of a site-sharded model is not supported");
   if (params && params->size() != rls.size())
     throw std::invalid_argument("site_lnls: one parameter set per root is required");
   const size_t P = _partitions.size(), total = pattern_count();
-  const saved_parameters_t saved_params(*this);
+  // two things the other analyses do not do: the pattern weights are saved and put back as well,
+  // and a failure leaves the rooting where it stopped (only the parameters go back)
   std::vector<std::vector<unsigned>> saved_weights(P);
   for (size_t p = 0; p < P; ++p) saved_weights[p] = _partitions[p]->pattern_weights;
-  const auto restore = [&] {
+  const auto restore_weights = [&] {
     for (size_t p = 0; p < P; ++p) rdamd_set_pattern_weights(_partitions[p], saved_weights[p].data());
-    saved_params.restore(*this);
   };
-  try {
+  with_saved_parameters(false, restore_weights, [&] {
     for (size_t p = 0; p < P; ++p) {
       const std::vector<unsigned> ones(rdamd_partition_sites(_partitions[p]), 1u);
       if (!ones.empty()) rdamd_set_pattern_weights(_partitions[p], ones.data());
     }
     for (size_t i = 0; i < rls.size(); ++i) {
       if (params) {
-        if ((*params)[i].size() != P)
-          throw std::invalid_argument("site_lnls: a parameter set needs one entry per partition");
-        for (size_t p = 0; p < P; ++p) {
-          const auto &pp = (*params)[i][p];
-          const size_t K = rdamd_partition_states(_partitions[p]);
-          if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
-              (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
-            throw std::invalid_argument("site_lnls: the parameters of root " + std::to_string(i) +
-                                        " do not fit partition " + std::to_string(p));
-        }
+        require_fit((*params)[i], "site_lnls", " of root " + std::to_string(i));
         set_model_params((*params)[i]);
       }
       auto sched = _tree.generate_operations(rls[i]);
@@ -465,12 +494,7 @@ void model_t::site_lnls(const std::vector<root_location_t> &rls,
         row += rdamd_partition_sites(_partitions[p]);
       }
     }
-  } catch (...) {
-    restore();
-    throw;
-  }
-  restore();
-  saved_params.restore_rooting(*this);
+  });
 }
 
 // Marginal ancestral states and site rates at one root: compute_lh's traversal, then the pre-order
@@ -479,22 +503,10 @@ void model_t::site_lnls(const std::vector<root_location_t> &rls,
 void model_t::ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                         std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
                         std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate) {
-  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
-    throw std::invalid_argument("ancestral: this model sums over a site group and holds one block of the "
-                                "columns; per-site output of a site-sharded model is not supported");
+  refuse_site_group("ancestral", "per-site output of a site-sharded model is not supported");
   const size_t P = _partitions.size(), total = pattern_count();
-  if (params) {
-    if (params->size() != P) throw std::invalid_argument("ancestral: a parameter set needs one entry per partition");
-    for (size_t p = 0; p < P; ++p) {
-      const auto &pp = (*params)[p];
-      const size_t K = rdamd_partition_states(_partitions[p]);
-      if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
-          (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
-        throw std::invalid_argument("ancestral: the parameters do not fit partition " + std::to_string(p));
-    }
-  }
-  const saved_parameters_t saved(*this);
-  try {
+  if (params) require_fit(*params, "ancestral", "");
+  with_saved_parameters(true, [] {}, [&] {
     if (params) set_model_params(*params);
     auto sched = _tree.generate_operations(rl);
     const auto &ops = std::get<0>(sched);
@@ -529,13 +541,7 @@ void model_t::ancestral(const root_location_t &rl, const std::vector<partition_p
       if (cat) cat += sites * R;
       at += sites;
     }
-  } catch (...) {
-    saved.restore(*this);
-    saved.restore_rooting(*this);
-    throw;
-  }
-  saved.restore(*this);
-  saved.restore_rooting(*this);
+  });
 }
 
 // Branch-length derivatives at one root, and (bounds given) the lengths that maximise lnL there.
@@ -544,26 +550,14 @@ void model_t::ancestral(const root_location_t &rl, const std::vector<partition_p
 // partition order.  Saves and restores what ancestral does.
 model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                                                   const branch_bounds_t *bounds) {
-  if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
-    throw std::invalid_argument("branch_lengths: this model sums over a site group and holds one block of the "
-                                "columns; derivatives of a site-sharded model are not supported");
+  refuse_site_group("branch_lengths", "derivatives of a site-sharded model are not supported");
   const size_t P = _partitions.size();
-  if (params) {
-    if (params->size() != P) throw std::invalid_argument("branch_lengths: a parameter set needs one entry per partition");
-    for (size_t p = 0; p < P; ++p) {
-      const auto &pp = (*params)[p];
-      const size_t K = rdamd_partition_states(_partitions[p]);
-      if (pp.subst_rates.size() != K * K - K || pp.freqs.size() != K || pp.gamma_alpha.empty() ||
-          (_rate_category_types[p] == rate_category::FREE && pp.gamma_weights.size() != _rate_rates[p].size()))
-        throw std::invalid_argument("branch_lengths: the parameters do not fit partition " + std::to_string(p));
-    }
-  }
+  if (params) require_fit(*params, "branch_lengths", "");
   if (bounds && !(bounds->min_len > 0.0 && bounds->min_len < bounds->max_len && std::isfinite(bounds->max_len) &&
                   bounds->atol > 0.0))
     throw std::invalid_argument("branch_lengths: 0 < min_len < max_len < inf and atol > 0 are required");
   branch_lengths_t out;
-  const saved_parameters_t saved(*this);
-  try {
+  with_saved_parameters(true, [] {}, [&] {
     if (params) set_model_params(*params);
     auto sched = _tree.generate_operations(rl);
     const auto &ops = std::get<0>(sched);
@@ -624,13 +618,7 @@ model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, con
       out.lengths = x;
       out.evaluations = 1;
     }
-  } catch (...) {
-    saved.restore(*this);
-    saved.restore_rooting(*this);
-    throw;
-  }
-  saved.restore(*this);
-  saved.restore_rooting(*this);
+  });
   return out;
 }
 

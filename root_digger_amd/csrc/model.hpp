@@ -315,7 +315,12 @@ public:
   rdamd_partition_t   *partition(size_t i) { return _partitions[i]; }
 
 private:
-  struct saved_parameters_t;   // model.cpp: what site_lnls and ancestral put back
+  // model.cpp: what the analyses at a root (site_lnls, ancestral, branch_lengths) share
+  struct saved_parameters_t;   // what they put back
+  void refuse_site_group(const char *who, const char *unsupported) const;
+  void require_fit(const std::vector<partition_parameters_t> &set, const char *who, const std::string &which) const;
+  template <class Restore, class Body>
+  void with_saved_parameters(bool rooting_back_on_failure, Restore restore_more, Body body);
   std::pair<root_location_t, double> brents(root_location_t beg, dlh_t d_beg,
                                             root_location_t end, dlh_t d_end, double atol);
   void set_tip_states(size_t p, const msa_t &msa);   // :302-325

@@ -424,6 +424,103 @@ static bool set_defaults(rdamd_partition *p) {
   return true;
 }
 #undef TRY
+
+// ---- the pre-order pass's call frame (kernels_preorder.hip) -----------------------------------
+// device memory of one call, given back however the call ends
+template <class T>
+struct DeviceArray {
+  T *d = nullptr;
+  ~DeviceArray() { if (d) (void)hipFree(d); }
+  hipError_t alloc(size_t n) { return hipMalloc(&d, sizeof(T) * n); }
+};
+
+// the shapes the pre-order pass does not take; says so and returns true
+static bool outer_refused(const rdamd_partition *p, const char *what) {
+  if (p->states != 4 || p->mfma_layout) {
+    set_error(63, "%s: %u-state partitions are not supported (ancestral states are computed for 4-state and binary data)",
+              what, p->api_states);
+    return true;
+  }
+  if (p->sparse) {
+    set_error(63, "%s: partitions with RDAMD_ATTRIB_SPARSE_CLVS are not supported (the pass reads every inner CLV of a "
+                  "materialising traversal)", what);
+    return true;
+  }
+  return false;
+}
+
+// What rdamd_marginal_ancestral and rdamd_branch_derivatives share, in two steps: preorder_admitted,
+// then preorder_run.  (RateIndices: a per-rate-category index vector of the caller and its name.)
+struct RateIndices { const unsigned *host; const char *name; };
+
+// the refusals and the plan; false: refused, the error set in the name of entry point `what`
+static bool preorder_admitted(const rdamd_partition *p, const char *what, const rdamd_operation_t *ops, unsigned n_ops,
+                              bool null_argument, std::initializer_list<RateIndices> indices, OuterPlan *plan) {
+  if (outer_refused(p, what)) return false;
+  if (null_argument) {
+    set_error(64, "%s: null argument", what);
+    return false;
+  }
+  for (unsigned i = 0; i < n_ops; ++i)
+    if (!op_in_range(p, ops[i])) {
+      set_error(10, "%s: operation %u has an index out of range", what, i);
+      return false;
+    }
+  *plan = plan_outer_program(ops, n_ops, p->tips);
+  if (plan->bad_op >= 0) {
+    set_error(64, "%s: not a complete post-order traversal ending in the root operation: operation %d: %s", what,
+              plan->bad_op, plan->why);
+    return false;
+  }
+  for (const RateIndices &v : indices)
+    if (bad_rate_index(p, v.host)) {
+      set_error(7, "%s: %s index out of range", what, v.name);
+      return false;
+    }
+  return true;
+}
+
+// Allocates the workspace, has the entry point allocate its result buffers (allocate()), uploads
+// the program and the index vectors and runs launch(d_prog, d_indices (in the caller's order),
+// d_work) between two events on the main stream; *ms: the time between them.  Returns when the
+// stream has drained.
+template <class Allocate, class Launch>
+static int preorder_run(rdamd_partition *p, const OuterPlan &plan, std::initializer_list<RateIndices> indices, double *ms,
+                        Allocate allocate, Launch launch) {
+  struct Frame {
+    DeviceArray<double> work;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    ~Frame() { for (hipEvent_t e : {t0, t1}) if (e) (void)hipEventDestroy(e); }
+  } mem;
+  const unsigned R = p->rate_cats;
+  const size_t prog_bytes = sizeof(OuterOp) * plan.prog.size();
+  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(ensure_scratch(p, prog_bytes + indices.size() * sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(mem.work.alloc(std::max<size_t>(1, outer_workspace_doubles(p, plan.slots))), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(allocate(), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t0), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipEventCreate(&mem.t1), RDAMD_FAILURE);
+  Scratch sc{p};
+  OuterOp *d_prog = (OuterOp *)sc.take(prog_bytes);
+  unsigned *d_indices[2] = {nullptr, nullptr};   // (no entry point has more)
+  RDAMD_HIP_TRY(upload(p, d_prog, plan.prog.data(), prog_bytes), RDAMD_FAILURE);
+  size_t n = 0;
+  for (const RateIndices &v : indices) {
+    d_indices[n] = (unsigned *)sc.take(sizeof(unsigned) * R);
+    RDAMD_HIP_TRY(upload(p, d_indices[n++], v.host, sizeof(unsigned) * R), RDAMD_FAILURE);
+  }
+  p->prof_begin(5);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t0, p->stream), RDAMD_FAILURE);
+  const hipError_t le = launch(d_prog, d_indices, mem.work.d);
+  RDAMD_HIP_TRY(hipEventRecord(mem.t1, p->stream), RDAMD_FAILURE);
+  p->prof_end();
+  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
+  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
+  float elapsed = 0.f;
+  if (hipEventElapsedTime(&elapsed, mem.t0, mem.t1) == hipSuccess) *ms = elapsed;
+  return RDAMD_SUCCESS;
+}
+
 }  // namespace rdamd
 
 extern "C" {
@@ -1035,21 +1132,8 @@ int rdamd_root_loglikelihood_fused_multi(unsigned int n_items, rdamd_partition_t
   return RDAMD_SUCCESS;
 }
 
-// ---- marginal ancestral states and site rates (kernels_outer.hip) ---------------------------
-namespace {
-thread_local double g_ancestral_ms = 0.0;
-// device memory and events of one call, given back however the call ends
-struct OuterScratch {
-  double *work = nullptr, *post = nullptr, *cat = nullptr, *mean = nullptr;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  ~OuterScratch() {
-    for (double *d : {work, post, cat, mean})
-      if (d) (void)hipFree(d);
-    if (t0) (void)hipEventDestroy(t0);
-    if (t1) (void)hipEventDestroy(t1);
-  }
-};
-}  // namespace
+// ---- the pre-order pass (kernels_preorder.hip): marginal ancestral states, branch-length derivatives, site rates ----
+static thread_local double g_ancestral_ms = 0.0, g_branch_ms = 0.0;   // what the last call of each pass took
 
 double rdamd_ancestral_last_ms(void) { return g_ancestral_ms; }
 
@@ -1076,72 +1160,23 @@ int rdamd_marginal_ancestral_nodes(const rdamd_operation_t *ops, unsigned int n_
   return RDAMD_SUCCESS;
 }
 
-// the shapes the pre-order pass does not take; says so and returns true
-static bool outer_refused(const rdamd_partition *p, const char *what) {
-  if (p->states != 4 || p->mfma_layout) {
-    set_error(63, "%s: %u-state partitions are not supported (ancestral states are computed for 4-state and binary data)",
-              what, p->api_states);
-    return true;
-  }
-  if (p->sparse) {
-    set_error(63, "%s: partitions with RDAMD_ATTRIB_SPARSE_CLVS are not supported (the pass reads every inner CLV of a "
-                  "materialising traversal)", what);
-    return true;
-  }
-  return false;
-}
-
 int rdamd_marginal_ancestral(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
                              const unsigned int *freqs_indices, double *post_out) {
   clear_error();
   g_ancestral_ms = 0.0;
-  if (outer_refused(p, "rdamd_marginal_ancestral")) return RDAMD_FAILURE;
-  if (!ops || !freqs_indices || !post_out) {
-    set_error(64, "rdamd_marginal_ancestral: null argument");
+  const std::initializer_list<RateIndices> indices = {{freqs_indices, "freqs"}};
+  OuterPlan plan;
+  if (!preorder_admitted(p, "rdamd_marginal_ancestral", ops, n_ops, !ops || !freqs_indices || !post_out, indices, &plan))
     return RDAMD_FAILURE;
-  }
-  for (unsigned i = 0; i < n_ops; ++i)
-    if (!op_in_range(p, ops[i])) {
-      set_error(10, "rdamd_marginal_ancestral: operation %u has an index out of range", i);
-      return RDAMD_FAILURE;
-    }
-  const OuterPlan plan = plan_outer_program(ops, n_ops, p->tips);
-  if (plan.bad_op >= 0) {
-    set_error(64, "rdamd_marginal_ancestral: not a complete post-order traversal ending in the root operation: "
-                  "operation %d: %s", plan.bad_op, plan.why);
-    return RDAMD_FAILURE;
-  }
-  if (bad_rate_index(p, freqs_indices)) {
-    set_error(7, "rdamd_marginal_ancestral: freqs index out of range");
-    return RDAMD_FAILURE;
-  }
   if (p->sites == 0) return RDAMD_SUCCESS;
-  const unsigned R = p->rate_cats;
-  const size_t prog_bytes = sizeof(OuterOp) * plan.prog.size();
   const size_t post_doubles = (size_t)n_ops * p->sites * p->api_states;
-  OuterScratch mem;
-  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(ensure_scratch(p, prog_bytes + sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.work, std::max<size_t>(8, sizeof(double) * outer_workspace_doubles(p, plan.slots))),
-                RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.post, sizeof(double) * post_doubles), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&mem.t0), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&mem.t1), RDAMD_FAILURE);
-  Scratch sc{p};
-  OuterOp *d_prog = (OuterOp *)sc.take(prog_bytes);
-  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
-  RDAMD_HIP_TRY(upload(p, d_prog, plan.prog.data(), prog_bytes), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
-  p->prof_begin(5);
-  RDAMD_HIP_TRY(hipEventRecord(mem.t0, p->stream), RDAMD_FAILURE);
-  const hipError_t le = launch_outer_program(p, d_prog, n_ops, plan.slots, d_fi, mem.work, mem.post);
-  RDAMD_HIP_TRY(hipEventRecord(mem.t1, p->stream), RDAMD_FAILURE);
-  p->prof_end();
-  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
-  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, mem.t0, mem.t1) == hipSuccess) g_ancestral_ms = ms;
-  RDAMD_HIP_TRY(hipMemcpy(post_out, mem.post, sizeof(double) * post_doubles, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  DeviceArray<double> post;
+  const auto allocate = [&] { return post.alloc(post_doubles); };
+  const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    return launch_outer_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_work, post.d);
+  };
+  if (preorder_run(p, plan, indices, &g_ancestral_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
+  RDAMD_HIP_TRY(hipMemcpy(post_out, post.d, sizeof(double) * post_doubles, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 
@@ -1155,10 +1190,6 @@ unsigned int rdamd_marginal_ancestral_workspace_slots(const rdamd_operation_t *o
   return plan.slots;
 }
 
-// ---- branch-length derivatives (kernels_brlen.hip) ----------------------------------------------
-namespace {
-thread_local double g_branch_ms = 0.0;
-}
 double rdamd_branch_last_ms(void) { return g_branch_ms; }
 
 int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
@@ -1166,77 +1197,43 @@ int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops,
                              double *d1_out, double *d2_out) {
   clear_error();
   g_branch_ms = 0.0;
-  if (outer_refused(p, "rdamd_branch_derivatives")) return RDAMD_FAILURE;
-  if (!ops || !params_indices || !freqs_indices || !d1_out) {
-    set_error(64, "rdamd_branch_derivatives: null argument");
+  const std::initializer_list<RateIndices> indices = {{params_indices, "params"}, {freqs_indices, "freqs"}};
+  OuterPlan plan;
+  if (!preorder_admitted(p, "rdamd_branch_derivatives", ops, n_ops, !ops || !params_indices || !freqs_indices || !d1_out,
+                         indices, &plan))
     return RDAMD_FAILURE;
-  }
-  for (unsigned i = 0; i < n_ops; ++i)
-    if (!op_in_range(p, ops[i])) {
-      set_error(10, "rdamd_branch_derivatives: operation %u has an index out of range", i);
-      return RDAMD_FAILURE;
-    }
-  const OuterPlan plan = plan_outer_program(ops, n_ops, p->tips);
-  if (plan.bad_op >= 0) {
-    set_error(64, "rdamd_branch_derivatives: not a complete post-order traversal ending in the root operation: "
-                  "operation %d: %s", plan.bad_op, plan.why);
-    return RDAMD_FAILURE;
-  }
-  if (bad_rate_index(p, params_indices)) {
-    set_error(7, "rdamd_branch_derivatives: params index out of range");
-    return RDAMD_FAILURE;
-  }
-  if (bad_rate_index(p, freqs_indices)) {
-    set_error(7, "rdamd_branch_derivatives: freqs index out of range");
-    return RDAMD_FAILURE;
-  }
   const size_t entries = (size_t)n_ops * 4;
   std::fill(d1_out, d1_out + 2 * (size_t)n_ops, 0.0);
   if (d2_out) std::fill(d2_out, d2_out + 2 * (size_t)n_ops, 0.0);
   if (p->sites == 0) return RDAMD_SUCCESS;
-  const unsigned R = p->rate_cats;
-  const size_t prog_bytes = sizeof(OuterOp) * plan.prog.size();
-  OuterScratch mem;   // (post: the partials, cat: the sums, mean: the count of sites without a likelihood)
-  RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(ensure_scratch(p, prog_bytes + 2 * sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.work, std::max<size_t>(8, sizeof(double) * outer_workspace_doubles(p, plan.slots))),
-                RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.post, sizeof(double) * entries * brlen_blocks(p)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.cat, sizeof(double) * entries), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMalloc(&mem.mean, sizeof(double)), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&mem.t0), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipEventCreate(&mem.t1), RDAMD_FAILURE);
-  Scratch sc{p};
-  OuterOp *d_prog = (OuterOp *)sc.take(prog_bytes);
-  unsigned *d_pi = (unsigned *)sc.take(sizeof(unsigned) * R);
-  unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
-  unsigned *d_bad = reinterpret_cast<unsigned *>(mem.mean);
-  RDAMD_HIP_TRY(upload(p, d_prog, plan.prog.data(), prog_bytes), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(upload(p, d_pi, params_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
-  RDAMD_HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(double), p->stream), RDAMD_FAILURE);
-  p->prof_begin(5);
-  RDAMD_HIP_TRY(hipEventRecord(mem.t0, p->stream), RDAMD_FAILURE);
-  const hipError_t le = launch_brlen_program(p, d_prog, n_ops, plan.slots, d_pi, d_fi, mem.work, mem.post, d_bad, mem.cat);
-  RDAMD_HIP_TRY(hipEventRecord(mem.t1, p->stream), RDAMD_FAILURE);
-  p->prof_end();
-  RDAMD_HIP_TRY(le, RDAMD_FAILURE);
-  RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
+  DeviceArray<double> partials, sums;   // [workgroup][entry] and [entry]
+  DeviceArray<unsigned> bad_sites;      // the count of sites without a likelihood
+  const auto allocate = [&] {
+    hipError_t e = partials.alloc(entries * preorder_blocks(p));
+    if (e == hipSuccess) e = sums.alloc(entries);
+    if (e == hipSuccess) e = bad_sites.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(bad_sites.d, 0, sizeof(unsigned), p->stream);
+    return e;
+  };
+  const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    return launch_brlen_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_indices[1], d_work, partials.d, bad_sites.d,
+                                sums.d);
+  };
+  if (preorder_run(p, plan, indices, &g_branch_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
   unsigned bad = 0;
-  RDAMD_HIP_TRY(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  RDAMD_HIP_TRY(hipMemcpy(&bad, bad_sites.d, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   if (bad) {
+    g_branch_ms = 0.0;   // (a call that returns nothing reports no time)
     set_error(65, "rdamd_branch_derivatives: %u of %u sites have a likelihood that is 0 or not finite; no derivative "
                   "is returned", bad, p->sites);
     return RDAMD_FAILURE;
   }
-  std::vector<double> sums(entries);
-  RDAMD_HIP_TRY(hipMemcpy(sums.data(), mem.cat, sizeof(double) * entries, hipMemcpyDeviceToHost), RDAMD_FAILURE);
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, mem.t0, mem.t1) == hipSuccess) g_branch_ms = ms;
+  std::vector<double> host(entries);
+  RDAMD_HIP_TRY(hipMemcpy(host.data(), sums.d, sizeof(double) * entries, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   for (size_t k = 0; k < n_ops; ++k)
     for (size_t c = 0; c < 2; ++c) {
-      d1_out[2 * k + c] = sums[4 * k + 2 * c];
-      if (d2_out) d2_out[2 * k + c] = sums[4 * k + 2 * c + 1];
+      d1_out[2 * k + c] = host[4 * k + 2 * c];
+      if (d2_out) d2_out[2 * k + c] = host[4 * k + 2 * c + 1];
     }
   return RDAMD_SUCCESS;
 }
@@ -1259,23 +1256,23 @@ int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int
   }
   if (p->sites == 0 || (!cat_out && !mean_rate_out)) return RDAMD_SUCCESS;
   const size_t S = p->sites, R = p->rate_cats;
-  OuterScratch mem;
+  DeviceArray<double> cat, mean;
   RDAMD_HIP_TRY(clv_phys(p, clv_index, &clv_index), RDAMD_FAILURE);
   RDAMD_HIP_TRY(flush_q(p), RDAMD_FAILURE);
   RDAMD_HIP_TRY(ensure_scratch(p, sizeof(unsigned) * R + 1024), RDAMD_FAILURE);
-  if (cat_out) RDAMD_HIP_TRY(hipMalloc(&mem.cat, sizeof(double) * S * R), RDAMD_FAILURE);
-  if (mean_rate_out) RDAMD_HIP_TRY(hipMalloc(&mem.mean, sizeof(double) * S), RDAMD_FAILURE);
+  if (cat_out) RDAMD_HIP_TRY(cat.alloc(S * R), RDAMD_FAILURE);
+  if (mean_rate_out) RDAMD_HIP_TRY(mean.alloc(S), RDAMD_FAILURE);
   Scratch sc{p};
   unsigned *d_fi = (unsigned *)sc.take(sizeof(unsigned) * R);
   RDAMD_HIP_TRY(upload(p, d_fi, freqs_indices, sizeof(unsigned) * R), RDAMD_FAILURE);
   p->prof_begin(5);
-  const hipError_t le = launch_site_rates(p, clv_index, d_fi, mem.cat, mem.mean);
+  const hipError_t le = launch_site_rates(p, clv_index, d_fi, cat.d, mean.d);
   p->prof_end();
   RDAMD_HIP_TRY(le, RDAMD_FAILURE);
   RDAMD_HIP_TRY(sync_main(p), RDAMD_FAILURE);
-  if (cat_out) RDAMD_HIP_TRY(hipMemcpy(cat_out, mem.cat, sizeof(double) * S * R, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (cat_out) RDAMD_HIP_TRY(hipMemcpy(cat_out, cat.d, sizeof(double) * S * R, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   if (mean_rate_out)
-    RDAMD_HIP_TRY(hipMemcpy(mean_rate_out, mem.mean, sizeof(double) * S, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+    RDAMD_HIP_TRY(hipMemcpy(mean_rate_out, mean.d, sizeof(double) * S, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 

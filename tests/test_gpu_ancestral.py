@@ -1,6 +1,6 @@
-"""Marginal ancestral states and site rates at a chosen root: the pre-order pass of
-csrc/kernels_outer.hip through rdamd_marginal_ancestral / rdamd_site_rate_posteriors,
-Model.ancestral and `rd_amd --ancestral --site-rates`.
+"""Marginal ancestral states and site rates at a chosen root: the pre-order walk of
+csrc/kernels_preorder.hip with its posterior consumer, through rdamd_marginal_ancestral /
+rdamd_site_rate_posteriors, Model.ancestral and `rd_amd --ancestral --site-rates`.
 
 The restatements are NumPy, in this file: an exact enumeration over all assignments of the inner
 nodes (no pruning recursion at all), and the recursion of include/root_digger_amd.h (inner CLVs up,
@@ -199,10 +199,17 @@ def thirty_three():
     return newick, random_columns(rng, labels, 67, "ACGT", "RYN-")
 
 
-@pytest.mark.parametrize("R", [1, 2, 4, 8, 3])
-@pytest.mark.parametrize("S", [1, 15, 67])
-def test_shapes_around_the_lane_map(thirty_three, S, R):
-    newick, all_seqs = thirty_three
+@pytest.fixture(scope="module")
+def thirty_three_wide(thirty_three):
+    """the same tree with 300 columns: two workgroups of the lane-per-site walk"""
+    labels = ["t%04d" % i for i in range(33)]
+    return thirty_three[0], random_columns(np.random.default_rng(300), labels, 300, "ACGT", "RYN-")
+
+
+# (300, 3): the generic walk in two workgroups, the second with 44 live lanes, parents from slots
+@pytest.mark.parametrize("S,R", [(S, R) for S in (1, 15, 67) for R in (1, 2, 4, 8, 3)] + [(300, 3)])
+def test_shapes_around_the_lane_map(thirty_three, thirty_three_wide, S, R):
+    newick, all_seqs = thirty_three if S <= 67 else thirty_three_wide
     tree = rd.Tree.from_newick(newick)
     seqs = {l: s[:S] for l, s in all_seqs.items()}
     rng = np.random.default_rng(1000 * S + R)
@@ -228,6 +235,16 @@ def test_shapes_around_the_lane_map(thirty_three, S, R):
     assert np.abs(cat - want_cat).max() < 1e-12 and np.abs(mean - want_mean).max() < 1e-12
 
 
+def test_two_calls_give_equal_bytes(thirty_three):
+    newick, seqs = thirty_three
+    tree = rd.Tree.from_newick(newick)
+    p, _, _, _ = make_partition(tree, seqs, rd.MAP_NT, 4, 4, np.random.default_rng(4))
+    ops = traverse(p, tree, tree.root_location(17).with_ratio(0.6))
+    a = p.marginal_ancestral(ops)
+    b = p.marginal_ancestral(ops)
+    assert a.shape == (32, 67, 4) and a.tobytes() == b.tobytes()
+
+
 # ---- 3. depth -------------------------------------------------------------------------------
 def caterpillar(n, deep_first, rng):
     """an n-tip caterpillar; the deep child is child 1 (deep_first) or child 2 of every spine node"""
@@ -242,14 +259,16 @@ def caterpillar(n, deep_first, rng):
     return "(%s:%s,t%d:%s,t%d:%s);" % (spine, length(), n - 1, length(), n, length()), ["t%d" % i for i in range(n + 1)]
 
 
-@pytest.mark.parametrize("deep_first", [True, False])
-def test_deep_tree_needs_and_gets_the_rescale_rule(deep_first):
+# (R = 3: the generic walk under the rule)
+@pytest.mark.parametrize("deep_first,R", [pytest.param(True, 2, id="True"), pytest.param(False, 2, id="False"),
+                                          pytest.param(True, 3, id="True-R3"), pytest.param(False, 3, id="False-R3")])
+def test_deep_tree_needs_and_gets_the_rescale_rule(deep_first, R):
     rng = np.random.default_rng(800 + deep_first)
     newick, labels = caterpillar(799, deep_first, rng)
     tree = rd.Tree.from_newick(newick)
     assert tree.tip_count() == 800
     seqs = {l: "".join(rng.choice(list("ACGT"), size=8)) for l in labels}
-    p, pi, rates, w = make_partition(tree, seqs, rd.MAP_NT, 4, 2, rng)
+    p, pi, rates, w = make_partition(tree, seqs, rd.MAP_NT, 4, R, rng)
     # root on the branch of the last tip: the whole spine hangs below one child
     rl = tree.root_location("t799").with_ratio(0.5)
     ops = traverse(p, tree, rl)
@@ -263,7 +282,7 @@ def test_deep_tree_needs_and_gets_the_rescale_rule(deep_first):
     assert np.all(root_plain == 0.0)
     want, _, _ = recursion(ops, 800, tipvec, pmat, pi, w, normalise=True)
     assert np.all(np.isfinite(post))
-    print("deep child first %s: largest difference %.3e" % (deep_first, np.abs(post - want).max()))
+    print("deep child first %s, R %d: largest difference %.3e" % (deep_first, R, np.abs(post - want).max()))
     assert np.abs(post - want).max() < 5e-11
     assert np.abs(post.sum(axis=2) - 1).max() < 1e-13
 

@@ -1,5 +1,5 @@
-"""Analytic branch-length derivatives and optimised lengths at a chosen root: csrc/kernels_brlen.hip
-through rdamd_branch_derivatives, Model.branch_derivatives, Model.optimize_branch_lengths and
+"""Analytic branch-length derivatives and optimised lengths at a chosen root: the pre-order walk of
+csrc/kernels_preorder.hip with its derivative consumer, through rdamd_branch_derivatives, Model.branch_derivatives, Model.optimize_branch_lengths and
 `rd_amd --branch-lengths`.
 
 The restatement is tests/brlen_ref.py (NumPy, every vector renormalised per site).  Device sums are
@@ -128,7 +128,9 @@ def thirty_three():
     return newick, random_columns(rng, labels, 2100, "ACGT", "RYN-")
 
 
-@pytest.mark.parametrize("S,R", [(1, 4), (15, 4), (16, 4), (17, 4), (63, 4), (64, 4), (65, 4), (300, 4), (2100, 8)])
+# (300, 3): the generic walk in two workgroups, the second with 44 live lanes; (1, 3): one live lane
+@pytest.mark.parametrize("S,R", [(1, 4), (15, 4), (16, 4), (17, 4), (63, 4), (64, 4), (65, 4), (300, 4), (2100, 8),
+                                 (300, 3), (1, 3)])
 def test_lane_map_and_both_stages_of_the_sum(thirty_three, S, R):
     newick, all_seqs = thirty_three
     tree = rd.Tree.from_newick(newick)
@@ -143,20 +145,22 @@ def test_lane_map_and_both_stages_of_the_sum(thirty_three, S, R):
 
 
 # ---- 3. depth ---------------------------------------------------------------------------------
-@pytest.mark.parametrize("deep_first", [True, False])
-def test_deep_tree_under_the_rescale_rule(deep_first):
+# (R = 3: the generic walk under the rule)
+@pytest.mark.parametrize("deep_first,R", [pytest.param(True, 4, id="True"), pytest.param(False, 4, id="False"),
+                                          pytest.param(True, 3, id="True-R3"), pytest.param(False, 3, id="False-R3")])
+def test_deep_tree_under_the_rescale_rule(deep_first, R):
     rng = np.random.default_rng(800 + deep_first)
     newick, labels = caterpillar(799, deep_first, rng)
     tree = rd.Tree.from_newick(newick)
     assert tree.tip_count() == 800
     seqs = {l: "".join(rng.choice(list("ACGT"), size=8)) for l in labels}
-    p, subst, freqs, rates, w, weights = make_partition(tree, seqs, rd.MAP_NT, 4, 4, rng)
+    p, subst, freqs, rates, w, weights = make_partition(tree, seqs, rd.MAP_NT, 4, R, rng)
     ops = traverse(p, tree, tree.root_location("t799").with_ratio(0.5))
     assert len(ops) == 799
     # the rule fires: some column of the root CLV carries a scaler
     assert p.get_scaler(tree.root_scaler_index()).max() > 0
     got = p.branch_derivatives(ops)
-    assert_close("deep child first %s" % deep_first, got,
+    assert_close("deep child first %s R %d" % (deep_first, R), got,
                  restate(p, tree, ops, seqs, rd.MAP_NT, 4, subst, freqs, rates, w, weights))
 
 
