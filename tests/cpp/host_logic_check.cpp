@@ -16,6 +16,9 @@
 //     source names a value that is really there (tip, the registers of the operation(s) in front,
 //     an LDS parking slot nobody has overwritten), segments, padding, slot counts and the 20-state
 //     look-ahead are what the traversal kernels rely on.
+//   * the launch rule of the fused 4-state evaluator (csrc/launch_plan.hpp): its defaults on the
+//     benchmark's workloads against values worked out by hand from the thresholds, the LDS bound
+//     over every rate count, sites per lane, table size and stack depth, and the forced values.
 // prints "host logic OK <cases>" on success.
 #include <algorithm>
 #include <cstdio>
@@ -30,6 +33,7 @@
 #include "clade_classes.hpp"
 #include "clv_plan.hpp"
 #include "k20_split.hpp"
+#include "launch_plan.hpp"
 #include "schedule_plan.hpp"
 
 static int fail(const char *what, int a = 0, int b = 0) {
@@ -772,6 +776,183 @@ static int check_clade_selection(std::mt19937 &rng, int &cases) {
   return 0;
 }
 
+// ---- the fused 4-state evaluator's launch rule (csrc/launch_plan.hpp) ---------------------------
+struct LaunchCase {
+  const char *name;
+  unsigned R, n_jobs, sites, tips, table_rows;
+  size_t arena_bytes, table_bytes;
+  unsigned depth[2], reg[2];
+  // expected, worked out by hand from the rule as rdamd_evaluate_batch applies it (evaluate.hip,
+  // kernels_fused.hip), not from the function under test: NS = 2 from n_jobs x blocks_x >= 8192; RW for 2 <= R <= 8, an arena of
+  // >= 512 MB and no speculation; job-major for n_jobs >= 16 and 4096 / (blocks_x / 2) x table
+  // bytes > 16 MB; speculation up to 256 tips; the private-segment stack for 64-row tables, one
+  // register level and 2..7 in-memory levels; LDS = waves x (8 TR x 8 + LDS levels x NS x 64 x 36)
+  unsigned blocks_x, ns, rw, job_major, speculate;
+  unsigned rl[2], sp[2];
+  size_t lds[2];
+};
+
+static rdamd::FusedLaunchInput launch_input(const LaunchCase &c) {
+  rdamd::FusedLaunchInput in;
+  in.rate_cats = c.R; in.n_jobs = c.n_jobs; in.blocks_x = ((c.sites + 63) / 64 + 15) / 16 * 16;
+  in.tipcodes_bytes = c.arena_bytes; in.table_bytes_per_job = c.table_bytes; in.table_rows = c.table_rows;
+  in.tips = c.tips;
+  for (int k = 0; k < 2; ++k) { in.max_depth[k] = c.depth[k]; in.reg_levels[k] = c.reg[k]; }
+  return in;
+}
+
+static int check_launch_rule(int &cases) {
+  using namespace rdamd;
+  const size_t MB = (size_t)1 << 20;
+  // Shapes: bench.py's configs (taxa, sites, R = 4, 197-job batches, 64-row tables), 2 n - 3
+  // matrices per job at 512 B per (matrix, rate) plus 2 KB per (64-row pseudo-tip, rate); arenas as
+  // the kernels' notes give them (c2 16 MB, c4 850 MB, c5 340 MB); c4's stack the one that makes
+  // its one-wave-per-rate launch 142 KB.  The last one is test_balanced_trees_deep_stacks' big launch.
+  const LaunchCase table[] = {
+      //  name        R  jobs  sites   tips TR  arena      tables                      depth   reg     bx    NS RW JM SPEC RL      SP      LDS
+      {"c2",          4, 197,  50000,  100, 64, 16 * MB,   197 * 2048 + 25 * 8192,     {1, 2}, {1, 1}, 784,  2, 0, 0, 1,   {1, 1}, {0, 7}, {8704, 8704}},
+      {"c4",          4, 197,  500000, 500, 64, 850 * MB,  997 * 2048 + 40 * 8192,     {7, 7}, {2, 2}, 7824, 2, 1, 0, 0,   {2, 2}, {0, 0}, {145408, 145408}},
+      {"c5",          4, 197,  100000, 1000, 64, 340 * MB, 1997 * 2048 + 60 * 8192,    {5, 6}, {1, 1}, 1568, 2, 0, 1, 0,   {1, 1}, {7, 7}, {8704, 8704}},
+      {"c4/8",        4, 197,  62500,  500, 64, 107 * MB,  997 * 2048 + 40 * 8192,     {7, 7}, {2, 2}, 992,  2, 0, 1, 0,   {2, 2}, {0, 0}, {36352, 36352}},
+      {"d125",        4, 197,  19436,  125, 64, 9 * MB,    247 * 2048 + 20 * 8192,     {2, 3}, {1, 1}, 304,  2, 0, 1, 1,   {1, 1}, {7, 7}, {8704, 8704}},
+      {"balanced700", 4, 60,   700,    192, 64, 268800,    381 * 2048,                 {6, 6}, {1, 1}, 16,   1, 0, 1, 1,   {1, 1}, {7, 7}, {6400, 6400}},
+  };
+  for (const LaunchCase &c : table) {
+    const FusedLaunchInput in = launch_input(c);
+    const FusedLaunchShape s = plan_fused_launch(in);
+    std::fprintf(stderr, "launch rule %-12s blocks_x %4u: NS %u RW %u job-major %u speculate %u | pass 0: RL %u SP %u LDS %zu | pass 1: RL %u SP %u LDS %zu\n",
+                 c.name, in.blocks_x, s.sites_per_lane, s.rates_across_waves, s.job_major, s.speculate, s.pass[0].reg_levels,
+                 s.pass[0].spill, s.pass[0].lds_bytes, s.pass[1].reg_levels, s.pass[1].spill, s.pass[1].lds_bytes);
+    if (in.blocks_x != c.blocks_x) return fail("launch rule: blocks_x of a named workload", (int)in.blocks_x, (int)c.blocks_x);
+    if (s.sites_per_lane != c.ns || s.rates_across_waves != c.rw || s.job_major != c.job_major || s.speculate != c.speculate ||
+        s.not_honoured != 0)
+      return fail(c.name, (int)s.sites_per_lane * 1000 + (int)s.rates_across_waves * 100 + (int)s.job_major * 10 + (int)s.speculate,
+                  (int)s.not_honoured);
+    for (int k = 0; k < 2; ++k)
+      if (s.pass[k].reg_levels != c.rl[k] || s.pass[k].spill != c.sp[k] || s.pass[k].lds_bytes != c.lds[k] ||
+          s.pass[k].mem_levels != c.depth[k])
+        return fail(c.name, k, (int)s.pass[k].lds_bytes);
+    ++cases;
+  }
+  // ---- the LDS bound: one wave per rate only where R waves fit 160 KB; nothing ever asks for more ----
+  static_assert(kFusedLdsLimit == 163840, "160 KB: a CU's LDS on gfx950");
+  static_assert(kPlanSpillLevels == kFusedSpillLevels, "launch_plan.hpp plans the stacks of kernels_fused.hip's kernels");
+  unsigned dropped = 0, kept = 0;
+  for (unsigned R = 1; R <= 8; ++R)
+    for (unsigned ns = 1; ns <= 2; ++ns)
+      for (unsigned tr : {16u, 64u})
+        for (unsigned depth = 0; depth <= 12; ++depth)
+          for (unsigned reg = 1; reg <= 2; ++reg)
+            for (int forced = 0; forced < 2; ++forced) {
+              FusedLaunchInput in;
+              in.rate_cats = R; in.n_jobs = 4; in.blocks_x = 16; in.table_rows = tr; in.tips = 1000;
+              in.table_bytes_per_job = 1 << 20;
+              in.max_depth[0] = 1; in.reg_levels[0] = 1;         // (a shallow folded program; the plain one decides)
+              in.max_depth[1] = depth; in.reg_levels[1] = reg;
+              in.force_ns = (int)ns;
+              if (forced) in.force_rw = 1;
+              else in.tipcodes_bytes = 600 * MB;
+              const FusedLaunchShape s = plan_fused_launch(in);
+              // by hand: the stack levels a wave keeps in LDS, its bytes, R of them
+              const bool priv = tr == 64 && reg == 1 && depth >= 2 && depth <= 7;
+              const unsigned levels = priv ? 1u : std::max(depth, 1u);
+              const size_t per_wave = 8u * tr * 8u + (size_t)levels * ns * 64u * 36u;
+              const bool legal_r = R >= 2;
+              const bool fits = per_wave * R <= 163840u && (8u * tr * 8u + ns * 64u * 36u) * (size_t)R <= 163840u;
+              const unsigned want_rw = legal_r && fits;
+              const unsigned want_word = !legal_r ? (forced ? kLaunchRwRates : 0u) : fits ? 0u : (forced ? kLaunchRwLds : kLaunchRuleRwLds);
+              if (s.rates_across_waves != want_rw) return fail("LDS bound: one wave per rate", (int)(R * 100 + depth), (int)(ns * 100 + tr));
+              if (s.not_honoured != want_word) return fail("LDS bound: the report's word", (int)s.not_honoured, (int)want_word);
+              if (s.sites_per_lane != ns || (s.pass[1].spill != 0) != priv || s.pass[1].reg_levels != (priv ? 1u : reg))
+                return fail("LDS bound: stack kind", (int)(R * 100 + depth), (int)(ns * 100 + tr));
+              if (s.pass[1].lds_bytes != per_wave * (want_rw ? R : 1u)) return fail("LDS bound: bytes", (int)s.pass[1].lds_bytes, (int)per_wave);
+              for (int k = 0; k < 2; ++k)
+                if (s.pass[k].lds_bytes > kFusedLdsLimit) return fail("LDS bound: a launch beyond the limit", (int)s.pass[k].lds_bytes);
+              dropped += legal_r && !fits;
+              kept += want_rw;
+              ++cases;
+            }
+  if (!dropped || !kept) return fail("LDS bound: the sweep never crosses the limit");
+  {   // the two launches that could not have fitted: 1000-taxon alignments beyond 512 MB of codes
+    struct { const char *name; unsigned R, ns, tr, depth, reg; size_t bytes; } named[] = {
+        {"A: R 4, two sites per lane, 64-row tables, nine in-memory levels", 4, 2, 64, 9, 2, 182272},
+        {"B: R 8, two sites per lane, 16-row tables, eight in-memory levels", 8, 2, 16, 8, 2, 303104},
+    };
+    for (const auto &c : named) {
+      FusedLaunchInput in;
+      in.rate_cats = c.R; in.n_jobs = 197; in.blocks_x = 1568; in.table_rows = c.tr; in.tips = 1000;
+      in.tipcodes_bytes = 600 * MB;
+      for (int k = 0; k < 2; ++k) { in.max_depth[k] = c.depth; in.reg_levels[k] = c.reg; }
+      const size_t would = fused_pass_shape(c.tr, c.ns, c.R, c.depth, c.reg).lds_bytes;
+      const FusedLaunchShape s = plan_fused_launch(in);
+      std::fprintf(stderr, "launch rule LDS case %s: one wave per rate would ask for %zu B of %zu -> RW %u, one wave: %zu B\n", c.name,
+                   would, (size_t)kFusedLdsLimit, s.rates_across_waves, s.pass[0].lds_bytes);
+      if (would != c.bytes) return fail("LDS case: bytes of the request", (int)would, (int)c.bytes);
+      if (s.sites_per_lane != c.ns || s.rates_across_waves != 0 || s.not_honoured != kLaunchRuleRwLds ||
+          s.pass[0].lds_bytes != c.bytes / c.R)
+        return fail("LDS case: the rule must take the one-wave form", (int)s.rates_across_waves, (int)s.not_honoured);
+      in.force_rw = 1;
+      if (plan_fused_launch(in).rates_across_waves != 0 || plan_fused_launch(in).not_honoured != kLaunchRwLds)
+        return fail("LDS case: forced beyond the limit");
+      ++cases;
+    }
+  }
+  {   // ---- forced values: honoured when legal, reported when not -------------------------------
+    FusedLaunchInput base;
+    base.rate_cats = 4; base.n_jobs = 3; base.blocks_x = 16; base.table_rows = 16; base.tips = 12;
+    base.table_bytes_per_job = 21 * 2048; base.tipcodes_bytes = 12 * 64;
+    const FusedLaunchShape rule = plan_fused_launch(base);
+    if (rule.sites_per_lane != 1 || rule.rates_across_waves || rule.job_major || !rule.speculate || rule.not_honoured)
+      return fail("forced: the small batch's defaults");
+    for (int ns : {1, 2})
+      for (int jm : {0, 1})
+        for (int rw : {0, 1})
+          for (int spec : {0, 1}) {
+            FusedLaunchInput in = base;
+            in.force_ns = ns; in.force_job_major = jm; in.force_rw = rw; in.speculation = spec;
+            const FusedLaunchShape s = plan_fused_launch(in);
+            if (s.sites_per_lane != (unsigned)ns || s.job_major != (unsigned)jm || s.speculate != (unsigned)spec)
+              return fail("forced: sites per lane / job-major", ns, jm);
+            if (s.rates_across_waves != (unsigned)(rw && !spec)) return fail("forced: one wave per rate", rw, spec);
+            if (s.not_honoured != (rw && spec ? kLaunchRwSpeculate : 0u)) return fail("forced: word", (int)s.not_honoured);
+            if (s.pass[0].lds_bytes != (size_t)(s.rates_across_waves ? 4 : 1) * (1024 + ns * 2304)) return fail("forced: bytes");
+            ++cases;
+          }
+    for (unsigned R : {1u, 9u, 16u}) {   // one wave per rate category: 2..8 categories
+      FusedLaunchInput in = base;
+      in.rate_cats = R; in.force_rw = 1; in.speculation = 0;
+      const FusedLaunchShape s = plan_fused_launch(in);
+      if (s.rates_across_waves || s.not_honoured != kLaunchRwRates) return fail("forced: R outside 2..8", (int)R);
+      in.force_rw = -1; in.tipcodes_bytes = 600 * MB;
+      if (plan_fused_launch(in).rates_across_waves || plan_fused_launch(in).not_honoured) return fail("rule: R outside 2..8", (int)R);
+      ++cases;
+    }
+    {   // the exporting launch: one job, one site per lane, plain program, all-LDS
+      FusedLaunchInput in = base;
+      in.n_jobs = 1; in.export_children = true; in.max_depth[1] = 3; in.reg_levels[1] = 2;
+      FusedLaunchShape s = plan_fused_launch(in);
+      if (s.sites_per_lane != 1 || s.rates_across_waves || s.job_major || s.speculate || s.not_honoured ||
+          s.pass[1].reg_levels != 2 || s.pass[1].spill || s.pass[1].lds_bytes != 1024 + 3 * 2304)
+        return fail("export: defaults");
+      in.force_ns = 2; in.force_rw = 1; in.force_job_major = 1;
+      s = plan_fused_launch(in);
+      if (s.sites_per_lane != 1 || s.rates_across_waves || s.job_major ||
+          s.not_honoured != (kLaunchRwExport | kLaunchNsExport | kLaunchJobMajorExport))
+        return fail("export: forced values", (int)s.not_honoured);
+      ++cases;
+    }
+    {   // values the seam refuses never reach the rule; should one, it is the rule's choice
+      FusedLaunchInput in = base;
+      in.force_ns = 3; in.force_rw = 7; in.force_job_major = -5;
+      const FusedLaunchShape s = plan_fused_launch(in);
+      if (s.sites_per_lane != rule.sites_per_lane || s.rates_across_waves != rule.rates_across_waves || s.job_major != rule.job_major)
+        return fail("forced: out-of-range values");
+      ++cases;
+    }
+  }
+  return 0;
+}
+
 int main() {
   std::mt19937 rng(20240603);
   int cases = 0;
@@ -917,6 +1098,7 @@ int main() {
   }
   if (check_planner(rng, cases)) return 1;
   if (check_validation(rng, cases) || check_clade_selection(rng, cases)) return 1;
+  if (check_launch_rule(cases)) return 1;
   std::printf("host logic OK %d\n", cases);
   return 0;
 }

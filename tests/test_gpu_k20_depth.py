@@ -23,7 +23,7 @@ import root_digger_amd as rd
 from root_digger_amd import synth
 import util
 from oracle_lib import OraclePartition
-from test_gpu_parity import _balanced_newick, LNL_TOL
+from test_gpu_parity import LNL_TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +43,7 @@ CMAP = util.make_map(AA)
 
 def _setup(n_tips, S, R, seed):
     rng = np.random.default_rng(seed)
-    tree = rd.Tree.from_newick(_balanced_newick(n_tips, rng))
+    tree = rd.Tree.from_newick(util.balanced_newick(n_tips, rng))
     seqs = {"t%d" % i: "".join(AA[k] for k in rng.integers(0, 20, S)) for i in range(n_tips)}
     weights = rng.integers(1, 4, size=S).astype(np.uint32)
     return rng, tree, seqs, weights

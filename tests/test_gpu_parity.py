@@ -795,14 +795,6 @@ def test_thousand_taxon_tree_vs_oracle():
     compare_state(g, o, [ops[i] for i in (0, 500, 998)], tree)
 
 
-def _balanced_newick(n_tips, rng):
-    nodes = ["t%d:%.5f" % (i, rng.uniform(0.02, 0.3)) for i in range(n_tips)]
-    while len(nodes) > 3:
-        nodes = ["(%s,%s):%.5f" % (nodes[i], nodes[i + 1], rng.uniform(0.02, 0.3))
-                 for i in range(0, len(nodes), 2)]
-    return "(" + ",".join(nodes) + ");"
-
-
 @pytest.mark.parametrize("n_tips,repeats,sites", [(48, 0, 700), (192, 0, 700), (192, 64, 700), (192, 16, 130),
                                                  (768, 0, 300)])
 def test_balanced_trees_deep_stacks(n_tips, repeats, sites):
@@ -811,10 +803,12 @@ def test_balanced_trees_deep_stacks(n_tips, repeats, sites):
     private segment up to eight levels in all (kernels_fused.hip, SP), two register levels and
     an all-LDS stack beyond and without repeats.
     Random (unrelated) sequences make the rescaling fire on the way up, so parked rescale
-    counts travel through every kind of level.  One and two sites per lane (launch size),
-    plain and folded programs."""
+    counts travel through every kind of level.  Plain and folded programs, a launch of 3 and one
+    of 60 jobs.  (Both run ONE site per lane: 60 jobs of at most 16 64-site blocks stay far below
+    the 8192 blocks from which a launch takes two, csrc/launch_plan.hpp -- the deep stacks at two
+    sites per lane run in the full-size tests of test_gpu_configs.py only.)"""
     rng = np.random.default_rng(n_tips + repeats)
-    tree = rd.Tree.from_newick(_balanced_newick(n_tips, rng))
+    tree = rd.Tree.from_newick(util.balanced_newick(n_tips, rng))
     seqs = {"t%d" % i: "".join(rng.choice(list("ACGT"), sites)) for i in range(n_tips)}
     w = synth.workload(8, 10, 4, 4, 5, simulate_seqs=False)
     g = rd.Partition.for_tree(tree, 4, sites, 4, attributes=rd.ATTRIB_SITE_REPEATS if repeats else 0)
@@ -833,8 +827,8 @@ def test_balanced_trees_deep_stacks(n_tips, repeats, sites):
     # (in-memory levels: behind one register level with repeats -- the 64-row kernels have
     # private-segment levels --, behind two from four levels on without)
     assert depth >= (3 if n_tips >= 192 and repeats != 16 else 2), depth
-    small = g.evaluate_batch(scheds, [w["subst"]] * 3, [freqs] * 3)                 # one site per lane
-    big = g.evaluate_batch(scheds * 20, [w["subst"]] * 60, [freqs] * 60)            # two
+    small = g.evaluate_batch(scheds, [w["subst"]] * 3, [freqs] * 3)
+    big = g.evaluate_batch(scheds * 20, [w["subst"]] * 60, [freqs] * 60)            # (one site per lane as well)
     for a, b in zip(small, want):
         assert util.rel_err(a, b) < LNL_TOL
     assert np.array_equal(big, np.tile(small, 20))

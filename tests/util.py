@@ -262,5 +262,17 @@ def tip_tip_pair(tree, ops):
     raise KeyError("no operation over two tips")
 
 
+def balanced_newick(n_tips, rng):
+    """a perfectly balanced unrooted tree over t0 .. t<n_tips - 1> (3 x 2^k tips, or 2^k: the top
+    node then joins one half and two quarters), random branch lengths: the deepest evaluator stacks
+    a tree of its size can ask for"""
+    nodes = ["t%d:%.5f" % (i, rng.uniform(0.02, 0.3)) for i in range(n_tips)]
+    while len(nodes) > 3:
+        pairs = 1 if len(nodes) == 4 else len(nodes) // 2
+        nodes = ["(%s,%s):%.5f" % (nodes[2 * i], nodes[2 * i + 1], rng.uniform(0.02, 0.3))
+                 for i in range(pairs)] + nodes[2 * pairs:]
+    return "(" + ",".join(nodes) + ");"
+
+
 def rel_err(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-300)
