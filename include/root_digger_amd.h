@@ -1069,6 +1069,90 @@ int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_locat
                                         double *lnl_before, double *lnl_after, unsigned int *iterations,
                                         unsigned int *evaluations, int *converged);
 
+/* ------------------------------------------------------------------------
+ * Branch pair sums: the derivative of lnL in every entry of every P-matrix, and from them the
+ * exact gradient of lnL in the model parameters.  NEW relative to the reference, which takes its
+ * gradient as 1 + n one-sided differences.
+ *
+ * Notation of the two sections above.  Branch (k, c) lies above child a of node k and has
+ * sibling b.  For site s and rate category r, with K the caller's state count:
+ *   t_r[i]   = U_u[i] (P_b L_b)[i]
+ *   f0(s)    = sum_r w_r t_r . (P_a L_a,r)                 (per-site scalings cancel below)
+ *   N[k][c][r][i][j] = sum_s weight_s w_r t_r[i] L_a,r[j] / f0(s)      (a tip's L: its 0/1 code vector)
+ *   froot(s) = sum_r w_r pi^(r) . L_root,r                 pi^(r): the set freqs_indices[r]
+ *   M[r][i]  = sum_s weight_s w_r L_root,r[i] / froot(s)
+ *   W[r]     = sum_s weight_s (pi^(r) . L_root,r) / froot(s)
+ * With every other quantity held fixed:
+ *   d lnL / d P_(k,c),r[i][j] = N[k][c][r][i][j]
+ *   d lnL / d pi^(m)_i at the root = sum over r with freqs_indices[r] = m of M[r][i]
+ *   d lnL / d w_r = W[r]
+ * Identities:
+ *   I1  sum_{r,i,j} N[k][c][r][i][j] P_(k,c),r[i][j] = sum_s weight_s           for every branch
+ *   I2  sum_r rho_r sum_{i,j} N[k][c][r][i][j] (Q_r P_(k,c),r)[i][j] = d1[k][c]   of rdamd_branch_derivatives
+ *   I3  sum_r sum_i pi^(r)_i M[r][i] = sum_s weight_s   and   sum_r w_r W[r] = sum_s weight_s
+ * ---------------------------------------------------------------------- */
+/* pair_out[n_ops][2][R][K][K], nodes as rdamd_marginal_ancestral_nodes orders them; root_out[R][K]
+ * and cat_out[R] may be NULL.  Preconditions and refusals are those of rdamd_branch_derivatives
+ * (errors 63, 64, 65, 10 / 7); error 67: pair_out is NULL.  Zero sites: zeros and success.  Nothing
+ * in the partition is written.  4-state and binary partitions; binary ones get the [2][2] / [2]
+ * blocks of their own states.  Every term is non-negative.  The sums over sites are made in one
+ * fixed order without floating-point atomics: inside a wave, the four waves of a workgroup in wave
+ * order, one partial per (workgroup, entry), and a second kernel that continues each entry's running
+ * sum by increasing workgroup.  The walk runs in passes over contiguous ranges of whole workgroups
+ * so that the partials of one pass take at most workspace_bytes (0: 256 MiB; never less than one
+ * workgroup per pass); the result is bit for bit independent of the number of passes.  The sums read
+ * the CLVs and outer vectors as they are kept: one power-of-two scaling per site for all rate
+ * categories, so a category's entry more than about 2^-510 below its site's largest contributes a
+ * denormal or zero. */
+int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                           const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
+                           double *root_out, double *cat_out);
+/* device time of the launches of this thread's last rdamd_branch_pair_sums call, milliseconds
+ * between two HIP events (0 after a failed call); for measurements */
+double rdamd_pair_sums_last_ms(void);
+/* The exact gradient from the pair sums: plain host code, a pure function of its arguments, no
+ * device needed.  states K in {2, ..., 64}; pair[n_ops][2][R][K][K], root[R][K], cat[R] as above;
+ * lengths[n_ops][2]: the length of branch (k, c); subst[rate_matrices][K K - K]: off-diagonal
+ * exchangeabilities row-major; freqs[rate_matrices][K]: K independent numbers that enter Q and the
+ * root exactly as given (no renormalisation, as rdamd_set_frequencies takes them); params_indices,
+ * freqs_indices, rates, weights: per rate category.
+ *   Q_m = raw / mu,  raw_ij = s_ij pi_j (i != j), zero row sums,  mu = -sum_i pi_i raw_ii
+ *   G_Q[m] = sum_branches sum_{r: params_indices[r] = m} rho_r tau F((rho_r tau Q_m)^T, N[branch][r])
+ *   F(X, E) = integral_0^1 exp(xX) E exp((1 - x)X) dx = the top-right block of exp([[X, E], [0, X]])
+ *   d lnL / d rho_r = sum_branches tau sum_ij N[branch][r][i][j] (Q P)[i][j]
+ *                   = sum_branches tau sum_ij (F((rho_r tau Q)^T, N[branch][r]))_ij Q_ij     (the same adjoint)
+ * F by scaling and squaring on the pair (exp, F): Taylor terms D_k = (X D_{k-1} + E X^{k-1}/(k-1)!)/k,
+ * squaring (P, F) -> (P P, P F + F P).  Then the chain rule through Q = raw / mu with all K K
+ * entries of G_Q free; the frequencies of set m get their part through Q (with the pi of
+ * params_indices' set m) and, as set m of freqs_indices, the root term M.
+ * Outputs (any may be NULL): d_subst[rate_matrices][K K - K], d_freqs[rate_matrices][K], d_rates[R],
+ * d_weights[R] (= cat).  Returns RDAMD_SUCCESS, or RDAMD_FAILURE with error 64 for a NULL input or
+ * a state count out of range, 7 for an index >= rate_matrices. */
+int rdamd_gradient_from_pair_sums(unsigned int states, unsigned int rate_cats, unsigned int rate_matrices,
+                                  unsigned int n_ops, const double *pair, const double *root, const double *cat,
+                                  const double *lengths, const double *subst, const double *freqs,
+                                  const unsigned int *params_indices, const unsigned int *freqs_indices,
+                                  const double *rates, const double *weights, double *d_subst, double *d_freqs,
+                                  double *d_rates, double *d_weights);
+
+/* The exact gradient of lnL at one root of a model.  counts / values: the parameters in the
+ * checkpoint's layout exactly as rdamd_model_branch_derivatives takes them, here required (the
+ * model does not keep the optimiser's variables).  grad_out has the layout of values and holds the
+ * gradient in the variables L-BFGS-B sees in the parameter steps of the search:
+ *   the substitution rates as given;
+ *   the unnormalised frequency vector x, pi = x / sum x:  g_x = (g_pi - pi . g_pi) / sum x;
+ *   alpha through rdamd_compute_gamma_cats(alpha, R, rates, RDAMD_GAMMA_RATES_MEDIAN): the Jacobian
+ *     d rho / d alpha is a CENTRAL DIFFERENCE of that host function with step 1e-6 max(1, alpha);
+ *   the unnormalised category weights u of a FREE partition, w = u / sum u; a FREE partition's rates
+ *     are inert, so its alpha entry is 0; the weight entries of any other partition are 0.
+ * Each evaluation is rdamd_update_prob_matrices, a materialising traversal, the root lnL (*lnl_out,
+ * may be NULL), rdamd_branch_pair_sums per partition and rdamd_gradient_from_pair_sums.  The model's
+ * parameters, its rooting and the conditional likelihoods of that rooting are as before when the
+ * call returns.  Refused (error 61) for a model that sums over a site group; a partition whose shape
+ * rdamd_branch_pair_sums refuses fails the call and is named in the message. */
+int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                         const double *values, double *grad_out, double *lnl_out);
+
 /* Column that draw d (0 <= d < N) of bootstrap replicate b resamples, N < 2^32 columns.
  * Stateless and counter-based (all arithmetic mod 2^64):
  *   sm(x):  x += 0x9E3779B97F4A7C15; z = x;

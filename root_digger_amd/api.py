@@ -305,6 +305,11 @@ _sig("rdamd_tree_newick_ancestral", _vp, _vp, _u, _pu)
 _sig("rdamd_tree_newick_branch_lengths", _vp, _vp, _u, _pu, _pd)
 _sig("rdamd_branch_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd)
 _sig("rdamd_branch_last_ms", C.c_double)
+_sig("rdamd_model_gradient", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pd, _pd)
+_sig("rdamd_branch_pair_sums",C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd, _pd)
+_sig("rdamd_pair_sums_last_ms", C.c_double)
+_sig("rdamd_gradient_from_pair_sums", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pd, _pd, _pd, _pd,
+     _pd, _pd)
 _sig("rdamd_model_branch_derivatives", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd,
      _pd, _pd)
 _sig("rdamd_model_optimize_branch_lengths", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, C.c_double, C.c_double,
@@ -798,6 +803,22 @@ class Partition:
             _fail("branch_derivatives")
         return d1, d2
 
+    def branch_pair_sums(self, ops, freqs_indices=None, workspace_bytes=0):
+        """(N[len(ops)][2][R][K][K], M[R][K], W[R]): the derivative of lnL in every entry of the P-matrix
+        of the branch above child c of node k, in the root frequencies per category and in the category
+        weights (rdamd_branch_pair_sums; workspace_bytes bounds the partial sums of one pass, 0: 256
+        MiB).  Call update_prob_matrices and update_clvs on this list first."""
+        ops = _op_array(ops)
+        fi = self.params_indices if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        R, K = self.rate_cats, self.states
+        pair = np.zeros((len(ops), 2, R, K, K), dtype=np.float64)
+        root = np.zeros((R, K), dtype=np.float64)
+        cat = np.zeros(R, dtype=np.float64)
+        if lib.rdamd_branch_pair_sums(self._h, ops, len(ops), _uptr(fi), int(workspace_bytes), _dptr(pair), _dptr(root),
+                                      _dptr(cat)) != 1:
+            _fail("branch_pair_sums")
+        return pair, root, cat
+
     def site_rate_posteriors(self, clv_index, scaler_index=SCALE_BUFFER_NONE, freqs_indices=None):
         """(cat[sites][R], mean_rate[sites]): posterior of every rate category and posterior mean rate of
         every site, from the root CLV (rdamd_site_rate_posteriors)."""
@@ -1128,6 +1149,35 @@ def ancestral_last_ms():
 def branch_last_ms():
     """device milliseconds of the launches of this thread's last branch_derivatives call"""
     return float(lib.rdamd_branch_last_ms())
+
+
+def pair_sums_last_ms():
+    """device milliseconds of the launches of this thread's last branch_pair_sums call"""
+    return float(lib.rdamd_pair_sums_last_ms())
+
+
+def gradient_from_pair_sums(pair, root, cat, lengths, subst, freqs, params_indices, freqs_indices, rates, weights):
+    """(d_subst[m][K K - K], d_freqs[m][K], d_rates[R], d_weights[R]): the exact gradient of lnL from the
+    pair sums of branch_pair_sums (rdamd_gradient_from_pair_sums; host only).  subst[m], freqs[m]: the
+    rate-matrix sets; frequencies enter exactly as given."""
+    pair = np.ascontiguousarray(pair, dtype=np.float64)
+    n, _, R, K, _ = pair.shape
+    root, cat, lengths, rates, weights = (np.ascontiguousarray(v, dtype=np.float64) for v in (root, cat, lengths, rates, weights))
+    subst = np.ascontiguousarray(subst, dtype=np.float64).reshape(-1, K * K - K)
+    freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1, K)
+    sets = subst.shape[0]
+    if freqs.shape[0] != sets or lengths.shape != (n, 2) or root.shape != (R, K) or any(v.shape != (R,) for v in (cat, rates, weights)):
+        raise ValueError("gradient_from_pair_sums: shapes do not fit the pair sums")
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+    if pi.shape != (R,) or fi.shape != (R,):
+        raise ValueError("gradient_from_pair_sums: one index per rate category")
+    d_subst, d_freqs, d_rates, d_weights = np.zeros_like(subst), np.zeros_like(freqs), np.zeros(R), np.zeros(R)
+    if lib.rdamd_gradient_from_pair_sums(K, R, sets, n, _dptr(pair), _dptr(root), _dptr(cat), _dptr(lengths), _dptr(subst),
+                                         _dptr(freqs), _uptr(pi), _uptr(fi), _dptr(rates), _dptr(weights), _dptr(d_subst),
+                                         _dptr(d_freqs), _dptr(d_rates), _dptr(d_weights)) != 1:
+        _fail("gradient_from_pair_sums")
+    return d_subst, d_freqs, d_rates, d_weights
 
 
 def rell_last_resample_ms():
@@ -1644,6 +1694,27 @@ class Model:
                  "branch_derivatives")
         assert nn.value == n
         return clv, parent, children, lengths, d1, d2, lnl.value
+
+    def gradient(self, rl, params):
+        """The exact gradient of lnL at root rl (rdamd_model_gradient) -> (grad, lnl).  params: the
+        per-partition dicts Checkpoint.read_results returns for one root (required: the gradient is in
+        the optimiser's variables -- substitution rates, unnormalised frequencies, alpha, a FREE
+        partition's unnormalised weights --, which the model does not keep); grad: a list of dicts of
+        the same keys and shapes.  Nothing is applied to the model."""
+        params = list(params)
+        counts, values = _flatten_params(params)
+        grad = np.zeros_like(values)
+        lnl = C.c_double(0.0)
+        self._ok(lib.rdamd_model_gradient(self._h, C.byref(rl), counts.ctypes.data_as(_pu64), _dptr(values), _dptr(grad),
+                                          C.byref(lnl)), "gradient")
+        out, at = [], 0
+        for row in np.asarray(counts).reshape(-1, 4):
+            d = {}
+            for key, n in zip(("subst_rates", "freqs", "gamma_alpha", "gamma_weights"), row):
+                d[key] = grad[at:at + int(n)].copy()
+                at += int(n)
+            out.append(d)
+        return out, lnl.value
 
     def optimize_branch_lengths(self, rl, params=None, min_len=1e-6, max_len=100.0, atol=1e-8, max_iters=200):
         """The branch lengths in [min_len, max_len] that maximise lnL at root rl and fixed parameters

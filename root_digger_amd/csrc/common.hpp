@@ -297,6 +297,16 @@ hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsig
                                 const unsigned *d_pidx, const unsigned *d_fidx, double *d_work, double *d_partials,
                                 unsigned *d_bad_sites, double *d_out);
 
+// pair sums over the same program, in passes of at most blocks_per_pass (>= 1) whole workgroups:
+// doubles of one workgroup's row of partials (= of d_out: [nops][2][R][16] pair sums, then [R][5]:
+// M[r][0..3] and W[r]) and of the generic walk's staging buffer for a pass of `blocks` workgroups
+// (0 for the fast walk); d_partials: [blocks_per_pass] rows
+size_t pair_sum_doubles(const rdamd_partition *p, unsigned nops);
+size_t pair_sum_stage_doubles(const rdamd_partition *p, unsigned blocks);
+hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                   const unsigned *d_fidx, double *d_work, double *d_partials, double *d_stage,
+                                   unsigned blocks_per_pass, unsigned *d_bad_sites, double *d_out);
+
 // kernels_root.hip
 // The grid every root reduction is laid out over: one lane per (site, rate) -- the group layout --
 // or per site, in workgroups of 256 lanes, at most 1024 of them (a lane strides beyond that), never 0.

@@ -1,6 +1,7 @@
-// The pre-order pass: OUTER vectors, and what two analyses make of them -- marginal ancestral
-// state posteriors, and the first and second derivative of lnL in every branch length.  Also the
-// site-rate posteriors, which need the root CLV alone.
+// The pre-order pass: OUTER vectors, and what three analyses make of them -- marginal ancestral
+// state posteriors, the first and second derivative of lnL in every branch length, and the pair
+// sums (the derivative of lnL in every entry of every P-matrix).  Also the site-rate posteriors,
+// which need the root CLV alone.
 //
 // New here -- the reference computes no ancestral states and has one derivative, the forward
 // difference of its compute_dlh (src/model.cpp), for the root's position alone; this pass extends
@@ -24,7 +25,7 @@
 // registers, any other waits in a workspace slot (host-side liveness analysis).  The partition is
 // only read.
 //
-// A CONSUMER is a functor the walk calls at fixed places.  There are two:
+// A CONSUMER is a functor the walk calls at fixed places.  There are three:
 //   posteriors   post[v][s][j] = sum_r w_r U_v[j] L_v[j], normalised over j: the root's from pi
 //                before the loop, an inner child's where its outer vector is formed, its CLV
 //                being in registers already.
@@ -36,6 +37,10 @@
 //                exchanges, the four waves of a workgroup in wave order, one partial per
 //                (workgroup, branch) in a workspace, and a second kernel that adds the partials by
 //                increasing workgroup.  No floating-point atomics; equal inputs give equal bits.
+//   pair sums    N[a][r][i][j] = sum_s weight_s w_r t[i] L_a[j] / f0 for both children of every
+//                operation (the one consumer that reads the child's own vector in `branch`), and
+//                the root's M and W before the loop; summed as the derivatives are, in passes over
+//                ranges of whole workgroups (definitions above PairSumDna).
 // A consumer names its arguments (Args), the LDS it wants beside the walk's (Lds; empty: none is
 // allocated) and whether it is told of tip children (kTipBranches) and sums over the workgroup
 // (kBlockSums, generic walk); its hooks are begin, op_begin, branch, (branch_done,) outer, op_end
@@ -219,7 +224,7 @@ preorder_dna_walk(WalkArgs a, typename Consumer::Args ca) {
       double t[4], uc[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];   // the parent's vector masked by the sibling
-      con.branch(ln, c, t, pl[c]);
+      con.branch(ln, c, t, pl[c], l[c]);
       if (!op.inner[c]) continue;
 #pragma unroll
       for (int j = 0; j < 4; ++j) uc[j] = t[0] * m[j] + t[1] * m[4 + j] + t[2] * m[8 + j] + t[3] * m[12 + j];
@@ -294,7 +299,7 @@ preorder_generic_walk(WalkArgs a, typename Consumer::Args ca, unsigned R) {
           if (!op.inner[c] && !Consumer::kTipBranches) continue;
           double t[4];
           for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];
-          con.branch(a, c, r, t, pl[c]);
+          con.branch(a, c, r, t, pl[c], l[c]);
           if (!op.inner[c]) continue;
           const double *m = a.pmat + ((size_t)op.child_mat[c] * R + r) * 16;
           for (int j = 0; j < 4; ++j) {
@@ -348,7 +353,8 @@ struct PosteriorDna {
     write_post(a, ln, 0, ln.pi, l);
   }
   __device__ __forceinline__ void op_begin(const WalkArgs &, const DnaLane &, unsigned) const {}
-  __device__ __forceinline__ void branch(const DnaLane &, int, const double (&)[4], const double (&)[4]) const {}
+  __device__ __forceinline__ void branch(const DnaLane &, int, const double (&)[4], const double (&)[4],
+                                         const double (&)[4]) const {}
   __device__ __forceinline__ void outer(const WalkArgs &a, const DnaLane &ln, unsigned node, const double (&uc)[4],
                                         const double (&l)[4]) const {
     write_post(a, ln, node, uc, l);
@@ -380,7 +386,8 @@ struct PosteriorGeneric {
     write_post(a, s, 0, q);
   }
   __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned, unsigned) const {}
-  __device__ __forceinline__ void branch(const WalkArgs &, int, unsigned, const double (&)[4], const double (&)[4]) const {}
+  __device__ __forceinline__ void branch(const WalkArgs &, int, unsigned, const double (&)[4], const double (&)[4],
+                                         const double (&)[4]) const {}
   __device__ __forceinline__ void branch_done(int) const {}
   // u: the site's outer vector, [rate][4]
   __device__ __forceinline__ void outer(const WalkArgs &a, unsigned R, unsigned s, unsigned node, unsigned clv,
@@ -454,7 +461,8 @@ struct DerivativeDna {
   __device__ __forceinline__ void op_begin(const WalkArgs &a, const DnaLane &ln, unsigned k) const {
     if (k > 0) flush_block_sums(lds.wsum[(k & 1u) ^ 1u], c.partials, a.nops, k - 1, ln.tid);
   }
-  __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4]) {
+  __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4],
+                                         const double (&)[4]) {
     double p0, p1, p2;
     branch_products(&lds.sq[ln.r * kRateStride], t, y, &p0, &p1, &p2);
     const double f0 = rate_sum<R>(ln.w * p0), f1 = rate_sum<R>(w1 * p1), f2 = rate_sum<R>(w2 * p2);
@@ -504,7 +512,8 @@ struct DerivativeGeneric {
     for (int i = 0; i < 4; ++i) term[i] = 0.0;
     for (int i = 0; i < 6; ++i) f[i / 3][i % 3] = 0.0;
   }
-  __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4]) {
+  __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4],
+                                         const double (&)[4]) {
     const double w = a.rate_w[r], rho = c.rates[r];
     double p0, p1, p2;
     branch_products(c.q + (size_t)c.pidx[r] * 16, t, y, &p0, &p1, &p2);
@@ -539,6 +548,215 @@ brlen_sum_kernel(const double *__restrict__ partials, unsigned blocks, unsigned 
   out[e] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// Consumer: pair sums -- the derivative of lnL in every entry of every P-matrix
+// ---------------------------------------------------------------------------
+//   N[k][c][r][i][j] = sum_s weight_s w_r t_r[i] L_a,r[j] / f0(s)        f0 = sum_r w_r t_r . (P_a L_a,r)
+//   M[r][i] = sum_s weight_s w_r L_root,r[i] / froot(s)                  froot = sum_r w_r pi^(r) . L_root,r
+//   W[r]    = sum_s weight_s (pi^(r) . L_root,r) / froot(s)
+// summed as the derivative consumer sums: inside the wave by site_sum, the four waves in wave order,
+// one partial per (workgroup, entry), pair_sum_kernel over the workgroups.  A workgroup's row of
+// partials is [nops][2][R][16] pair entries, then [R][5] root entries (M[r][0..3], W[r]).
+struct PairSumArgs {
+  const unsigned *pattern_w;
+  double *partials;           // [workgroup][pair_sum_entries]
+  unsigned *bad_sites;
+  double *tstage;             // generic walk: [2][lane][R][4], the masked outer vectors of one operation
+  unsigned R;
+};
+
+__host__ __device__ inline size_t pair_sum_entries(unsigned nops, unsigned R) {
+  return (size_t)nops * 2 * R * 16 + (size_t)R * 5;
+}
+
+// weight / f, and whether f is a likelihood
+__device__ __forceinline__ bool site_factor(double f, double weight, double *g) {
+  const bool ok = f > 0.0 && isfinite(f);
+  *g = ok ? weight / f : 0.0;
+  return ok;
+}
+
+template <int R>
+struct PairSumDna {
+  using Args = PairSumArgs;
+  struct Lds {
+    alignas(16) double wsum[2][4][2][R][16];   // [operation parity][wave][child][rate][i][j]
+    alignas(16) double rsum[4][R][5];
+  };
+  static constexpr bool kTipBranches = true;
+  static constexpr unsigned kOpEntries = 2 * R * 16;
+  const Args c;
+  Lds &lds;
+  double weight;
+  unsigned buf = 0;
+  bool site_bad = false;
+  __device__ __forceinline__ PairSumDna(const Args &c, Lds &lds) : c(c), lds(lds) {}
+
+  __device__ __forceinline__ void flush(unsigned nops, unsigned k, unsigned tid) const {
+    if (tid < kOpEntries) {
+      const double *w = &lds.wsum[k & 1u][0][0][0][0];
+      c.partials[(size_t)blockIdx.x * pair_sum_entries(nops, R) + (size_t)k * kOpEntries + tid] =
+          ((w[tid] + w[kOpEntries + tid]) + w[2 * kOpEntries + tid]) + w[3 * kOpEntries + tid];
+    }
+  }
+  __device__ __forceinline__ void begin(const WalkArgs &a, const DnaLane &ln) {
+    weight = (double)c.pattern_w[ln.s];
+    double l[4], g;
+    load_clv(a, ln, a.prog[0].parent_clv, l);
+    const double dot = ln.pi[0] * l[0] + ln.pi[1] * l[1] + ln.pi[2] * l[2] + ln.pi[3] * l[3];
+    if (!site_factor(rate_sum<R>(ln.w * dot), weight, &g)) site_bad = true;
+    if (!ln.active) g = 0.0;
+    const double gw = g * ln.w;
+    const double term[5] = {gw * l[0], gw * l[1], gw * l[2], gw * l[3], g * dot};
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const double v = site_sum<R>(term[q]);
+      if (ln.lane < R) lds.rsum[ln.tid >> 6][ln.lane][q] = v;
+    }
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &a, const DnaLane &ln, unsigned k) {
+    buf = k & 1u;
+    if (k > 0) {
+      flush(a.nops, k - 1, ln.tid);
+    } else if (ln.tid < R * 5) {   // (the barrier after begin has passed)
+      const double *w = &lds.rsum[0][0][0];
+      const unsigned t = ln.tid;
+      c.partials[(size_t)blockIdx.x * pair_sum_entries(a.nops, R) + (size_t)a.nops * kOpEntries + t] =
+          ((w[t] + w[R * 5 + t]) + w[2 * R * 5 + t]) + w[3 * R * 5 + t];
+    }
+  }
+  __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4],
+                                         const double (&l)[4]) {
+    const double p0 = t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3];
+    double g;
+    if (!site_factor(rate_sum<R>(ln.w * p0), weight, &g)) site_bad = true;
+    if (!ln.active) g = 0.0;
+    const double gw = g * ln.w;
+    double *o = &lds.wsum[buf][ln.tid >> 6][ch][ln.lane < R ? ln.lane : 0][0];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double gt = gw * t[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double v = site_sum<R>(gt * l[j]);
+        if (ln.lane < R) o[i * 4 + j] = v;
+      }
+    }
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, const DnaLane &, unsigned, const double (&)[4],
+                                        const double (&)[4]) const {}
+  __device__ __forceinline__ void op_end(const DnaLane &, unsigned) const {}
+  __device__ __forceinline__ void end(const WalkArgs &a, const DnaLane &ln) const {
+    if (a.nops > 0) flush(a.nops, a.nops - 1, ln.tid);
+    if (ln.active && ln.r == 0 && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
+// One lane per site: the site's factor weight / f0 needs every rate, so `branch` stages w_r t_r and
+// op_end, which every lane of the workgroup reaches, forms and sums the products -- one (child,
+// rate) chunk of 16 at a time through wsum, whose two halves alternate from chunk to chunk (one
+// barrier per chunk: a half is written again only after the barrier that follows its readers).
+struct PairSumGeneric {
+  using Args = PairSumArgs;
+  struct Lds { alignas(16) double wsum[2][4][16]; };
+  static constexpr bool kTipBranches = true, kBlockSums = true;
+  const Args c;
+  Lds &lds;
+  const WalkArgs *wa = nullptr;
+  double weight = 0.0, f0[2], g[2];
+  unsigned s = 0, chunk = 0;
+  bool live = false, site_bad = false;
+  __device__ __forceinline__ PairSumGeneric(const Args &c, Lds &lds) : c(c), lds(lds) {}
+
+  __device__ __forceinline__ double *stage(int ch, unsigned r) const {
+    return c.tstage + ((((size_t)ch * gridDim.x + blockIdx.x) * 256 + threadIdx.x) * c.R + r) * 4;
+  }
+  // v: this lane's terms of N entries; the workgroup's sums go to partials[at..at + N)
+  template <int N>
+  __device__ __forceinline__ void block_sum(const double (&v)[N], size_t at, unsigned tid) {
+    double (&w)[4][16] = lds.wsum[chunk & 1u];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const double x = site_sum<1>(v[q]);
+      if ((tid & 63) == 0) w[tid >> 6][q] = x;
+    }
+    __syncthreads();
+    if (tid < (unsigned)N) c.partials[at + tid] = ((w[0][tid] + w[1][tid]) + w[2][tid]) + w[3][tid];
+    ++chunk;
+  }
+  __device__ __forceinline__ void begin(const WalkArgs &a, unsigned R, unsigned site, bool active) {
+    wa = &a; s = site; live = active;
+    weight = active ? (double)c.pattern_w[site] : 0.0;
+    const unsigned root = a.prog[0].parent_clv;
+    double froot = 0.0, l[4], gr = 0.0;
+    if (active) {
+      for (unsigned r = 0; r < R; ++r) {
+        const double *f = a.freqs + (size_t)a.fidx[r] * 4;
+        load_clv(a, R, site, root, r, l);
+        froot += a.rate_w[r] * (f[0] * l[0] + f[1] * l[1] + f[2] * l[2] + f[3] * l[3]);
+      }
+      if (!site_factor(froot, weight, &gr)) site_bad = true;
+    }
+    const size_t row = (size_t)blockIdx.x * pair_sum_entries(a.nops, R) + (size_t)a.nops * 2 * R * 16;
+    for (unsigned r = 0; r < R; ++r) {
+      double v[5] = {0, 0, 0, 0, 0};
+      if (active) {
+        const double *f = a.freqs + (size_t)a.fidx[r] * 4;
+        load_clv(a, R, site, root, r, l);
+        for (int i = 0; i < 4; ++i) v[i] = gr * a.rate_w[r] * l[i];
+        v[4] = gr * (f[0] * l[0] + f[1] * l[1] + f[2] * l[2] + f[3] * l[3]);
+      }
+      block_sum(v, row + (size_t)r * 5, threadIdx.x);
+    }
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned, unsigned) { f0[0] = f0[1] = 0.0; }
+  __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4],
+                                         const double (&)[4]) {
+    const double w = a.rate_w[r];
+    f0[ch] += w * (t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3]);
+    double *o = stage(ch, r);
+    for (int i = 0; i < 4; ++i) o[i] = w * t[i];
+  }
+  __device__ __forceinline__ void branch_done(int ch) {
+    if (!site_factor(f0[ch], weight, &g[ch])) site_bad = true;
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, unsigned, unsigned, unsigned, unsigned, const double *) const {}
+  __device__ __forceinline__ void op_end(unsigned k, unsigned tid) {
+    const WalkArgs &a = *wa;
+    const unsigned R = c.R;
+    const OuterOp op = a.prog[k];
+    const size_t row = (size_t)blockIdx.x * pair_sum_entries(a.nops, R) + (size_t)k * 2 * R * 16;
+    for (int ch = 0; ch < 2; ++ch)
+      for (unsigned r = 0; r < R; ++r) {
+        double v[16];
+        if (live) {
+          double l[4];
+          load_clv(a, R, s, op.child_clv[ch], r, l);
+          const double *t = stage(ch, r);
+          for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) v[i * 4 + j] = (g[ch] * t[i]) * l[j];
+        } else {
+          for (int e = 0; e < 16; ++e) v[e] = 0.0;
+        }
+        block_sum(v, row + ((size_t)ch * R + r) * 16, tid);
+      }
+  }
+  __device__ __forceinline__ void end(const WalkArgs &, bool active, unsigned) const {
+    if (active && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
+// out[e] = (first pass: 0, else out[e]) + the partials of entry e added by increasing workgroup:
+// the running sum of an entry goes through the workgroups in one order however the passes cut them
+__global__ void __launch_bounds__(256)
+pair_sum_kernel(const double *__restrict__ partials, unsigned blocks, size_t entries, int first, double *out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= entries) return;
+  double acc = first ? 0.0 : out[e];
+  for (unsigned b = 0; b < blocks; ++b) acc += partials[(size_t)b * entries + e];
+  out[e] = acc;
+}
+
 // posterior of every rate category and the posterior mean rate of every site, from the root CLV
 // (any state count; one lane per site).  Per-site scalers cancel in the normalisation.
 __global__ void __launch_bounds__(256)
@@ -563,18 +781,23 @@ site_rates_kernel(const double *__restrict__ clv, const double *__restrict__ fre
   if (mean) mean[s] = m;
 }
 
-// one walk over the partition for a consumer pair (the fast walk's and the generic walk's)
+// one walk over the partition for a consumer pair (the fast walk's and the generic walk's), or
+// over the `sites` sites from site0 on alone: a range is offset pointers and a smaller site count
+// (the workspace is the range's own; a consumer offsets what it reads per site itself)
 template <template <int> class Dna, class Generic>
 hipError_t launch_walk(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots, const unsigned *d_fidx,
-                       double *d_work, const typename Generic::Args &ca) {
+                       double *d_work, const typename Generic::Args &ca, unsigned site0 = 0, unsigned sites = ~0u) {
   WalkArgs a;
-  a.clv = p->d_clv; a.clv_stride = p->clv_doubles();
-  a.tipcodes = p->d_tipcodes; a.tip_stride = p->tip_stride(); a.codemask = p->d_codemask;
+  const bool fast = outer_fast_shape(p);
+  const unsigned R = p->rate_cats;
+  if (sites == ~0u) sites = p->sites - site0;
+  a.clv = p->d_clv + (size_t)site0 * R * 4; a.clv_stride = p->clv_doubles();
+  a.tipcodes = p->d_tipcodes + site0; a.tip_stride = p->tip_stride(); a.codemask = p->d_codemask;
   a.pmat = p->d_pmat; a.freqs = p->d_freqs; a.fidx = d_fidx; a.rate_w = p->d_rate_weights;
-  a.tips = p->tips; a.sites = p->sites;
+  a.tips = p->tips; a.sites = sites;
   a.work = d_work; a.prog = d_prog; a.nops = nops; a.slots = slots;
-  const unsigned R = p->rate_cats, grid = preorder_blocks(p);
-  if (!outer_fast_shape(p)) {
+  const unsigned grid = (unsigned)(((size_t)sites * (fast ? R : 1u) + 255) / 256);
+  if (!fast) {
     preorder_generic_walk<Generic><<<grid, 256, 0, p->stream>>>(a, ca, R);
   } else {
     switch (R) {
@@ -623,6 +846,32 @@ hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsig
   const unsigned entries = nops * 4;
   brlen_sum_kernel<<<(entries + 255) / 256, 256, 0, p->stream>>>(d_partials, preorder_blocks(p), entries, d_out);
   return hipGetLastError();
+}
+
+size_t pair_sum_doubles(const rdamd_partition *p, unsigned nops) { return pair_sum_entries(nops, p->rate_cats); }
+
+size_t pair_sum_stage_doubles(const rdamd_partition *p, unsigned blocks) {
+  return outer_fast_shape(p) ? 0 : (size_t)2 * blocks * 256 * p->rate_cats * 4;
+}
+
+hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                   const unsigned *d_fidx, double *d_work, double *d_partials, double *d_stage,
+                                   unsigned blocks_per_pass, unsigned *d_bad_sites, double *d_out) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const unsigned R = p->rate_cats, blocks = preorder_blocks(p);
+  const unsigned block_sites = outer_fast_shape(p) ? 256 / R : 256;   // sites of one workgroup
+  const size_t entries = pair_sum_entries(nops, R);
+  for (unsigned b0 = 0; b0 < blocks; b0 += blocks_per_pass) {
+    const unsigned nb = std::min(blocks_per_pass, blocks - b0);
+    const unsigned site0 = b0 * block_sites, sites = std::min(p->sites - site0, nb * block_sites);
+    const PairSumArgs ca{p->d_pattern_weights + site0, d_partials, d_bad_sites, d_stage, R};
+    hipError_t e = launch_walk<PairSumDna, PairSumGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca, site0, sites);
+    if (e != hipSuccess) return e;
+    pair_sum_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, p->stream>>>(d_partials, nb, entries, b0 == 0, d_out);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,

@@ -622,6 +622,93 @@ model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, con
   return out;
 }
 
+// The exact gradient at one root in the optimiser's variables (model.hpp).  The pair sums give
+// d lnL / d (subst, pi, rho, w) with pi and w as the partition holds them (rdamd_gradient_from_pair_sums);
+// the chain rule to the optimiser's variables is closed-form for pi = x / sum x and w = u / sum u,
+// and a central difference of the host's own rdamd_compute_gamma_cats (step 1e-6 max(1, alpha))
+// for rho(alpha).
+std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
+                                                      const std::vector<partition_parameters_t> &params, double *lnl) {
+  refuse_site_group("gradient", "derivatives of a site-sharded model are not supported");
+  const size_t P = _partitions.size();
+  require_fit(params, "gradient", "");
+  std::vector<partition_parameters_t> out(P);
+  with_saved_parameters(true, [] {}, [&] {
+    set_model_params(params);
+    auto sched = _tree.generate_operations(rl);
+    const auto &ops = std::get<0>(sched);
+    const auto &pmi = std::get<1>(sched);
+    const auto &brl = std::get<2>(sched);
+    const unsigned n_ops = (unsigned)ops.size();
+    std::unordered_map<unsigned, size_t> place;
+    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
+    std::vector<double> lengths(2 * (size_t)n_ops);
+    for (unsigned k = 0; k < n_ops; ++k) {
+      const rdamd_operation_t &o = ops[n_ops - 1 - k];
+      lengths[2 * k] = brl[place.at(o.child1_matrix_index)];
+      lengths[2 * k + 1] = brl[place.at(o.child2_matrix_index)];
+    }
+    update_pmatrices(pmi, brl);
+    ++_n_full;
+    double lh = 0.0;
+    for (size_t p = 0; p < P; ++p) {
+      rdamd_partition_t *part = _partitions[p];
+      const unsigned K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part);
+      const partition_parameters_t &pp = params[p];
+      const bool free_rates = _rate_category_types[p] == rate_category::FREE;
+      rdamd_update_clvs(part, ops.data(), n_ops);
+      if (rdamd_errno()) fail("update_clvs");
+      lh += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
+                                             _param_indicies[p].data(), nullptr);
+      if (rdamd_errno()) fail("compute_root_loglikelihood");
+      std::vector<double> pair((size_t)n_ops * 2 * R * K * K), root((size_t)R * K), cat(R);
+      if (rdamd_branch_pair_sums(part, ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), root.data(),
+                                 cat.data()) != RDAMD_SUCCESS)
+        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+      // pi and w as set_model_params applied them
+      model_params_t pi(pp.freqs), w(_rate_weights[p]);
+      double xsum = 0.0, usum = 1.0;
+      for (double f : pi) xsum += f;
+      for (double &f : pi) f /= xsum;
+      if (free_rates) {
+        w = pp.gamma_weights;
+        usum = 0.0;
+        for (double f : w) usum += f;
+        for (double &f : w) f /= usum;
+      }
+      std::vector<double> d_pi(K), d_rho(R), d_w(R);
+      partition_parameters_t &g = out[p];
+      g.subst_rates.assign(pp.subst_rates.size(), 0.0);
+      g.freqs.assign(pp.freqs.size(), 0.0);
+      g.gamma_alpha.assign(pp.gamma_alpha.size(), 0.0);
+      g.gamma_weights.assign(pp.gamma_weights.size(), 0.0);
+      const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
+      if (rdamd_gradient_from_pair_sums(K, R, 1, n_ops, pair.data(), root.data(), cat.data(), lengths.data(),
+                                        pp.subst_rates.data(), pi.data(), zeros.data(), zeros.data(), _rate_rates[p].data(),
+                                        w.data(), g.subst_rates.data(), d_pi.data(), d_rho.data(), d_w.data()) != RDAMD_SUCCESS)
+        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+      double mean = 0.0;
+      for (unsigned i = 0; i < K; ++i) mean += pi[i] * d_pi[i];
+      for (unsigned i = 0; i < K; ++i) g.freqs[i] = (d_pi[i] - mean) / xsum;
+      if (free_rates) {
+        mean = 0.0;
+        for (unsigned r = 0; r < R; ++r) mean += w[r] * d_w[r];
+        for (unsigned r = 0; r < R; ++r) g.gamma_weights[r] = (d_w[r] - mean) / usum;
+      } else if (!pp.gamma_alpha.empty()) {
+        const double alpha = pp.gamma_alpha[0], h = 1e-6 * std::max(1.0, alpha);
+        std::vector<double> up(R), down(R);
+        rdamd_compute_gamma_cats(alpha + h, R, up.data(), RDAMD_GAMMA_RATES_MEDIAN);
+        rdamd_compute_gamma_cats(alpha - h, R, down.data(), RDAMD_GAMMA_RATES_MEDIAN);
+        double ga = 0.0;
+        for (unsigned r = 0; r < R; ++r) ga += d_rho[r] * (up[r] - down[r]) / (2.0 * h);
+        g.gamma_alpha[0] = ga;
+      }
+    }
+    if (lnl) *lnl = lh;
+  });
+  return out;
+}
+
 // compute_lh for the searches, between optimize_params and the root-only steps: the same
 // value for the caller's convergence test, but only what those steps read is left behind --
 // the CLVs and scalers of the root's two children (rdamd_evaluate_root_children: one job of

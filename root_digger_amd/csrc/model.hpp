@@ -165,6 +165,14 @@ public:
   // bounds == nullptr: the derivatives at the schedule's own lengths (lnl_before = lnl_after)
   branch_lengths_t branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                                   const branch_bounds_t *bounds);
+  // The exact gradient of lnL at root rl in the variables L-BFGS-B sees in bfgs_params: the
+  // substitution rates as given, the unnormalised frequency vector, alpha through the MEDIAN gamma
+  // rates, the unnormalised weights of a FREE partition (whose alpha entry is 0: its rates are
+  // inert).  grad has the layout of params; *lnl: the log-likelihood there.  One materialising
+  // traversal, the root lnL, rdamd_branch_pair_sums per partition and the host assembly of
+  // param_gradient.hpp.  Saves and restores what branch_lengths does.
+  std::vector<partition_parameters_t> gradient(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
+                                               double *lnl);
 
   // batched objective: lnL of (root, parameter set) pairs, all partitions,
   // through rdamd_evaluate_batch (one fused launch per partition)

@@ -461,6 +461,23 @@ int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t
     return RDAMD_SUCCESS;
   })
 }
+int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts, const double *values,
+                         double *grad_out, double *lnl_out) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_gradient")) return RDAMD_FAILURE;
+    if (!rl || !counts || !values || !grad_out)
+      throw std::invalid_argument("rdamd_model_gradient: null argument (the parameters are required: the gradient is "
+                                  "taken in the optimiser's variables, which the model does not keep)");
+    const std::vector<rdamd::partition_parameters_t> params = one_root_params(m, counts, values);
+    double lnl = 0.0;
+    const std::vector<rdamd::partition_parameters_t> g = m->model->gradient(to_cpp(rl), params, &lnl);
+    for (const rdamd::partition_parameters_t &pp : g)
+      for (const rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights})
+        grad_out = std::copy(v->begin(), v->end(), grad_out);
+    if (lnl_out) *lnl_out = lnl;
+    return RDAMD_SUCCESS;
+  })
+}
 int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                                         const double *values, double min_len, double max_len, double atol,
                                         unsigned int max_iters, double *lengths_out, double *d1_out, double *d2_out,

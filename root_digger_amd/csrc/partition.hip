@@ -1238,6 +1238,72 @@ int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops,
   return RDAMD_SUCCESS;
 }
 
+static thread_local double g_pair_sums_ms = 0.0;
+
+double rdamd_pair_sums_last_ms(void) { return g_pair_sums_ms; }
+
+int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                           const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
+                           double *root_out, double *cat_out) {
+  clear_error();
+  g_pair_sums_ms = 0.0;
+  const std::initializer_list<RateIndices> indices = {{freqs_indices, "freqs"}};
+  OuterPlan plan;
+  if (!preorder_admitted(p, "rdamd_branch_pair_sums", ops, n_ops, !ops || !freqs_indices, indices, &plan))
+    return RDAMD_FAILURE;
+  if (!pair_out) {
+    set_error(67, "rdamd_branch_pair_sums: pair_out is null");
+    return RDAMD_FAILURE;
+  }
+  const size_t R = p->rate_cats, KA = p->api_states;
+  std::fill(pair_out, pair_out + (size_t)n_ops * 2 * R * KA * KA, 0.0);
+  if (root_out) std::fill(root_out, root_out + R * KA, 0.0);
+  if (cat_out) std::fill(cat_out, cat_out + R, 0.0);
+  if (p->sites == 0 || n_ops == 0) return RDAMD_SUCCESS;
+  // passes over whole workgroups: as many rows of partials as the bound holds, never less than one
+  const size_t entries = pair_sum_doubles(p, n_ops);
+  if (workspace_bytes == 0) workspace_bytes = (size_t)256 << 20;
+  const unsigned blocks = preorder_blocks(p);
+  const unsigned per_pass =
+      (unsigned)std::min<size_t>(blocks, std::max<size_t>(1, workspace_bytes / (entries * sizeof(double))));
+  DeviceArray<double> partials, stage, sums;
+  DeviceArray<unsigned> bad_sites;
+  const auto allocate = [&] {
+    hipError_t e = partials.alloc(entries * per_pass);
+    if (e == hipSuccess) e = stage.alloc(std::max<size_t>(1, pair_sum_stage_doubles(p, per_pass)));
+    if (e == hipSuccess) e = sums.alloc(entries);
+    if (e == hipSuccess) e = bad_sites.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(bad_sites.d, 0, sizeof(unsigned), p->stream);
+    return e;
+  };
+  const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    return launch_pair_sum_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_work, partials.d, stage.d, per_pass,
+                                   bad_sites.d, sums.d);
+  };
+  if (preorder_run(p, plan, indices, &g_pair_sums_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
+  unsigned bad = 0;
+  RDAMD_HIP_TRY(hipMemcpy(&bad, bad_sites.d, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (bad) {
+    g_pair_sums_ms = 0.0;   // (a call that returns nothing reports no time)
+    set_error(65, "rdamd_branch_pair_sums: %u of %u sites have a likelihood that is 0 or not finite; no sum is returned",
+              bad, p->sites);
+    return RDAMD_FAILURE;
+  }
+  std::vector<double> host(entries);
+  RDAMD_HIP_TRY(hipMemcpy(host.data(), sums.d, sizeof(double) * entries, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  // the caller's states are the first KA of the walk's 4
+  for (size_t b = 0; b < (size_t)n_ops * 2 * R; ++b)
+    for (size_t i = 0; i < KA; ++i)
+      for (size_t j = 0; j < KA; ++j) pair_out[(b * KA + i) * KA + j] = host[b * 16 + i * 4 + j];
+  const double *root = host.data() + (size_t)n_ops * 2 * R * 16;
+  for (size_t r = 0; r < R; ++r) {
+    if (root_out)
+      for (size_t i = 0; i < KA; ++i) root_out[r * KA + i] = root[r * 5 + i];
+    if (cat_out) cat_out[r] = root[r * 5 + 4];
+  }
+  return RDAMD_SUCCESS;
+}
+
 int rdamd_site_rate_posteriors(rdamd_partition_t *p, unsigned int clv_index, int scaler_index,
                                const unsigned int *freqs_indices, double *cat_out, double *mean_rate_out) {
   clear_error();

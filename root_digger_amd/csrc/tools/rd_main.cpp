@@ -43,6 +43,12 @@
 // back into the search): <prefix>.brlen.tsv, one row per branch with the input and the optimised length
 // and both derivatives at the optimum; <prefix>.brlen.tree, the rooted tree with the optimised lengths.
 //
+// --gradient (new here, with --exhaustive): after the search rank 0 takes the best record's root and
+// parameters from the checkpoint and writes the exact gradient of lnL there in the variables the
+// search's L-BFGS-B sees (rdamd_model_gradient): <prefix>.gradient.tsv, one row per parameter with its
+// value, the exact gradient, the forward difference with the search's own step h = max(1e-4 |x|, 1e-4)
+// and whether the value sits at the optimiser's bound; one line with the largest projected component.
+//
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
 #include <chrono>
@@ -82,7 +88,7 @@ struct options_t {
   // what the best root implies: ancestral states (.ancestral.tsv, .ancestral.tree), site rates (.siterates.tsv)
   bool ancestral = false, site_rates = false;
   // the ML branch lengths at the best root (.brlen.tsv, .brlen.tree) and their box
-  bool branch_lengths = false;
+  bool branch_lengths = false, gradient = false;   // gradient: the exact gradient at the best record (.gradient.tsv)
   double brlen_min = 1e-6, brlen_max = 100.0;
   uint64_t rell_seed = 0;
 };
@@ -110,7 +116,9 @@ void usage() {
       "  --ancestral   (with --exhaustive: ancestral state posteriors at the best root, <prefix>.ancestral.tsv / .tree)\n"
       "  --site-rates   (with --exhaustive: posterior mean rate of every column at the best root, <prefix>.siterates.tsv)\n"
       "  --branch-lengths [--brlen-min <X>] [--brlen-max <X>]   (with --exhaustive: ML branch lengths at the best root,\n"
-      "                <prefix>.brlen.tsv / .tree)");
+      "                <prefix>.brlen.tsv / .tree)\n"
+      "  --gradient   (with --exhaustive: exact gradient of lnL in the model parameters at the best record,\n"
+      "                <prefix>.gradient.tsv)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -139,6 +147,7 @@ options_t parse(int argc, char **argv) {
       {"au", no_argument, 0, 0},                 {"ancestral", no_argument, 0, 0},
       {"site-rates", no_argument, 0, 0},         {"branch-lengths", no_argument, 0, 0},
       {"brlen-min", required_argument, 0, 0},    {"brlen-max", required_argument, 0, 0},
+      {"gradient", no_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -190,6 +199,7 @@ options_t parse(int argc, char **argv) {
     else if (name == "ancestral") o.ancestral = true;
     else if (name == "site-rates") o.site_rates = true;
     else if (name == "branch-lengths") o.branch_lengths = true;
+    else if (name == "gradient") o.gradient = true;
     else if (name == "brlen-min") o.brlen_min = std::atof(v);
     else if (name == "brlen-max") o.brlen_max = std::atof(v);
     else if (name == "site-reduce") {
@@ -230,7 +240,8 @@ static int run(int argc, char **argv) {
   // the candidates' records and parameters are read back from the checkpoint; a site group's
   // member holds one block of the columns
   const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : o.ancestral ? "--ancestral"
-                            : o.site_rates ? "--site-rates" : o.branch_lengths ? "--branch-lengths" : nullptr;
+                            : o.site_rates ? "--site-rates" : o.branch_lengths ? "--branch-lengths"
+                            : o.gradient ? "--gradient" : nullptr;
   const bool site_support = o.rell_given || o.site_lh;   // the site lnLs of every candidate are wanted
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
   if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
@@ -821,6 +832,49 @@ static int run(int argc, char **argv) {
     std::snprintf(line, sizeof line, "Branch lengths at root %llu: lnL before %.6f, after %.6f, iterations %u, evaluations %u, "
                   "converged %d, %.3f s; written to: %s.brlen.tsv %s.brlen.tree", (unsigned long long)best.id, before, after,
                   iterations, evaluations, converged, seconds, o.prefix.c_str(), o.prefix.c_str());
+    std::cout << line << std::endl;
+  }
+  // ---- the exact gradient at the best record, beside the forward difference the search took there
+  if (o.gradient) {
+    std::vector<uint64_t> counts;
+    std::vector<double> values;
+    best_record_params(counts, values);
+    const size_t n_parts = counts.size() / 4;
+    size_t n_values = 0;
+    for (uint64_t c : counts) n_values += c;
+    std::vector<double> grad(n_values + 1, 0.0);
+    double lnl = 0.0;
+    need(rdamd_model_gradient(model, &best, counts.data(), values.data(), grad.data(), &lnl), "gradient");
+    // the optimiser's box and step (model.cpp, optimize_params): rates, frequencies, alpha; weights are not searched
+    const char *field[4] = {"subst_rate", "freq", "alpha", "weight"};
+    const double lo[4] = {1e-4, 1e-4, 0.2, -INFINITY}, hi[4] = {1e4, 1.0 - 1e-4 * 3, 10000.0, INFINITY};
+    std::FILE *f = std::fopen((o.prefix + ".gradient.tsv").c_str(), "w");
+    if (!f) die("could not write " + o.prefix + ".gradient.tsv");
+    std::fprintf(f, "partition\tname\tvalue\tgradient\tforward_difference\tat_bound\n");
+    double worst = 0.0;
+    std::string worst_name = "-";
+    size_t at = 0;
+    for (size_t p = 0; p < n_parts; ++p)
+      for (unsigned k = 0; k < 4; ++k)
+        for (uint64_t i = 0; i < counts[4 * p + k]; ++i, ++at) {
+          const double x = values[at], g = grad[at], h = std::max(1e-4 * std::fabs(x), 1e-4);
+          std::vector<double> moved(values);
+          moved[at] = x + h;
+          double up = 0.0;
+          need(rdamd_model_branch_derivatives(model, &best, counts.data(), moved.data(), nullptr, nullptr, nullptr, nullptr,
+                                              nullptr, nullptr, nullptr, &up), "lnL at a moved parameter");
+          const char *bound = x <= lo[k] ? "min" : x >= hi[k] ? "max" : "no";
+          // a component that points out of the box at a bound is not a direction the optimiser has (it maximises lnL)
+          const double projected = (x <= lo[k] && g < 0.0) || (x >= hi[k] && g > 0.0) ? 0.0 : g;
+          const std::string name = std::string(field[k]) + "_" + std::to_string(i);
+          if (std::fabs(projected) > std::fabs(worst)) { worst = projected; worst_name = "partition " + std::to_string(p) + " " + name; }
+          std::fprintf(f, "%zu\t%s\t%.17g\t%.17g\t%.10e\t%s\n", p, name.c_str(), x, g, (up - lnl) / h, bound);
+        }
+    std::fclose(f);
+    char line[512];
+    std::snprintf(line, sizeof line, "Gradient at root %llu: lnL %.6f, %zu parameters, largest projected component %.6e (%s); "
+                  "written to: %s.gradient.tsv", (unsigned long long)best.id, lnl, n_values, worst, worst_name.c_str(),
+                  o.prefix.c_str());
     std::cout << line << std::endl;
   }
   rdamd_tree_t *out = rdamd_tree_from_file(o.tree.c_str());
