@@ -1153,6 +1153,88 @@ int rdamd_gradient_from_pair_sums(unsigned int states, unsigned int rate_cats, u
 int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                          const double *values, double *grad_out, double *lnl_out);
 
+/* ------------------------------------------------------------------------
+ * Substitutions mapped onto branches: per site, the joint posterior of a branch's two ends and the
+ * expected number of substitutions on it; per branch, the expected number of substitutions of every
+ * type and the expected time spent in every state.  NEW relative to the reference.  Under a rooted
+ * non-reversible model the direction of a substitution is identified; under a reversible one
+ * i -> j and j -> i on a branch cannot be told apart.
+ *
+ * Notation of the three sections above.  The tree is rooted as the operation list says.  Branch
+ * (k, c) lies above child a = child c of node k, has sibling b and length tau.  For rate category
+ * r: rate rho_r, weight w_r, Q_r = Q[params_indices[r]], X_r = rho_r tau Q_r, P_r = exp(X_r);
+ *   t_r[i] = U_u[i] (P_b L_b)[i]          L_r = L_a,r (a tip's: its 0/1 code vector)
+ *   f0(s)  = sum_r w_r t_r . (P_r L_r)    weight_s: the pattern weight
+ * Per site, for every branch, tip branches included:
+ *   J_s[i][j] = sum_r w_r t_r[i] P_r[i][j] L_r[j] / f0(s)   the posterior probability that the branch
+ *               starts in state i and ends in state j; sum_ij J_s = 1
+ *   change_s  = sum_{i != j} J_s[i][j]
+ *   top pair: the pair i != j with the largest J_s[i][j], as the code i K + j (K: the caller's state
+ *               count); the smallest code wins an exact tie.  top_prob_s: that largest value
+ *   n_s       = sum_r w_r t_r^T C_r L_r / f0(s),  C_r = F(X_r, offdiag(X_r)): the expected number of
+ *               substitutions at the site on the branch, multiple hits included
+ *   F(X, E) = integral_0^1 exp(xX) E exp((1 - x)X) dx, as in rdamd_gradient_from_pair_sums
+ * The 2^256 rule on U and the CLVs' scalers act per site over all rates and cancel.  No scaler is
+ * read.
+ * Per branch, from the pair sums N of rdamd_branch_pair_sums, with F_r = F(X_r^T, N[k][c][r]):
+ *   E[k][c][i][j] = sum_r X_r[i][j] F_r[i][j], i != j: the expected number of i -> j substitutions
+ *               on the branch over the whole alignment
+ *   D[k][c][i]    = tau sum_r F_r[i][i]: the expected time spent in state i, in branch-length units
+ * Identities:
+ *   A  sum_s weight_s n_s = sum_{i != j} E[i][j]
+ *   B  sum_s weight_s J_s[i][j] = sum_r N_r[i][j] P_r[i][j]
+ *   C  tau d1 = sum_{i != j} E[i][j] + sum_r sum_i X_r[i][i] F_r[i][i],  d1 of rdamd_branch_derivatives
+ *   D  sum_i D[i] = tau sum_s weight_s
+ * ---------------------------------------------------------------------- */
+/* change_out, count_out, top_prob_out[n_ops][2][sites], top_pair_out[n_ops][2][sites] (bytes) and
+ * joint_out[n_ops][2][sites][K][K], nodes as rdamd_marginal_ancestral_nodes orders them; each may be
+ * NULL and is then not written.  lengths[n_ops][2]: the length of branch (k, c).  THESE MUST BE THE
+ * LENGTHS THE P-MATRICES OF THE LIST WERE LAST BUILT WITH (rdamd_update_prob_matrices, with these
+ * params_indices): the partition does not keep them, and the count matrices C_r are made from them on
+ * the host (one block exponential per branch and rate category) and uploaded.  Otherwise the
+ * preconditions and refusals of rdamd_branch_derivatives: error 63 for 20-state partitions and
+ * RDAMD_ATTRIB_SPARSE_CLVS, 64 for a NULL input, a list that is not a complete post-order traversal
+ * ending in the root operation or a length that is negative or not finite, 10 / 7 for indices out
+ * of range, 65 when a site's f0 is 0 or not finite (nothing is returned).  4-state and binary
+ * partitions; binary ones get [2][2] joints and codes 2 i + j.  One launch of the pre-order program;
+ * nothing is summed over sites, so there is no second launch and two calls with the same inputs
+ * return the same bits.  Nothing in the partition is written.  Zero sites: success. */
+int rdamd_branch_substitutions(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                               const unsigned int *params_indices, const unsigned int *freqs_indices,
+                               const double *lengths, double *change_out, double *count_out,
+                               unsigned char *top_pair_out, double *top_prob_out, double *joint_out);
+/* device time of the launch of this thread's last rdamd_branch_substitutions call, milliseconds
+ * between two HIP events (0 after a failed call); for measurements */
+double rdamd_branch_substitutions_last_ms(void);
+/* E and D from the pair sums: plain host code, a pure function of its arguments, no device needed.
+ * states K in {2, ..., 64}; pair[n_ops][2][R][K][K], lengths[n_ops][2], subst[rate_matrices][K K - K],
+ * freqs[rate_matrices][K], params_indices[R], rates[R] as rdamd_gradient_from_pair_sums takes them.
+ * typed_out[n_ops][2][K][K]: the off-diagonal entries are E, the diagonal entries are D.  Returns
+ * RDAMD_SUCCESS, or RDAMD_FAILURE with error 64 for a NULL argument, a state count out of range or
+ * a length that is negative or not finite, 7 for an index >= rate_matrices. */
+int rdamd_substitution_counts_from_pair_sums(unsigned int states, unsigned int rate_cats, unsigned int rate_matrices,
+                                             unsigned int n_ops, const double *pair, const double *lengths,
+                                             const double *subst, const double *freqs,
+                                             const unsigned int *params_indices, const double *rates,
+                                             double *typed_out);
+/* All of it for one root of a model.  counts / values: the parameters in the checkpoint's layout
+ * exactly as rdamd_model_gradient takes them (required).  Outputs, any of which may be NULL:
+ * *n_nodes, node_clv, node_parent, node_children, lengths_out[n][2] as
+ * rdamd_model_branch_derivatives gives them; typed_out: one [n][2][K][K] block per partition, back
+ * to back in partition order, K the partition's state count; change_out, count_out,
+ * top_prob_out[n][2][P_total] and top_pair_out[n][2][P_total] (bytes) with the patterns of all
+ * partitions concatenated in partition order (rdamd_model_site_patterns); *lnl_out: the
+ * log-likelihood at that root.  Each partition: rdamd_update_prob_matrices, a materialising
+ * traversal, rdamd_branch_pair_sums, rdamd_substitution_counts_from_pair_sums and
+ * rdamd_branch_substitutions.  The model's parameters, its rooting and the conditional likelihoods
+ * of that rooting are as before when the call returns.  Refused (error 61) for a model that sums
+ * over a site group; a partition whose shape rdamd_branch_substitutions refuses fails the call and
+ * is named in the message. */
+int rdamd_model_substitutions(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                              const double *values, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
+                              unsigned int *node_children, double *lengths_out, double *typed_out, double *change_out,
+                              double *count_out, unsigned char *top_pair_out, double *top_prob_out, double *lnl_out);
+
 /* Column that draw d (0 <= d < N) of bootstrap replicate b resamples, N < 2^32 columns.
  * Stateless and counter-based (all arithmetic mod 2^64):
  *   sm(x):  x += 0x9E3779B97F4A7C15; z = x;

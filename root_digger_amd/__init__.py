@@ -51,6 +51,8 @@ from .api import (  # noqa: F401
     branch_last_ms,
     pair_sums_last_ms,
     gradient_from_pair_sums,
+    branch_substitutions_last_ms,
+    substitution_counts,
     rell_tests,
     rell_last_tests_ms,
     rell_scale_seed,
@@ -71,7 +73,7 @@ __all__ = [
     "device_count", "hip_runtime_path", "mapped_hip_runtimes", "set_device", "device_memory", "msa_probe",
     "rank_order_sum", "COMM_SUM_GATHER", "COMM_SUM_ALLREDUCE",
     "msa_pattern_probe", "rell_column", "rell_bootstrap", "rell_last_resample_ms", "ancestral_nodes", "ancestral_workspace_slots", "ancestral_last_ms", "branch_last_ms",
-    "pair_sums_last_ms", "gradient_from_pair_sums",
+    "pair_sums_last_ms", "gradient_from_pair_sums", "branch_substitutions_last_ms", "substitution_counts",
     "rell_tests", "rell_last_tests_ms", "rell_scale_seed", "rell_multiscale", "rell_last_multiscale_ms",
     "au_scales", "au_fit", "au_test", "elw_confidence_set",
 ]

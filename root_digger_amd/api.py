@@ -310,6 +310,12 @@ _sig("rdamd_branch_pair_sums",C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd,
 _sig("rdamd_pair_sums_last_ms", C.c_double)
 _sig("rdamd_gradient_from_pair_sums", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pd, _pd, _pd, _pd,
      _pd, _pd)
+_pub = C.POINTER(C.c_ubyte)
+_sig("rdamd_branch_substitutions", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd, _pd, _pub, _pd, _pd)
+_sig("rdamd_branch_substitutions_last_ms", C.c_double)
+_sig("rdamd_substitution_counts_from_pair_sums", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pu, _pd, _pd)
+_sig("rdamd_model_substitutions", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd, _pd, _pd,
+     _pub, _pd, _pd)
 _sig("rdamd_model_branch_derivatives", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd,
      _pd, _pd)
 _sig("rdamd_model_optimize_branch_lengths", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, C.c_double, C.c_double,
@@ -819,6 +825,29 @@ class Partition:
             _fail("branch_pair_sums")
         return pair, root, cat
 
+    def branch_substitutions(self, ops, lengths, params_indices=None, freqs_indices=None, joint=False):
+        """Substitutions mapped onto the branches, per site (rdamd_branch_substitutions) -> dict with
+        change, count, top_prob [len(ops)][2][sites] (float64), top_pair [len(ops)][2][sites] (uint8, the
+        code i K + j) and, with joint=True, joint [len(ops)][2][sites][K][K]: branch (k, c) above child c of
+        node k, nodes as ancestral_nodes orders them.  lengths[len(ops)][2]: the lengths the P-matrices
+        of the list were last built with.  Call update_prob_matrices and update_clvs on this list first."""
+        ops = _op_array(ops)
+        pi = self.params_indices if params_indices is None else np.ascontiguousarray(params_indices, dtype=np.uint32)
+        fi = pi if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        lengths = np.ascontiguousarray(lengths, dtype=np.float64)
+        if lengths.shape != (len(ops), 2):
+            raise ValueError("branch_substitutions: lengths[len(ops)][2] is wanted")
+        n, S, K = len(ops), self.sites, self.states
+        out = {"change": np.zeros((n, 2, S)), "count": np.zeros((n, 2, S)), "top_pair": np.zeros((n, 2, S), dtype=np.uint8),
+               "top_prob": np.zeros((n, 2, S))}
+        if joint:
+            out["joint"] = np.zeros((n, 2, S, K, K))
+        if lib.rdamd_branch_substitutions(self._h, ops, n, _uptr(pi), _uptr(fi), _dptr(lengths), _dptr(out["change"]),
+                                          _dptr(out["count"]), out["top_pair"].ctypes.data_as(_pub), _dptr(out["top_prob"]),
+                                          _dptr(out["joint"]) if joint else None) != 1:
+            _fail("branch_substitutions")
+        return out
+
     def site_rate_posteriors(self, clv_index, scaler_index=SCALE_BUFFER_NONE, freqs_indices=None):
         """(cat[sites][R], mean_rate[sites]): posterior of every rate category and posterior mean rate of
         every site, from the root CLV (rdamd_site_rate_posteriors)."""
@@ -1178,6 +1207,34 @@ def gradient_from_pair_sums(pair, root, cat, lengths, subst, freqs, params_indic
                                          _dptr(d_freqs), _dptr(d_rates), _dptr(d_weights)) != 1:
         _fail("gradient_from_pair_sums")
     return d_subst, d_freqs, d_rates, d_weights
+
+
+def branch_substitutions_last_ms():
+    """device milliseconds of the launch of this thread's last branch_substitutions call"""
+    return float(lib.rdamd_branch_substitutions_last_ms())
+
+
+def substitution_counts(pair, lengths, subst, freqs, params_indices, rates):
+    """typed[n][2][K][K] from the pair sums of branch_pair_sums (rdamd_substitution_counts_from_pair_sums;
+    host only): off the diagonal the expected number of i -> j substitutions on branch (k, c) over the
+    whole alignment, on the diagonal the expected time spent in state i.  subst[m], freqs[m]: the
+    rate-matrix sets; frequencies enter exactly as given."""
+    pair = np.ascontiguousarray(pair, dtype=np.float64)
+    n, _, R, K, _ = pair.shape
+    lengths, rates = (np.ascontiguousarray(v, dtype=np.float64) for v in (lengths, rates))
+    subst = np.ascontiguousarray(subst, dtype=np.float64).reshape(-1, K * K - K)
+    freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1, K)
+    sets = subst.shape[0]
+    if freqs.shape[0] != sets or lengths.shape != (n, 2) or rates.shape != (R,):
+        raise ValueError("substitution_counts: shapes do not fit the pair sums")
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if pi.shape != (R,):
+        raise ValueError("substitution_counts: one index per rate category")
+    typed = np.zeros((n, 2, K, K), dtype=np.float64)
+    if lib.rdamd_substitution_counts_from_pair_sums(K, R, sets, n, _dptr(pair), _dptr(lengths), _dptr(subst), _dptr(freqs),
+                                                    _uptr(pi), _dptr(rates), _dptr(typed)) != 1:
+        _fail("substitution_counts")
+    return typed
 
 
 def rell_last_resample_ms():
@@ -1715,6 +1772,36 @@ class Model:
                 at += int(n)
             out.append(d)
         return out, lnl.value
+
+    def substitutions(self, rl, params):
+        """Substitutions mapped onto the branches at root rl (rdamd_model_substitutions) -> dict with
+        node_clv[n], node_parent[n], node_children[n][2], lengths[n][2], typed (the list of the
+        partitions' [n][2][K][K] arrays: expected i -> j counts off the diagonal, dwell times on it),
+        change, count, top_prob, top_pair [n][2][P_total] (patterns of all partitions concatenated) and
+        lnl.  params: the per-partition dicts Checkpoint.read_results returns for one root (required).
+        Nothing is applied to the model."""
+        counts, values = _flatten_params(list(params))
+        n = self._tree.tip_count() - 1
+        total = sum(self.partition_shape(p)[0] for p in range(self.partition_count()))
+        ks = [int(round((1 + (1 + 4 * int(c)) ** 0.5) / 2)) for c in np.asarray(counts).reshape(-1, 4)[:, 0]]
+        out = {"node_clv": np.zeros(n, dtype=np.uint32), "node_parent": np.zeros(n, dtype=np.int32),
+               "node_children": np.zeros((n, 2), dtype=np.uint32), "lengths": np.zeros((n, 2))}
+        typed = np.zeros(max(1, sum(n * 2 * k * k for k in ks)))
+        for key in ("change", "count", "top_prob"):
+            out[key] = np.zeros((n, 2, total))
+        out["top_pair"] = np.zeros((n, 2, total), dtype=np.uint8)
+        nn, lnl = C.c_uint(0), C.c_double(0.0)
+        self._ok(lib.rdamd_model_substitutions(self._h, C.byref(rl), counts.ctypes.data_as(_pu64), _dptr(values), C.byref(nn),
+                                               _uptr(out["node_clv"]), out["node_parent"].ctypes.data_as(_pi),
+                                               _uptr(out["node_children"]), _dptr(out["lengths"]), _dptr(typed),
+                                               _dptr(out["change"]), _dptr(out["count"]),
+                                               out["top_pair"].ctypes.data_as(_pub), _dptr(out["top_prob"]), C.byref(lnl)),
+                 "substitutions")
+        assert nn.value == n
+        cuts = np.cumsum([0] + [n * 2 * k * k for k in ks])
+        out["typed"] = [typed[cuts[i]:cuts[i + 1]].reshape(n, 2, k, k).copy() for i, k in enumerate(ks)]
+        out["lnl"] = lnl.value
+        return out
 
     def optimize_branch_lengths(self, rl, params=None, min_len=1e-6, max_len=100.0, atol=1e-8, max_iters=200):
         """The branch lengths in [min_len, max_len] that maximise lnL at root rl and fixed parameters

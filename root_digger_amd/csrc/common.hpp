@@ -307,6 +307,14 @@ hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, un
                                    const unsigned *d_fidx, double *d_work, double *d_partials, double *d_stage,
                                    unsigned blocks_per_pass, unsigned *d_bad_sites, double *d_out);
 
+// substitutions mapped onto the branches of the same program, per site: d_cmat: the count matrices
+// [nops][2][R][16] of program operation k's two children (subst_map.hpp); the outputs, any of which
+// may be null: d_change, d_count, d_top_pair, d_top_prob [nops][2][sites] and d_joint
+// [nops][2][sites][api_states][api_states]; *d_bad_sites as launch_brlen_program's
+hipError_t launch_subst_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_fidx, double *d_work, const double *d_cmat, unsigned *d_bad_sites,
+                                double *d_change, double *d_count, uint8_t *d_top_pair, double *d_top_prob, double *d_joint);
+
 // kernels_root.hip
 // The grid every root reduction is laid out over: one lane per (site, rate) -- the group layout --
 // or per site, in workgroups of 256 lanes, at most 1024 of them (a lane strides beyond that), never 0.

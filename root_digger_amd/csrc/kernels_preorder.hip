@@ -1,7 +1,7 @@
-// The pre-order pass: OUTER vectors, and what three analyses make of them -- marginal ancestral
-// state posteriors, the first and second derivative of lnL in every branch length, and the pair
-// sums (the derivative of lnL in every entry of every P-matrix).  Also the site-rate posteriors,
-// which need the root CLV alone.
+// The pre-order pass: OUTER vectors, and what four analyses make of them -- marginal ancestral
+// state posteriors, the first and second derivative of lnL in every branch length, the pair
+// sums (the derivative of lnL in every entry of every P-matrix) and the substitutions mapped onto
+// every branch per site.  Also the site-rate posteriors, which need the root CLV alone.
 //
 // New here -- the reference computes no ancestral states and has one derivative, the forward
 // difference of its compute_dlh (src/model.cpp), for the root's position alone; this pass extends
@@ -25,7 +25,7 @@
 // registers, any other waits in a workspace slot (host-side liveness analysis).  The partition is
 // only read.
 //
-// A CONSUMER is a functor the walk calls at fixed places.  There are three:
+// A CONSUMER is a functor the walk calls at fixed places.  There are four:
 //   posteriors   post[v][s][j] = sum_r w_r U_v[j] L_v[j], normalised over j: the root's from pi
 //                before the loop, an inner child's where its outer vector is formed, its CLV
 //                being in registers already.
@@ -41,6 +41,10 @@
 //                operation (the one consumer that reads the child's own vector in `branch`), and
 //                the root's M and W before the loop; summed as the derivatives are, in passes over
 //                ranges of whole workgroups (definitions above PairSumDna).
+//   substitutions  per site and branch: the joint posterior of the branch's two ends, the
+//                probability of a change, the likeliest change and the expected number of
+//                substitutions (definitions above SubstArgs); the one consumer that reads the
+//                child's staged P-matrix, which `branch` gets as its last argument.  No sums over sites.
 // A consumer names its arguments (Args), the LDS it wants beside the walk's (Lds; empty: none is
 // allocated) and whether it is told of tip children (kTipBranches) and sums over the workgroup
 // (kBlockSums, generic walk); its hooks are begin, op_begin, branch, (branch_done,) outer, op_end
@@ -224,7 +228,7 @@ preorder_dna_walk(WalkArgs a, typename Consumer::Args ca) {
       double t[4], uc[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];   // the parent's vector masked by the sibling
-      con.branch(ln, c, t, pl[c], l[c]);
+      con.branch(ln, c, t, pl[c], l[c], m);
       if (!op.inner[c]) continue;
 #pragma unroll
       for (int j = 0; j < 4; ++j) uc[j] = t[0] * m[j] + t[1] * m[4 + j] + t[2] * m[8 + j] + t[3] * m[12 + j];
@@ -299,7 +303,7 @@ preorder_generic_walk(WalkArgs a, typename Consumer::Args ca, unsigned R) {
           if (!op.inner[c] && !Consumer::kTipBranches) continue;
           double t[4];
           for (int i = 0; i < 4; ++i) t[i] = up[i] * pl[1 - c][i];
-          con.branch(a, c, r, t, pl[c], l[c]);
+          con.branch(a, c, r, t, pl[c], l[c], a.pmat + ((size_t)op.child_mat[c] * R + r) * 16);
           if (!op.inner[c]) continue;
           const double *m = a.pmat + ((size_t)op.child_mat[c] * R + r) * 16;
           for (int j = 0; j < 4; ++j) {
@@ -354,7 +358,7 @@ struct PosteriorDna {
   }
   __device__ __forceinline__ void op_begin(const WalkArgs &, const DnaLane &, unsigned) const {}
   __device__ __forceinline__ void branch(const DnaLane &, int, const double (&)[4], const double (&)[4],
-                                         const double (&)[4]) const {}
+                                         const double (&)[4], const double *) const {}
   __device__ __forceinline__ void outer(const WalkArgs &a, const DnaLane &ln, unsigned node, const double (&uc)[4],
                                         const double (&l)[4]) const {
     write_post(a, ln, node, uc, l);
@@ -387,7 +391,7 @@ struct PosteriorGeneric {
   }
   __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned, unsigned) const {}
   __device__ __forceinline__ void branch(const WalkArgs &, int, unsigned, const double (&)[4], const double (&)[4],
-                                         const double (&)[4]) const {}
+                                         const double (&)[4], const double *) const {}
   __device__ __forceinline__ void branch_done(int) const {}
   // u: the site's outer vector, [rate][4]
   __device__ __forceinline__ void outer(const WalkArgs &a, unsigned R, unsigned s, unsigned node, unsigned clv,
@@ -462,7 +466,7 @@ struct DerivativeDna {
     if (k > 0) flush_block_sums(lds.wsum[(k & 1u) ^ 1u], c.partials, a.nops, k - 1, ln.tid);
   }
   __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4],
-                                         const double (&)[4]) {
+                                         const double (&)[4], const double *) {
     double p0, p1, p2;
     branch_products(&lds.sq[ln.r * kRateStride], t, y, &p0, &p1, &p2);
     const double f0 = rate_sum<R>(ln.w * p0), f1 = rate_sum<R>(w1 * p1), f2 = rate_sum<R>(w2 * p2);
@@ -513,7 +517,7 @@ struct DerivativeGeneric {
     for (int i = 0; i < 6; ++i) f[i / 3][i % 3] = 0.0;
   }
   __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4],
-                                         const double (&)[4]) {
+                                         const double (&)[4], const double *) {
     const double w = a.rate_w[r], rho = c.rates[r];
     double p0, p1, p2;
     branch_products(c.q + (size_t)c.pidx[r] * 16, t, y, &p0, &p1, &p2);
@@ -626,7 +630,7 @@ struct PairSumDna {
     }
   }
   __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4],
-                                         const double (&l)[4]) {
+                                         const double (&l)[4], const double *) {
     const double p0 = t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3];
     double g;
     if (!site_factor(rate_sum<R>(ln.w * p0), weight, &g)) site_bad = true;
@@ -711,7 +715,7 @@ struct PairSumGeneric {
   }
   __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned, unsigned) { f0[0] = f0[1] = 0.0; }
   __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4],
-                                         const double (&)[4]) {
+                                         const double (&)[4], const double *) {
     const double w = a.rate_w[r];
     f0[ch] += w * (t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3]);
     double *o = stage(ch, r);
@@ -756,6 +760,194 @@ pair_sum_kernel(const double *__restrict__ partials, unsigned blocks, size_t ent
   for (unsigned b = 0; b < blocks; ++b) acc += partials[(size_t)b * entries + e];
   out[e] = acc;
 }
+
+// ---------------------------------------------------------------------------
+// Consumer: substitutions mapped onto branches, per site
+// ---------------------------------------------------------------------------
+//   J[i][j] = sum_r w_r t_r[i] P_r[i][j] L_a,r[j] / f0(s)     the branch starts in i and ends in j
+//   change  = sum_{i != j} J[i][j]      top pair: the largest J[i][j], i != j, the smallest code i K + j at a tie
+//   n       = sum_r w_r t_r^T C_r L_a,r / f0(s)               C_r = F(X_r, offdiag(X_r)), made on the host
+// for both children of every operation, over the caller's K states.  Nothing is summed over sites:
+// every output is written where it is formed, by vector stores, and equal inputs give equal bits.
+// The count matrices of an operation ([nops][2][R][16]) are staged in LDS one operation ahead as the
+// walk stages P: thread t fetches one double in op_begin and puts it in op_end, under the walk's
+// own barrier.
+struct SubstArgs {
+  const double *cmat;         // [nops][2][R][16], rows = parent state
+  double *change, *count;     // [nops][2][sites]; any output may be null
+  uint8_t *top_pair;
+  double *top_prob;
+  double *joint;              // [nops][2][sites][K][K]
+  unsigned *bad_sites;
+  unsigned api_states, R;
+};
+
+// change, the top pair and its probability from the 16 joint entries (K = 2: the first 2 x 2 block)
+__device__ __forceinline__ void joint_summary(const double (&J)[16], unsigned K, double *change, unsigned *code, double *top) {
+  double sum = 0.0, best = -1.0;
+  unsigned at = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (i == j || (unsigned)i >= K || (unsigned)j >= K) continue;   // (uniform)
+      const double v = J[i * 4 + j];
+      sum += v;
+      if (v > best) { best = v; at = (unsigned)i * K + (unsigned)j; }
+    }
+  *change = sum; *code = at; *top = best;
+}
+
+__device__ __forceinline__ void write_site_summary(const SubstArgs &c, size_t at, double change, double n, unsigned code,
+                                                   double top) {
+  if (c.change) c.change[at] = change;
+  if (c.count) c.count[at] = n;
+  if (c.top_pair) c.top_pair[at] = (uint8_t)code;
+  if (c.top_prob) c.top_prob[at] = top;
+}
+
+template <int R>
+struct SubstDna {
+  using Args = SubstArgs;
+  struct Lds { alignas(16) double cm[2][2][R * kRateStride]; };   // [operation parity][child][rate]
+  static constexpr bool kTipBranches = true;
+  static constexpr unsigned kOpDoubles = 2 * R * 16;   // <= 256: one per thread
+  const Args c;
+  Lds &lds;
+  unsigned k = 0, sites = 0;
+  double next_c = 0.0;
+  bool site_bad = false;
+  __device__ __forceinline__ SubstDna(const Args &c, Lds &lds) : c(c), lds(lds) {}
+
+  __device__ __forceinline__ double fetch(unsigned nops, unsigned op, unsigned tid) const {
+    if (tid >= kOpDoubles || op >= nops) return 0.0;
+    return c.cmat[(size_t)op * kOpDoubles + tid];
+  }
+  __device__ __forceinline__ void put(unsigned buf, unsigned tid, double v) const {
+    if (tid < kOpDoubles) lds.cm[buf][tid / (R * 16)][((tid % (R * 16)) / 16) * kRateStride + (tid % 16)] = v;
+  }
+  __device__ __forceinline__ void begin(const WalkArgs &a, const DnaLane &ln) {   // (the walk's first barrier follows)
+    sites = a.sites;
+    put(0, ln.tid, fetch(a.nops, 0, ln.tid));
+  }
+  __device__ __forceinline__ void op_begin(const WalkArgs &a, const DnaLane &ln, unsigned op) {
+    k = op;
+    next_c = fetch(a.nops, op + 1, ln.tid);
+  }
+  __device__ __forceinline__ void branch(const DnaLane &ln, int ch, const double (&t)[4], const double (&y)[4],
+                                         const double (&l)[4], const double *m) {
+    const double *cm = &lds.cm[k & 1u][ch][ln.r * kRateStride];
+    const double p0 = t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3];
+    double g;
+    if (!site_factor(rate_sum<R>(ln.w * p0), 1.0, &g)) site_bad = true;
+    const double gw = g * ln.w;
+    double tc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      tc += t[i] * (cm[i * 4 + 0] * l[0] + cm[i * 4 + 1] * l[1] + cm[i * 4 + 2] * l[2] + cm[i * 4 + 3] * l[3]);
+    const double n = rate_sum<R>(gw * tc);
+    double J[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double gt = gw * t[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) J[i * 4 + j] = rate_sum<R>(gt * (m[i * 4 + j] * l[j]));
+    }
+    if (!ln.active) return;   // (after the exchanges)
+    const size_t at = ((size_t)k * 2 + (unsigned)ch) * sites + ln.s;
+    if (ln.r == 0) {
+      double change, top;
+      unsigned code;
+      joint_summary(J, c.api_states, &change, &code, &top);
+      write_site_summary(c, at, change, n, code, top);
+    }
+    if (!c.joint) return;
+    if (c.api_states == 4) {   // every lane of the site holds J: lane r writes the rows i = r (mod R)
+      double2 *o = reinterpret_cast<double2 *>(c.joint + at * 16);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if ((unsigned)i % R == ln.r) {
+          o[2 * i] = make_double2(J[i * 4], J[i * 4 + 1]);
+          o[2 * i + 1] = make_double2(J[i * 4 + 2], J[i * 4 + 3]);
+        }
+    } else if (ln.r == 0) {
+      double2 *o = reinterpret_cast<double2 *>(c.joint + at * 4);
+      o[0] = make_double2(J[0], J[1]);
+      o[1] = make_double2(J[4], J[5]);
+    }
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, const DnaLane &, unsigned, const double (&)[4],
+                                        const double (&)[4]) const {}
+  __device__ __forceinline__ void op_end(const DnaLane &ln, unsigned op) const { put((op & 1u) ^ 1u, ln.tid, next_c); }
+  __device__ __forceinline__ void end(const WalkArgs &, const DnaLane &ln) const {
+    if (ln.active && ln.r == 0 && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
+// one lane per site: the sums over rates are kept unnormalised until the site's f0 is known
+struct SubstGeneric {
+  using Args = SubstArgs;
+  using Lds = NoLds;
+  static constexpr bool kTipBranches = true, kBlockSums = false;
+  const Args c;
+  unsigned k = 0, s = 0, sites = 0;
+  double f0[2], n[2], J[2][16];
+  bool site_bad = false;
+  __device__ __forceinline__ SubstGeneric(const Args &c, Lds &) : c(c) {}
+
+  __device__ __forceinline__ void begin(const WalkArgs &a, unsigned, unsigned site, bool) { s = site; sites = a.sites; }
+  __device__ __forceinline__ void op_begin(const WalkArgs &, unsigned op, unsigned) {
+    k = op;
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      f0[ch] = n[ch] = 0.0;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) J[ch][e] = 0.0;
+    }
+  }
+  __device__ __forceinline__ void branch(const WalkArgs &a, int ch, unsigned r, const double (&t)[4], const double (&y)[4],
+                                         const double (&l)[4], const double *m) {
+    const double w = a.rate_w[r];
+    const double *cm = c.cmat + (((size_t)k * 2 + (unsigned)ch) * c.R + r) * 16;
+    f0[ch] += w * (t[0] * y[0] + t[1] * y[1] + t[2] * y[2] + t[3] * y[3]);
+    double tc = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      tc += t[i] * (cm[i * 4 + 0] * l[0] + cm[i * 4 + 1] * l[1] + cm[i * 4 + 2] * l[2] + cm[i * 4 + 3] * l[3]);
+    n[ch] += w * tc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const double wt = w * t[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) J[ch][i * 4 + j] += wt * (m[i * 4 + j] * l[j]);
+    }
+  }
+  __device__ __forceinline__ void branch_done(int ch) {   // (active lanes only)
+    double g;
+    if (!site_factor(f0[ch], 1.0, &g)) site_bad = true;
+    double Jn[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) Jn[e] = g * J[ch][e];
+    const size_t at = ((size_t)k * 2 + (unsigned)ch) * sites + s;
+    double change, top;
+    unsigned code;
+    joint_summary(Jn, c.api_states, &change, &code, &top);
+    write_site_summary(c, at, change, g * n[ch], code, top);
+    if (!c.joint) return;
+    const unsigned K = c.api_states;
+    double *o = c.joint + at * K * K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if ((unsigned)i < K && (unsigned)j < K) o[(unsigned)i * K + (unsigned)j] = Jn[i * 4 + j];
+  }
+  __device__ __forceinline__ void outer(const WalkArgs &, unsigned, unsigned, unsigned, unsigned, const double *) const {}
+  __device__ __forceinline__ void op_end(unsigned, unsigned) const {}
+  __device__ __forceinline__ void end(const WalkArgs &, bool active, unsigned) const {
+    if (active && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
 
 // posterior of every rate category and the posterior mean rate of every site, from the root CLV
 // (any state count; one lane per site).  Per-site scalers cancel in the normalisation.
@@ -872,6 +1064,14 @@ hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, un
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_subst_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
+                                const unsigned *d_fidx, double *d_work, const double *d_cmat, unsigned *d_bad_sites,
+                                double *d_change, double *d_count, uint8_t *d_top_pair, double *d_top_prob, double *d_joint) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const SubstArgs ca{d_cmat, d_change, d_count, d_top_pair, d_top_prob, d_joint, d_bad_sites, p->api_states, p->rate_cats};
+  return launch_walk<SubstDna, SubstGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca);
 }
 
 hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,

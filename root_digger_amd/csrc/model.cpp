@@ -709,6 +709,91 @@ std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
   return out;
 }
 
+// Substitutions mapped onto the branches at one root (model.hpp): gradient's evaluation, with the
+// host assembly of subst_map.hpp in place of the gradient's and the walk's fourth consumer after it.
+model_t::substitutions_t model_t::substitutions(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
+                                                bool per_site) {
+  refuse_site_group("substitutions", "per-site output of a site-sharded model is not supported");
+  const size_t P = _partitions.size(), total = pattern_count();
+  require_fit(params, "substitutions", "");
+  substitutions_t out;
+  with_saved_parameters(true, [] {}, [&] {
+    set_model_params(params);
+    auto sched = _tree.generate_operations(rl);
+    const auto &ops = std::get<0>(sched);
+    const auto &pmi = std::get<1>(sched);
+    const auto &brl = std::get<2>(sched);
+    const unsigned n_ops = (unsigned)ops.size();
+    out.node_clv.resize(n_ops);
+    out.node_parent.resize(n_ops);
+    out.node_children.resize(2 * (size_t)n_ops);
+    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, out.node_clv.data(), out.node_parent.data(),
+                                       out.node_children.data()) != RDAMD_SUCCESS)
+      fail("marginal_ancestral_nodes");
+    std::unordered_map<unsigned, size_t> place;
+    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
+    const size_t branches = 2 * (size_t)n_ops;
+    out.lengths.resize(branches);
+    for (unsigned k = 0; k < n_ops; ++k) {
+      const rdamd_operation_t &o = ops[n_ops - 1 - k];
+      out.lengths[2 * k] = brl[place.at(o.child1_matrix_index)];
+      out.lengths[2 * k + 1] = brl[place.at(o.child2_matrix_index)];
+    }
+    if (per_site) {
+      out.change.assign(branches * total, 0.0);
+      out.count.assign(branches * total, 0.0);
+      out.top_prob.assign(branches * total, 0.0);
+      out.top_pair.assign(branches * total, 0);
+    }
+    update_pmatrices(pmi, brl);
+    ++_n_full;
+    size_t at = 0;   // first pattern of the partition in the concatenated list
+    std::vector<double> pair, change, count, top_prob;
+    std::vector<unsigned char> top_pair;
+    for (size_t p = 0; p < P; ++p) {
+      rdamd_partition_t *part = _partitions[p];
+      const size_t K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part), sites = rdamd_partition_sites(part);
+      const auto refused = [&] { return std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg()); };
+      rdamd_update_clvs(part, ops.data(), n_ops);
+      if (rdamd_errno()) fail("update_clvs");
+      out.lnl += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
+                                                  _param_indicies[p].data(), nullptr);
+      if (rdamd_errno()) fail("compute_root_loglikelihood");
+      pair.assign(branches * R * K * K, 0.0);
+      if (rdamd_branch_pair_sums(part, ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), nullptr, nullptr) !=
+          RDAMD_SUCCESS)
+        throw refused();
+      model_params_t pi(params[p].freqs);   // as set_model_params applied them
+      double xsum = 0.0;
+      for (double f : pi) xsum += f;
+      for (double &f : pi) f /= xsum;
+      const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
+      const size_t typed_at = out.typed.size();
+      out.typed.resize(typed_at + branches * K * K);
+      if (rdamd_substitution_counts_from_pair_sums((unsigned)K, (unsigned)R, 1, n_ops, pair.data(), out.lengths.data(),
+                                                   params[p].subst_rates.data(), pi.data(), zeros.data(),
+                                                   _rate_rates[p].data(), out.typed.data() + typed_at) != RDAMD_SUCCESS)
+        throw refused();
+      if (per_site) {
+        change.resize(branches * sites); count.resize(branches * sites);
+        top_prob.resize(branches * sites); top_pair.resize(branches * sites);
+        if (rdamd_branch_substitutions(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
+                                       out.lengths.data(), change.data(), count.data(), top_pair.data(), top_prob.data(),
+                                       nullptr) != RDAMD_SUCCESS)
+          throw refused();
+        for (size_t b = 0; b < branches; ++b) {
+          std::copy(change.begin() + b * sites, change.begin() + (b + 1) * sites, out.change.begin() + b * total + at);
+          std::copy(count.begin() + b * sites, count.begin() + (b + 1) * sites, out.count.begin() + b * total + at);
+          std::copy(top_prob.begin() + b * sites, top_prob.begin() + (b + 1) * sites, out.top_prob.begin() + b * total + at);
+          std::copy(top_pair.begin() + b * sites, top_pair.begin() + (b + 1) * sites, out.top_pair.begin() + b * total + at);
+        }
+      }
+      at += sites;
+    }
+  });
+  return out;
+}
+
 // compute_lh for the searches, between optimize_params and the root-only steps: the same
 // value for the caller's convergence test, but only what those steps read is left behind --
 // the CLVs and scalers of the root's two children (rdamd_evaluate_root_children: one job of

@@ -173,6 +173,19 @@ public:
   // param_gradient.hpp.  Saves and restores what branch_lengths does.
   std::vector<partition_parameters_t> gradient(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
                                                double *lnl);
+  // Substitutions mapped onto the branches at root rl (include/root_digger_amd.h,
+  // rdamd_model_substitutions).  Nodes and lengths as branch_lengths gives them; typed: one
+  // [nodes][2][K][K] block per partition back to back; change, count, top_prob, top_pair:
+  // [nodes][2][pattern_count()], partitions concatenated.  The per-site arrays are filled only when
+  // per_site is set.  Saves and restores what branch_lengths does.
+  struct substitutions_t {
+    std::vector<unsigned> node_clv, node_children;
+    std::vector<int> node_parent;
+    std::vector<double> lengths, typed, change, count, top_prob;
+    std::vector<unsigned char> top_pair;
+    double lnl = 0.0;
+  };
+  substitutions_t substitutions(const root_location_t &rl, const std::vector<partition_parameters_t> &params, bool per_site);
 
   // batched objective: lnL of (root, parameter set) pairs, all partitions,
   // through rdamd_evaluate_batch (one fused launch per partition)

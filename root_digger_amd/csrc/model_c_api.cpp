@@ -478,6 +478,32 @@ int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, cons
     return RDAMD_SUCCESS;
   })
 }
+int rdamd_model_substitutions(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                              const double *values, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
+                              unsigned int *node_children, double *lengths_out, double *typed_out, double *change_out,
+                              double *count_out, unsigned char *top_pair_out, double *top_prob_out, double *lnl_out) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_substitutions")) return RDAMD_FAILURE;
+    if (!rl || !counts || !values)
+      throw std::invalid_argument("rdamd_model_substitutions: null argument (the parameters are required: the typed counts "
+                                  "are made from the substitution rates, which the model does not keep)");
+    const std::vector<rdamd::partition_parameters_t> params = one_root_params(m, counts, values);
+    const bool per_site = change_out || count_out || top_pair_out || top_prob_out;
+    const rdamd::model_t::substitutions_t r = m->model->substitutions(to_cpp(rl), params, per_site);
+    if (n_nodes) *n_nodes = (unsigned)r.node_clv.size();
+    if (node_clv) std::copy(r.node_clv.begin(), r.node_clv.end(), node_clv);
+    if (node_parent) std::copy(r.node_parent.begin(), r.node_parent.end(), node_parent);
+    if (node_children) std::copy(r.node_children.begin(), r.node_children.end(), node_children);
+    if (lengths_out) std::copy(r.lengths.begin(), r.lengths.end(), lengths_out);
+    if (typed_out) std::copy(r.typed.begin(), r.typed.end(), typed_out);
+    if (change_out) std::copy(r.change.begin(), r.change.end(), change_out);
+    if (count_out) std::copy(r.count.begin(), r.count.end(), count_out);
+    if (top_pair_out) std::copy(r.top_pair.begin(), r.top_pair.end(), top_pair_out);
+    if (top_prob_out) std::copy(r.top_prob.begin(), r.top_prob.end(), top_prob_out);
+    if (lnl_out) *lnl_out = r.lnl;
+    return RDAMD_SUCCESS;
+  })
+}
 int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                                         const double *values, double min_len, double max_len, double atol,
                                         unsigned int max_iters, double *lengths_out, double *d1_out, double *d2_out,

@@ -14,6 +14,7 @@
 #include "clv_plan.hpp"
 #include "common.hpp"
 #include "outer_plan.hpp"
+#include "subst_map.hpp"
 #include "tip_encode.hpp"
 
 namespace rdamd {
@@ -1301,6 +1302,71 @@ int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, u
       for (size_t i = 0; i < KA; ++i) root_out[r * KA + i] = root[r * 5 + i];
     if (cat_out) cat_out[r] = root[r * 5 + 4];
   }
+  return RDAMD_SUCCESS;
+}
+
+static thread_local double g_subst_ms = 0.0;
+
+double rdamd_branch_substitutions_last_ms(void) { return g_subst_ms; }
+
+int rdamd_branch_substitutions(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                               const unsigned int *params_indices, const unsigned int *freqs_indices,
+                               const double *lengths, double *change_out, double *count_out,
+                               unsigned char *top_pair_out, double *top_prob_out, double *joint_out) {
+  clear_error();
+  g_subst_ms = 0.0;
+  const char *what = "rdamd_branch_substitutions";
+  const std::initializer_list<RateIndices> indices = {{params_indices, "params"}, {freqs_indices, "freqs"}};
+  OuterPlan plan;
+  if (!preorder_admitted(p, what, ops, n_ops, !ops || !params_indices || !freqs_indices || !lengths, indices, &plan))
+    return RDAMD_FAILURE;
+  const size_t branches = (size_t)n_ops * 2;
+  for (size_t b = 0; b < branches; ++b)
+    if (!length_ok(lengths[b])) {
+      set_error(64, "%s: the length of branch (%zu, %zu) is negative or not finite", what, b / 2, b % 2);
+      return RDAMD_FAILURE;
+    }
+  if (p->sites == 0 || n_ops == 0) return RDAMD_SUCCESS;
+  // the count matrices, from the rate matrices as flush_q builds them
+  const unsigned R = p->rate_cats, K = p->states;
+  const size_t KA = p->api_states, cells = branches * p->sites;
+  std::vector<double> q((size_t)p->rate_matrices * K * K), cmat(branches * R * K * K);
+  for (unsigned m = 0; m < p->rate_matrices; ++m)
+    build_q_host(K, p->subst[m].data(), p->freqs[m].data(), q.data() + (size_t)m * K * K);
+  smap::count_matrices(K, R, q.data(), params_indices, p->rates.data(), lengths, branches, cmat.data());
+  DeviceArray<double> d_cmat, change, count, top_prob, joint;
+  DeviceArray<uint8_t> top_pair;
+  DeviceArray<unsigned> bad_sites;
+  const auto allocate = [&] {
+    hipError_t e = d_cmat.alloc(cmat.size());
+    if (e == hipSuccess && change_out) e = change.alloc(cells);
+    if (e == hipSuccess && count_out) e = count.alloc(cells);
+    if (e == hipSuccess && top_pair_out) e = top_pair.alloc(cells);
+    if (e == hipSuccess && top_prob_out) e = top_prob.alloc(cells);
+    if (e == hipSuccess && joint_out) e = joint.alloc(cells * KA * KA);
+    if (e == hipSuccess) e = bad_sites.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(bad_sites.d, 0, sizeof(unsigned), p->stream);
+    if (e == hipSuccess) e = hipMemcpy(d_cmat.d, cmat.data(), sizeof(double) * cmat.size(), hipMemcpyHostToDevice);
+    return e;
+  };
+  const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    return launch_subst_program(p, d_prog, n_ops, plan.slots, d_indices[1], d_work, d_cmat.d, bad_sites.d, change.d, count.d,
+                                top_pair.d, top_prob.d, joint.d);
+  };
+  if (preorder_run(p, plan, indices, &g_subst_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
+  unsigned bad = 0;
+  RDAMD_HIP_TRY(hipMemcpy(&bad, bad_sites.d, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (bad) {
+    g_subst_ms = 0.0;   // (a call that returns nothing reports no time)
+    set_error(65, "%s: %u of %u sites have a likelihood that is 0 or not finite; nothing is returned", what, bad, p->sites);
+    return RDAMD_FAILURE;
+  }
+  if (change_out) RDAMD_HIP_TRY(hipMemcpy(change_out, change.d, sizeof(double) * cells, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (count_out) RDAMD_HIP_TRY(hipMemcpy(count_out, count.d, sizeof(double) * cells, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (top_pair_out) RDAMD_HIP_TRY(hipMemcpy(top_pair_out, top_pair.d, cells, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (top_prob_out) RDAMD_HIP_TRY(hipMemcpy(top_prob_out, top_prob.d, sizeof(double) * cells, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  if (joint_out)
+    RDAMD_HIP_TRY(hipMemcpy(joint_out, joint.d, sizeof(double) * cells * KA * KA, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 

@@ -49,6 +49,15 @@
 // value, the exact gradient, the forward difference with the search's own step h = max(1e-4 |x|, 1e-4)
 // and whether the value sits at the optimiser's bound; one line with the largest projected component.
 //
+// --substitutions [--subst-min-prob P] (new here, with --exhaustive): after the search rank 0 maps the
+// substitutions onto the branches at the best record's root and parameters (rdamd_model_substitutions):
+// <prefix>.substitutions.tsv, one row per branch with the child's name as in .ancestral.tree, the length,
+// the expected number of substitutions, the K K - K typed counts, the K dwell times and the sum over
+// columns of the probability of a change; <prefix>.mutations.tsv, one row per (branch, alignment column)
+// whose likeliest change i -> j has posterior probability >= P (default 0.5), with that probability and
+// the expected number of substitutions at the column; <prefix>.substitutions.tree, the rooted tree with
+// the inner nodes named as in the rows.
+//
 //   rd_amd --msa aln.fasta --tree t.nwk --prefix out --exhaustive --lbfgsb liblbfgsb.so
 #include <algorithm>
 #include <chrono>
@@ -89,6 +98,9 @@ struct options_t {
   bool ancestral = false, site_rates = false;
   // the ML branch lengths at the best root (.brlen.tsv, .brlen.tree) and their box
   bool branch_lengths = false, gradient = false;   // gradient: the exact gradient at the best record (.gradient.tsv)
+  // substitutions mapped onto the branches at the best record (.substitutions.tsv / .tree, .mutations.tsv)
+  bool substitutions = false;
+  double subst_min_prob = 0.5;
   double brlen_min = 1e-6, brlen_max = 100.0;
   uint64_t rell_seed = 0;
 };
@@ -118,7 +130,10 @@ void usage() {
       "  --branch-lengths [--brlen-min <X>] [--brlen-max <X>]   (with --exhaustive: ML branch lengths at the best root,\n"
       "                <prefix>.brlen.tsv / .tree)\n"
       "  --gradient   (with --exhaustive: exact gradient of lnL in the model parameters at the best record,\n"
-      "                <prefix>.gradient.tsv)");
+      "                <prefix>.gradient.tsv)\n"
+      "  --substitutions [--subst-min-prob <P>]   (with --exhaustive: expected substitution counts per branch and the\n"
+      "                mutations with posterior probability >= P (default 0.5) at the best record,\n"
+      "                <prefix>.substitutions.tsv / .tree, <prefix>.mutations.tsv)");
 }
 
 options_t parse(int argc, char **argv) {
@@ -148,6 +163,7 @@ options_t parse(int argc, char **argv) {
       {"site-rates", no_argument, 0, 0},         {"branch-lengths", no_argument, 0, 0},
       {"brlen-min", required_argument, 0, 0},    {"brlen-max", required_argument, 0, 0},
       {"gradient", no_argument, 0, 0},
+      {"substitutions", no_argument, 0, 0},      {"subst-min-prob", required_argument, 0, 0},
       {0, 0, 0, 0}};
   options_t o;
   int index = 0;
@@ -200,6 +216,8 @@ options_t parse(int argc, char **argv) {
     else if (name == "site-rates") o.site_rates = true;
     else if (name == "branch-lengths") o.branch_lengths = true;
     else if (name == "gradient") o.gradient = true;
+    else if (name == "substitutions") o.substitutions = true;
+    else if (name == "subst-min-prob") o.subst_min_prob = std::atof(v);
     else if (name == "brlen-min") o.brlen_min = std::atof(v);
     else if (name == "brlen-max") o.brlen_max = std::atof(v);
     else if (name == "site-reduce") {
@@ -241,7 +259,7 @@ static int run(int argc, char **argv) {
   // member holds one block of the columns
   const char *support_opt = o.rell_given ? "--rell" : o.site_lh ? "--site-lh" : o.ancestral ? "--ancestral"
                             : o.site_rates ? "--site-rates" : o.branch_lengths ? "--branch-lengths"
-                            : o.gradient ? "--gradient" : nullptr;
+                            : o.gradient ? "--gradient" : o.substitutions ? "--substitutions" : nullptr;
   const bool site_support = o.rell_given || o.site_lh;   // the site lnLs of every candidate are wanted
   if (o.rell_seed_given && !o.rell_given) die("--rell-seed: there is no --rell to seed");
   if (o.root_tests && !o.rell_given) die("--root-tests: the tests are made from the replicates of --rell <B>");
@@ -250,6 +268,7 @@ static int run(int argc, char **argv) {
   if (o.au && o.rell < 2) die("--au: --rell must give at least 2 replicates");
   if (o.branch_lengths && !(o.brlen_min > 0.0 && o.brlen_min < o.brlen_max && std::isfinite(o.brlen_max)))
     die("--branch-lengths: 0 < --brlen-min < --brlen-max is required");
+  if (!(o.subst_min_prob >= 0.0 && o.subst_min_prob <= 1.0)) die("--subst-min-prob: a probability in [0, 1] is required");
   if (support_opt) {
     const std::string opt = support_opt;
     if (o.rell_given && (o.rell < 1 || o.rell > 0x7fffffffl)) die("--rell: the number of replicates must be at least 1");
@@ -874,6 +893,96 @@ static int run(int argc, char **argv) {
     char line[512];
     std::snprintf(line, sizeof line, "Gradient at root %llu: lnL %.6f, %zu parameters, largest projected component %.6e (%s); "
                   "written to: %s.gradient.tsv", (unsigned long long)best.id, lnl, n_values, worst, worst_name.c_str(),
+                  o.prefix.c_str());
+    std::cout << line << std::endl;
+  }
+  // ---- substitutions mapped onto the branches at the best record's root and parameters
+  if (o.substitutions) {
+    std::vector<uint64_t> counts;
+    std::vector<double> values;
+    best_record_params(counts, values);
+    unsigned P = 0, columns = 0;
+    need(rdamd_model_site_patterns(model, &P, &columns, nullptr, nullptr), "site_patterns");
+    std::vector<unsigned> weights(P), pattern_of(columns);
+    need(rdamd_model_site_patterns(model, nullptr, nullptr, weights.data(), pattern_of.data()), "site_patterns");
+    const unsigned n_parts = (unsigned)rdamd_model_partition_count(model), K = o.states;
+    std::vector<unsigned> part_columns(n_parts);
+    for (unsigned p = 0; p < n_parts; ++p)
+      need(rdamd_model_partition_shape(model, p, nullptr, &part_columns[p], nullptr), "partition_shape");
+    unsigned n_nodes = rdamd_tree_tip_count(tree) - 1;
+    const size_t branches = 2 * (size_t)n_nodes, cells = branches * P;
+    std::vector<unsigned> node_clv(n_nodes), node_children(branches);
+    std::vector<double> lengths(branches), typed((size_t)n_parts * branches * K * K), change(cells), count(cells), top_prob(cells);
+    std::vector<unsigned char> top_pair(cells);
+    double lnl = 0.0;
+    need(rdamd_model_substitutions(model, &best, counts.data(), values.data(), &n_nodes, node_clv.data(), nullptr,
+                                   node_children.data(), lengths.data(), typed.data(), change.data(), count.data(),
+                                   top_pair.data(), top_prob.data(), &lnl), "substitutions");
+    const char *letters = K == 2 ? "01" : "ACGT";
+    std::vector<std::string> name(branches);
+    for (size_t b = 0; b < branches; ++b) {
+      const auto inner = std::find(node_clv.begin(), node_clv.end(), node_children[b]);
+      name[b] = inner != node_clv.end() ? "N" + std::to_string(inner - node_clv.begin())
+                                        : std::string(rdamd_tree_tip_label(tree, node_children[b]));
+    }
+    std::FILE *f = std::fopen((o.prefix + ".substitutions.tsv").c_str(), "w");
+    if (!f) die("could not write " + o.prefix + ".substitutions.tsv");
+    std::fprintf(f, "node\tchild\tname\tlength\texpected_total");
+    for (unsigned i = 0; i < K; ++i)
+      for (unsigned j = 0; j < K; ++j)
+        if (i != j) std::fprintf(f, "\t%c>%c", letters[i], letters[j]);
+    for (unsigned i = 0; i < K; ++i) std::fprintf(f, "\tdwell_%c", letters[i]);
+    std::fprintf(f, "\tchange_probability_sum\n");
+    double all = 0.0;
+    for (size_t b = 0; b < branches; ++b) {
+      std::vector<double> sum((size_t)K * K, 0.0);   // the partitions in partition order
+      for (unsigned p = 0; p < n_parts; ++p)
+        for (size_t e = 0; e < (size_t)K * K; ++e) sum[e] += typed[((size_t)p * branches + b) * K * K + e];
+      double total = 0.0, changed = 0.0;
+      for (unsigned i = 0; i < K; ++i)
+        for (unsigned j = 0; j < K; ++j)
+          if (i != j) total += sum[i * K + j];
+      for (unsigned s = 0; s < P; ++s) changed += weights[s] * change[b * P + s];
+      all += total;
+      std::fprintf(f, "N%zu\t%zu\t%s\t%.10f\t%.17g", b / 2, b % 2, name[b].c_str(), lengths[b], total);
+      for (unsigned i = 0; i < K; ++i)
+        for (unsigned j = 0; j < K; ++j)
+          if (i != j) std::fprintf(f, "\t%.17g", sum[i * K + j]);
+      for (unsigned i = 0; i < K; ++i) std::fprintf(f, "\t%.17g", sum[i * K + i]);
+      std::fprintf(f, "\t%.17g\n", changed);
+    }
+    std::fclose(f);
+    f = std::fopen((o.prefix + ".mutations.tsv").c_str(), "w");
+    if (!f) die("could not write " + o.prefix + ".mutations.tsv");
+    std::fprintf(f, "node\tchild\tname\tpartition\tcolumn\tfrom\tto\tprobability\texpected_count\n");
+    size_t listed = 0;
+    for (size_t b = 0; b < branches; ++b) {
+      size_t col = 0;   // column of the concatenated partitions
+      for (unsigned p = 0; p < n_parts; ++p)
+        for (unsigned c = 0; c < part_columns[p]; ++c, ++col) {
+          const size_t at = b * P + pattern_of[col];
+          if (!(top_prob[at] >= o.subst_min_prob)) continue;
+          std::fprintf(f, "N%zu\t%zu\t%s\t%u\t%u\t%c\t%c\t%.17g\t%.17g\n", b / 2, b % 2, name[b].c_str(), p, c + 1,
+                       letters[top_pair[at] / K], letters[top_pair[at] % K], top_prob[at], count[at]);
+          ++listed;
+        }
+    }
+    std::fclose(f);
+    rdamd_tree_t *named = rdamd_tree_from_file(o.tree.c_str());
+    if (!named) die(rdamd_errmsg());
+    rdamd_root_location_t rl;
+    need(rdamd_tree_root_location(named, (unsigned)best.id, &rl), "root_location");
+    rl.brlen_ratio = best.brlen_ratio;
+    need(rdamd_tree_root_by(named, &rl), "root_by");
+    char *nw = rdamd_tree_newick_ancestral(named, n_nodes, node_clv.data());
+    if (!nw) die(rdamd_errmsg());
+    std::ofstream(o.prefix + ".substitutions.tree") << nw;
+    std::free(nw);
+    rdamd_tree_destroy(named);
+    char line[640];
+    std::snprintf(line, sizeof line, "Substitutions at root %llu: lnL %.6f, %.6f expected on %zu branches, %zu mutations with "
+                  "probability >= %g; written to: %s.substitutions.tsv %s.mutations.tsv %s.substitutions.tree",
+                  (unsigned long long)best.id, lnl, all, branches, listed, o.subst_min_prob, o.prefix.c_str(), o.prefix.c_str(),
                   o.prefix.c_str());
     std::cout << line << std::endl;
   }
