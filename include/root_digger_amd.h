@@ -995,6 +995,47 @@ int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl,
                           double *post_out, double *cat_out, double *mean_rate_out);
 
 /* ------------------------------------------------------------------------
+ * Ancestral sequences at a chosen root: the likeliest state of every inner node and alignment
+ * column with its posterior probability -- for DNA, binary AND protein data.  NEW relative to the
+ * reference, which reconstructs nothing: like the section above it extends the traversal made with
+ * corax_update_clvs at src/model.cpp:402 by the complementary pre-order pass, here also for the
+ * 20-state partitions that keep their CLVs in the matrix-core operand layout (20 states, up to 8
+ * rate categories), where the pass runs on v_mfma_f64_4x4x4_4b_f64 like the traversal itself.
+ *
+ * Definitions (L, P, pi, U, post) and the 2^256 rule are those of "Marginal ancestral states"
+ * above;  state[v][s] = the smallest j among the largest post[v][s][j],  prob[v][s] = that
+ * posterior: exactly argmax and max of the table, bit for bit.  Equal inputs give equal bits.
+ * ---------------------------------------------------------------------- */
+/* state_out[n_ops][sites] (index of the likeliest state, the smallest among equals), prob_out[n_ops][sites],
+ * post_out[n_ops][sites][states]; any may be NULL.  Nodes as rdamd_marginal_ancestral_nodes orders them.
+ * Precondition as for rdamd_marginal_ancestral: rdamd_update_prob_matrices and rdamd_update_clvs on
+ * exactly this list; nothing in the partition is written.  4-state and binary partitions run
+ * rdamd_marginal_ancestral's launch (post_out has its bits), matrix-core 20-state partitions a
+ * walk of their own; the posterior table stays on the device unless post_out is given (20 states:
+ * five times the 4-state table).  Refused (error 63, nothing launched, the shape named):
+ * partitions with RDAMD_ATTRIB_SPARSE_CLVS, state counts other than 2, 4 and 20, 20 states with
+ * more than 8 rate categories (the plain CLV layout).  Errors 64, 10 and 7 as for
+ * rdamd_marginal_ancestral. */
+int rdamd_ancestral_sequences(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                              const unsigned int *freqs_indices, uint8_t *state_out, double *prob_out,
+                              double *post_out);
+/* device time of the launches (walk and arg-max) of this thread's last rdamd_ancestral_sequences
+ * call, milliseconds between two HIP events (0 after a failed call); for measurements */
+double rdamd_ancestral_sequences_last_ms(void);
+/* The same for one root of a model, as rdamd_model_ancestral: parameters in the checkpoint's layout
+ * (counts = values = NULL: the model's own), the patterns of all partitions concatenated in
+ * partition order -- state_out[n_nodes][P_total], prob_out[n_nodes][P_total],
+ * post_out[n_nodes][P_total][states] -- and the model's parameters, its rooting and the conditional
+ * likelihoods of that rooting as before when the call returns.  Any output may be NULL.  Refused:
+ * a model that sums over a site group (error 61); partitions of different state counts in one
+ * model (post_out has one `states`); a partition whose shape rdamd_ancestral_sequences refuses fails
+ * the call and is named in the message. */
+int rdamd_model_ancestral_sequences(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                                    const double *values, unsigned int *n_nodes, unsigned int *node_clv,
+                                    int *node_parent, unsigned int *node_children, uint8_t *state_out,
+                                    double *prob_out, double *post_out);
+
+/* ------------------------------------------------------------------------
  * Analytic branch-length derivatives and optimised lengths at a chosen root.  NEW relative to the
  * reference, whose only derivative is the forward difference of compute_dlh (one parameter: the
  * root's position).

@@ -301,6 +301,10 @@ _sig("rdamd_site_rate_posteriors", C.c_int, _vp, _u, C.c_int, _pu, _pd, _pd)
 _sig("rdamd_ancestral_last_ms", C.c_double)
 _sig("rdamd_model_partition_shape", C.c_int, _vp, _u, _pu, _pu, _pu)
 _sig("rdamd_model_ancestral", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu, _pd, _pd, _pd)
+_sig("rdamd_ancestral_sequences", C.c_int, _vp, _pop, _u, _pu, C.POINTER(C.c_ubyte), _pd, _pd)
+_sig("rdamd_ancestral_sequences_last_ms", C.c_double)
+_sig("rdamd_model_ancestral_sequences", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pu, _pu, _pi, _pu,
+     C.POINTER(C.c_ubyte), _pd, _pd)
 _sig("rdamd_tree_newick_ancestral", _vp, _vp, _u, _pu)
 _sig("rdamd_tree_newick_branch_lengths", _vp, _vp, _u, _pu, _pd)
 _sig("rdamd_branch_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd)
@@ -796,6 +800,22 @@ class Partition:
             _fail("marginal_ancestral")
         return out
 
+    def ancestral_sequences(self, ops, freqs_indices=None, posteriors=False):
+        """The likeliest state of every inner node and site of the tree `ops` roots, and its posterior
+        -> (state uint8 [len(ops)][sites], prob [len(ops)][sites]), plus post [len(ops)][sites][states]
+        with posteriors=True (rdamd_ancestral_sequences; nodes as ancestral_nodes(ops) orders them).
+        Takes 4-state, binary and matrix-core 20-state partitions.  Call update_prob_matrices and
+        update_clvs on this list first."""
+        ops = _op_array(ops)
+        fi = self.params_indices if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        state = np.zeros((len(ops), self.sites), dtype=np.uint8)
+        prob = np.zeros((len(ops), self.sites), dtype=np.float64)
+        post = np.zeros((len(ops), self.sites, self.states), dtype=np.float64) if posteriors else None
+        if lib.rdamd_ancestral_sequences(self._h, ops, len(ops), _uptr(fi), state.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                         _dptr(prob), _dptr(post) if posteriors else None) != 1:
+            _fail("ancestral_sequences")
+        return (state, prob, post) if posteriors else (state, prob)
+
     def branch_derivatives(self, ops, params_indices=None, freqs_indices=None):
         """(d1[len(ops)][2], d2[len(ops)][2]): first and second derivative of lnL in the length of the
         branch above child c of node k, nodes as ancestral_nodes(ops) orders them
@@ -1173,6 +1193,11 @@ def ancestral_workspace_slots(ops, tips):
 def ancestral_last_ms():
     """device milliseconds of the pre-order launch of this thread's last marginal_ancestral call"""
     return float(lib.rdamd_ancestral_last_ms())
+
+
+def ancestral_sequences_last_ms():
+    """device milliseconds of the launches (walk and arg-max) of this thread's last ancestral_sequences call"""
+    return float(lib.rdamd_ancestral_sequences_last_ms())
 
 
 def branch_last_ms():
@@ -1728,6 +1753,32 @@ class Model:
             cuts = np.cumsum([0] + [sh[0] * sh[2] for sh in shapes])
             cat = [cat[cuts[i]:cuts[i + 1]].reshape(sh[0], sh[2]) for i, sh in enumerate(shapes)]
         return clv, parent, children, post, cat, mean
+
+    def ancestral_sequences(self, rl, params=None, posteriors=False):
+        """Ancestral sequences at root rl (rdamd_model_ancestral_sequences) -> (node_clv[n],
+        node_parent[n], node_children[n][2], state uint8 [n][P_total], prob[n][P_total]), plus
+        post[n][P_total][states] with posteriors=True; nodes as ancestral_nodes orders them, patterns of
+        all partitions concatenated.  DNA, binary and protein models; params as ancestral takes them."""
+        total = sum(self.partition_shape(p)[0] for p in range(self.partition_count()))
+        n = self._tree.tip_count() - 1
+        clv = np.zeros(n, dtype=np.uint32)
+        parent = np.zeros(n, dtype=np.int32)
+        children = np.zeros((n, 2), dtype=np.uint32)
+        state = np.zeros((n, total), dtype=np.uint8)
+        prob = np.zeros((n, total), dtype=np.float64)
+        post = np.zeros((n, total, self.states), dtype=np.float64) if posteriors else None
+        counts = values = None
+        if params is not None:
+            counts, values = _flatten_params(list(params))
+        nn = C.c_uint(0)
+        self._ok(lib.rdamd_model_ancestral_sequences(self._h, C.byref(rl),
+                                                     counts.ctypes.data_as(_pu64) if counts is not None else None,
+                                                     _dptr(values) if values is not None else None, C.byref(nn),
+                                                     _uptr(clv), parent.ctypes.data_as(_pi), _uptr(children),
+                                                     state.ctypes.data_as(C.POINTER(C.c_ubyte)), _dptr(prob),
+                                                     _dptr(post) if posteriors else None), "ancestral_sequences")
+        assert nn.value == n
+        return (clv, parent, children, state, prob) + ((post,) if posteriors else ())
 
     def branch_derivatives(self, rl, params=None):
         """Derivatives of lnL in every branch length at root rl (rdamd_model_branch_derivatives) ->

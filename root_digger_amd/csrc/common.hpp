@@ -285,6 +285,14 @@ unsigned preorder_blocks(const rdamd_partition *p);
 // posteriors: the whole program in one launch; d_post: [nops][sites][api_states]
 hipError_t launch_outer_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
                                 const unsigned *d_fidx, double *d_work, double *d_post);
+// kernels_preorder_k20.hip: the same program over a 20-state partition in the matrix-core operand
+// layout (mfma_layout, up to 8 rate categories); d_work: outer_workspace_doubles, operand layout;
+// d_post: [nops][sites][20]
+hipError_t launch_outer_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                    double *d_work, double *d_post);
+// d_state[row] = the smallest index among the largest of d_post[row][0..K), d_prob[row] = that posterior
+hipError_t launch_ancestral_argmax(rdamd_partition *p, const double *d_post, size_t rows, unsigned K, uint8_t *d_state,
+                                   double *d_prob);
 // d_cat [sites][R] and d_mean [sites] (either may be null) from the CLV in device buffer clv_phys_index
 hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const unsigned *d_fidx, double *d_cat,
                              double *d_mean);

@@ -1,0 +1,68 @@
+// The 20-state pre-order walk's index arithmetic (kernels_preorder_k20.hip): where a lane finds its
+// A operand of the forward product P L and of the transposed product P^T t in the ONE MFMA-ready
+// copy of a P-matrix, and the sizes of the walk's workspace and LDS.  Pure constexpr arithmetic over
+// plain numbers -- no HIP, no partition -- so that tests/cpp/k20_preorder_check.cpp can emulate the
+// matrix cores' lane map on the host and prove both gathers before any GPU run.
+//
+// Lanes (kernels_clv_mfma.hip): col = lane % 16 is the site of the wave's tile, grp = lane / 16; a
+// vector of 20 states lives as five doubles per lane, operand t = state k20p_state_of(grp, t).
+// One v_mfma_f64_4x4x4_4b_f64 takes from lane (col, grp)  A[i = col % 4][k = grp]  and
+// B[k = grp][site = col]  and leaves  D[i = grp][site = col].
+#pragma once
+
+#include <cstddef>
+
+namespace rdamd {
+
+constexpr unsigned kK20States = 20, kK20Steps = 5, kK20Groups = 5;
+constexpr unsigned kK20TileDoubles = 16 * kK20States;                  // one CLV tile: 16 sites of one rate
+constexpr unsigned kK20CopyDoubles = kK20Groups * kK20Steps * 16;      // the MFMA-ready copy of one (matrix, rate)
+constexpr unsigned kK20MaxRates = 8;
+
+// (the same dealing and the same tile as common.hpp's k20_state_of / k20_tile_index, restated here
+// without HIP; kernels_preorder_k20.hip asserts that they agree everywhere)
+constexpr unsigned k20p_state_of(unsigned g, unsigned t) { return 5u * g + (t + (g & 1u)) % 5u; }
+constexpr unsigned k20p_tile_index(unsigned site_in_tile, unsigned state) {
+  const unsigned g = state / 5u, t = (state % 5u + 5u - (g & 1u)) % 5u, lane = 16u * g + site_in_tile;
+  return t < 4u ? (t >> 1) * 128u + lane * 2u + (t & 1u) : 256u + lane;
+}
+// a lane's operand t of a tile, in doubles from the tile's start (k20p_tile_index of its state)
+constexpr unsigned k20p_lane_operand(unsigned lane, unsigned t) {
+  return t < 4u ? (t >> 1) * 128u + lane * 2u + (t & 1u) : 256u + lane;
+}
+
+// pmat_to_mfma_kernel's formula: the copy holds P[state_of(i, rg)][state_of(k, ks)] here
+constexpr unsigned k20_copy_index(unsigned rg, unsigned ks, unsigned k, unsigned i) {
+  return ((rg * kK20Steps + ks) * 4u + k) * 4u + i;
+}
+
+// FORWARD product  d[rg] = sum_ks A . b[ks]  with  d = P c:  the lane needs
+// P[state_of(col % 4, rg)][state_of(grp, ks)]  = element (k = grp, i = col % 4) of block (rg, ks)
+constexpr unsigned k20_a_forward(unsigned rg, unsigned ks, unsigned col, unsigned grp) {
+  return k20_copy_index(rg, ks, grp, col & 3u);
+}
+// TRANSPOSED product  d[rg] = sum_ks A' . t[ks]  with  d = P^T t:  the lane needs
+// P[state_of(grp, ks)][state_of(col % 4, rg)]  = element (k = col % 4, i = grp) of block (ks, rg):
+// the same copy serves both products
+constexpr unsigned k20_a_transposed(unsigned rg, unsigned ks, unsigned col, unsigned grp) {
+  return k20_copy_index(ks, rg, col & 3u, grp);
+}
+
+// workspace of a program with `slots` slots: outer vectors in the operand layout, whole tiles
+constexpr size_t k20_preorder_workspace_doubles(size_t slots, size_t rate_cats, size_t tiles) {
+  return slots * rate_cats * tiles * kK20TileDoubles;
+}
+
+// LDS of one workgroup (R waves), in bytes: per wave the A copies of the operation's two children
+// (wave-private), the consumer's exchange area of both children ([child][rate][320 doubles]: the
+// posteriors' sum over rates), and the rescale flags ([parity][16] words)
+constexpr size_t k20_preorder_stage_bytes(size_t rate_cats) { return rate_cats * 2 * kK20CopyDoubles * sizeof(double); }
+constexpr size_t k20_preorder_exchange_bytes(size_t rate_cats) { return 2 * rate_cats * kK20TileDoubles * sizeof(double); }
+constexpr size_t k20_preorder_flag_bytes() { return 2 * 16 * sizeof(unsigned); }
+constexpr size_t k20_preorder_lds_bytes(size_t rate_cats) {
+  return k20_preorder_stage_bytes(rate_cats) + k20_preorder_exchange_bytes(rate_cats) + k20_preorder_flag_bytes();
+}
+constexpr size_t kK20LdsLimit = 160 * 1024;   // one CU's LDS on gfx950
+static_assert(k20_preorder_lds_bytes(kK20MaxRates) <= kK20LdsLimit, "the walk's LDS fits a CU at 8 rate categories");
+
+}  // namespace rdamd

@@ -50,6 +50,7 @@
 // (kBlockSums, generic walk); its hooks are begin, op_begin, branch, (branch_done,) outer, op_end
 // and end, in the order the walk reaches them.
 #include "common.hpp"
+#include "k20_preorder.hpp"
 #include "outer_plan.hpp"
 
 namespace rdamd {
@@ -1012,6 +1013,7 @@ bool outer_fast_shape(const rdamd_partition *p) {
 }
 
 size_t outer_workspace_doubles(const rdamd_partition *p, unsigned slots) {
+  if (p->mfma_layout) return k20_preorder_workspace_doubles(slots, p->rate_cats, p->clv_tiles());   // kernels_preorder_k20.hip
   const size_t buffers = outer_fast_shape(p) ? slots : (size_t)slots + 4;
   return buffers * p->sites * p->rate_cats * 4;
 }

@@ -1,0 +1,394 @@
+// The pre-order pass for 20-state partitions in the matrix-core operand layout
+// (rdamd_partition::mfma_layout): the OUTER vectors of kernels_preorder.hip on
+// v_mfma_f64_4x4x4_4b_f64, and their first consumer, the marginal ancestral state posteriors.
+//
+// New here -- the reference computes no ancestral states; this extends the traversal it makes with
+// corax_update_clvs (src/model.cpp:402) by the complementary pass, for protein data.  Definitions as
+// in kernels_preorder.hip:  U_root = pi_r,  t = U_u (.) (P_b L_b),  U_a = t^T P_a,
+// post[v][s][j] = sum_r w_r U_v L_v normalised over j, and the 2^256 rule on the outer vectors per
+// site over all rates and all 20 states (no count is kept: the outputs are normalised per site).
+//
+// The program is the planner's, unchanged (outer_plan.hpp): parents from pi, registers or a
+// workspace slot, children kept in registers or a slot, the whole list in ONE launch; the
+// partition is only read.
+//
+// Lane map: the traversal kernel's (kernels_clv_mfma.hip).  A wave is (16 sites, one rate), a
+// workgroup the R rates of the same 16 sites; col = lane % 16 is the site, grp = lane / 16 holds the
+// states k20_state_of(grp, t), t = 0..4 -- five doubles per vector and lane.
+//
+// Per operation, with `up` the parent's outer vector:
+//   pl_c = P_c L_c     inner child: 25 MFMAs, A = the MFMA-ready copy d_pmat_mfma, B = the child's
+//                      CLV tile (the forward kernel's child_product); tip child: its tip-table row,
+//                      in operand order already, no MFMA
+//   t    = up (.) pl_sibling   lane-wise: the D layout is the B layout, nothing moves
+//   uc   = P_c^T t     inner child: 25 MFMAs, A from the SAME staged copy read transposed
+//                      (k20_preorder.hpp, k20_a_transposed; proven on the host by
+//                      tests/cpp/k20_preorder_check.cpp)
+// so an operation costs up to 100 MFMAs per wave where the forward kernel spends 50.
+//
+// Rescale rule: the largest of the lane's five entries against 2^-256, one ballot folded over the
+// four lane groups on the scalar unit, one word per wave (bits 0-15 child 0, 16-31 child 1) in a
+// flag array double-buffered by operation parity, ONE barrier; a site small in every rate is
+// multiplied by 2^256 in every rate.
+//
+// A CONSUMER is a functor called at fixed places (begin, op_begin, branch, outer, op_end, end), as in
+// kernels_preorder.hip; it owns the exchange area of the workgroup's LDS ([child][rate][320]).
+// The posteriors: each wave puts w_r U L of an inner child there in `outer`; after one barrier (op_end)
+// wave c % R adds the rates r = 0, 1, ... in that order, adds the 20 states of a site in one fixed order
+// (five in the lane, then lane groups 1 apart, then 2 apart), divides and stores.  No floating-point
+// atomics, vector stores only, equal inputs give equal bits.  The next operation writes the area
+// only behind its own flag barrier, which every wave reaches after its sums.
+//
+// Sites past the end: loads are clamped as the forward kernel clamps them (ls, ll: a lane past S reads
+// the last site's data, never a tile's padding, which no kernel writes); such lanes store nothing.
+//
+// Pipelining: plain.  The A copies of the operation's inner children are fetched (global -> wave-
+// private LDS, four 16-byte pieces per lane, no barrier) at the start of the operation, together
+// with the parent's vector and the children's tiles or table rows; the compiler overlaps those
+// independent loads with each other, and other waves of the CU cover the wait.  Nothing of
+// operation k + 1 is requested during operation k: no prefetch, no store deferral.
+//
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
+//   preorder_k20_walk<256, PosteriorK20>   VGPRs 190   SGPRs 98   scratch 0 B   2 waves per SIMD
+//   preorder_k20_walk<512, PosteriorK20>   VGPRs 190   SGPRs 98   scratch 0 B   2 waves per SIMD
+//   LDS (dynamic, k20_preorder_lds_bytes): R x 11 520 B + 128 B -- 46 208 B at R = 4, 92 288 B at R = 8
+// (the four products of an operation are unrolled side by side: 100 A operands in flight)
+#include <mutex>
+
+#include "common.hpp"
+#include "k20_preorder.hpp"
+#include "outer_plan.hpp"
+
+namespace rdamd {
+
+namespace {
+
+// k20_preorder.hpp restates the dealing of states and the tile without HIP: the same everywhere
+constexpr bool k20_layouts_agree() {
+  for (unsigned g = 0; g < 4; ++g)
+    for (unsigned t = 0; t < 5; ++t)
+      if (k20p_state_of(g, t) != k20_state_of(g, t)) return false;
+  for (unsigned c = 0; c < 16; ++c)
+    for (unsigned s = 0; s < 20; ++s)
+      if (k20p_tile_index(c, s) != k20_tile_index(c, s)) return false;
+  for (unsigned lane = 0; lane < 64; ++lane)
+    for (unsigned t = 0; t < 5; ++t)
+      if (k20p_lane_operand(lane, t) != k20_tile_index(lane & 15u, k20_state_of(lane >> 4, t))) return false;
+  return true;
+}
+static_assert(k20_layouts_agree(), "k20_preorder.hpp and common.hpp describe one layout");
+static_assert(k20_preorder_lds_bytes(kK20MaxRates) <= kK20LdsLimit, "LDS fits a CU at 8 rate categories");
+
+// what the walk reads and the one thing it writes, the workspace
+struct K20WalkArgs {
+  const double *clv;          // inner CLVs, [buffer][rate][tile][320]
+  size_t clv_stride;          // doubles per buffer
+  const uint8_t *tipcodes;
+  unsigned tip_stride;
+  const double *tiptab;       // [matrix][rate][code][20], rows in operand order
+  unsigned ncodes_cap;
+  const double *pmfma;        // [matrix][rate][400], the MFMA-ready copies
+  const double *freqs;        // [rate matrix][20]
+  const unsigned *fidx;       // rate -> frequency set
+  const double *rate_w;
+  unsigned tips, sites, tiles, R;
+  double *work;               // [slot][rate][tile][320]
+  const OuterOp *prog;
+  unsigned nops;
+};
+
+struct K20Lane {
+  unsigned lane, col, grp, r, tile, site, ll;   // ll: the lane whose data this lane loads (itself unless past S)
+  bool active;                                  // site < S
+  double pi[5], w;
+};
+
+// a lane's five operands of a tile (the tile's three pieces)
+__device__ __forceinline__ void load_tile(const double *tile, unsigned ll, double (&x)[5]) {
+  const double2 a = *reinterpret_cast<const double2 *>(tile + k20p_lane_operand(ll, 0));
+  const double2 b = *reinterpret_cast<const double2 *>(tile + k20p_lane_operand(ll, 2));
+  x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
+  x[4] = tile[k20p_lane_operand(ll, 4)];
+}
+__device__ __forceinline__ void store_tile(double *tile, unsigned lane, const double (&x)[5]) {
+  *reinterpret_cast<double2 *>(tile + k20p_lane_operand(lane, 0)) = make_double2(x[0], x[1]);
+  *reinterpret_cast<double2 *>(tile + k20p_lane_operand(lane, 2)) = make_double2(x[2], x[3]);
+  tile[k20p_lane_operand(lane, 4)] = x[4];
+}
+
+// d = P b (kTransposed: P^T b) on the matrix cores, P's staged copy in `copy` (LDS, wave-private)
+template <bool kTransposed>
+__device__ __forceinline__ void k20_product(const double *copy, unsigned col, unsigned grp, const double (&b)[5],
+                                            double (&d)[5]) {
+  const double *ap = copy + (kTransposed ? k20_a_transposed(0, 0, col, grp) : k20_a_forward(0, 0, col, grp));
+  double a[kK20Groups * kK20Steps];
+#pragma unroll
+  for (unsigned rg = 0; rg < kK20Groups; ++rg)
+#pragma unroll
+    for (unsigned ks = 0; ks < kK20Steps; ++ks)   // (block (rg, ks) forward, (ks, rg) transposed: 16 doubles each)
+      a[rg * kK20Steps + ks] = ap[kTransposed ? k20_copy_index(ks, rg, 0, 0) : k20_copy_index(rg, ks, 0, 0)];
+#pragma unroll
+  for (unsigned rg = 0; rg < kK20Groups; ++rg) {
+    d[rg] = 0.0;
+#pragma unroll
+    for (unsigned ks = 0; ks < kK20Steps; ++ks)
+      d[rg] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[rg * kK20Steps + ks], b[ks], d[rg], 0, 0, 0);
+  }
+}
+
+template <int MAXT, class Consumer>   // 64 x rate categories, rounded up to 256 or 512
+__global__ void __launch_bounds__(MAXT)
+preorder_k20_walk(K20WalkArgs a, typename Consumer::Args ca) {
+  extern __shared__ __attribute__((aligned(16))) double k20_lds[];
+  const unsigned R = a.R, S = a.sites;
+  K20Lane ln;
+  ln.lane = threadIdx.x & 63u;
+  ln.r = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave = rate
+  ln.col = ln.lane & 15u; ln.grp = ln.lane >> 4;
+  ln.tile = blockIdx.x;
+  ln.site = ln.tile * 16u + ln.col;
+  ln.active = ln.site < S;
+  const unsigned ls = ln.active ? ln.site : S - 1u;   // clamped for loads
+  ln.ll = ln.grp * 16u + (ls & 15u);
+  const unsigned lane = ln.lane, col = ln.col, grp = ln.grp, r = ln.r;
+  double *stage = k20_lds + (size_t)r * 2u * kK20CopyDoubles;                      // this wave's two A copies
+  double *exchange = k20_lds + (size_t)R * 2u * kK20CopyDoubles;                   // [child][rate][320]
+  unsigned *flags = reinterpret_cast<unsigned *>(exchange + (size_t)2u * R * kK20TileDoubles);   // [parity][16]
+  {
+    const double *f = a.freqs + (size_t)a.fidx[r] * kK20States;
+#pragma unroll
+    for (unsigned t = 0; t < 5; ++t) ln.pi[t] = f[k20p_state_of(grp, t)];
+  }
+  ln.w = a.rate_w[r];
+  const size_t tile_at = ((size_t)r * a.tiles + ln.tile) * kK20TileDoubles;        // this wave's tile in a CLV or a slot
+  const size_t slot_doubles = (size_t)R * a.tiles * kK20TileDoubles;
+
+  Consumer con(ca, exchange, R);
+  con.begin(a, ln, tile_at);
+
+  double u[5] = {0, 0, 0, 0, 0};   // the outer vector the next operation reads from registers
+  for (unsigned k = 0; k < a.nops; ++k) {
+    const OuterOp op = a.prog[k];
+    con.op_begin(ln, k);
+    // the A copies of the inner children: 3200 contiguous bytes each, global -> this wave's LDS
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (!op.inner[c]) continue;   // (wave-uniform)
+      const double2 *src = reinterpret_cast<const double2 *>(a.pmfma + ((size_t)op.child_mat[c] * R + r) * kK20CopyDoubles);
+      double2 *dst = reinterpret_cast<double2 *>(stage + (unsigned)c * kK20CopyDoubles);
+#pragma unroll
+      for (unsigned e = 0; e < 4; ++e) {
+        const unsigned at = lane + 64u * e;
+        if (at < kK20CopyDoubles / 2u) dst[at] = src[at];
+      }
+    }
+    double up[5];
+    if (op.parent_src == kOuterFromSlot) {
+      load_tile(a.work + (size_t)op.parent_slot * slot_doubles + tile_at, ln.ll, up);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 5; ++t) up[t] = op.parent_src == kOuterFromPi ? ln.pi[t] : u[t];
+    }
+    // the children: an inner child's CLV tile, a tip's finished term P . (0/1 vector) from its table row
+    double l[2][5], pl[2][5];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (op.inner[c]) {
+        load_tile(a.clv + (size_t)(op.child_clv[c] - a.tips) * a.clv_stride + tile_at, ln.ll, l[c]);
+      } else {
+        const unsigned code = a.tipcodes[(size_t)op.child_clv[c] * a.tip_stride + ls];
+        const double *row = a.tiptab + (((size_t)op.child_mat[c] * R + r) * a.ncodes_cap + code) * kK20States;
+        const double2 p01 = *reinterpret_cast<const double2 *>(row + grp * 2u);
+        const double2 p23 = *reinterpret_cast<const double2 *>(row + 8u + grp * 2u);
+        pl[c][0] = p01.x; pl[c][1] = p01.y; pl[c][2] = p23.x; pl[c][3] = p23.y;
+        pl[c][4] = row[16u + grp];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) l[c][t] = 0.0;   // (never read: a tip has no outer vector here)
+      }
+    }
+    __builtin_amdgcn_wave_barrier();   // the staged copies are read by other lanes of this wave than wrote them
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      if (op.inner[c]) k20_product<false>(stage + (unsigned)c * kK20CopyDoubles, col, grp, l[c], pl[c]);
+    // the children's outer vectors, and which sites of this rate are small
+    double uc[2][5];
+    unsigned bits = 0u;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (!op.inner[c]) continue;
+      double t[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) t[i] = up[i] * pl[1 - c][i];   // the parent's vector masked by the sibling
+      con.branch(ln, c, t, pl[c], l[c]);
+      k20_product<true>(stage + (unsigned)c * kK20CopyDoubles, col, grp, t, uc[c]);
+      const double m = fmax(fmax(fmax(uc[c][0], uc[c][1]), fmax(uc[c][2], uc[c][3])), uc[c][4]);
+      // across the four lane groups that hold the other states of a site (bit s = site s of the wave)
+      unsigned long long bm = __builtin_amdgcn_ballot_w64(m < kScaleThreshold);
+      bm &= bm >> 32;
+      bm &= bm >> 16;
+      bits |= ((unsigned)bm & 0xFFFFu) << (16 * c);
+    }
+    __builtin_amdgcn_wave_barrier();   // (the next operation's copies land only behind these reads)
+    if (lane == 0) flags[(k & 1u) * 16u + r] = bits;
+    __syncthreads();
+    unsigned all_bits = ~0u;
+    for (unsigned q = 0; q < R; ++q) all_bits &= flags[(k & 1u) * 16u + q];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (!op.inner[c]) continue;
+      if ((all_bits >> (16 * c + (int)col)) & 1u) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) uc[c][j] *= kScaleFactor;
+      }
+      con.outer(ln, c, op.node[c], uc[c], l[c]);
+      if (op.keep[c] == kOuterKeepReg) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) u[j] = uc[c][j];
+      } else if (op.keep[c] == kOuterKeepSlot && ln.active) {
+        store_tile(a.work + (size_t)op.slot[c] * slot_doubles + tile_at, lane, uc[c]);
+      }
+    }
+    con.op_end(a, ln, op.inner[0] != 0u, op.inner[1] != 0u);
+  }
+  con.end(ln);
+}
+
+// ---------------------------------------------------------------------------
+// Consumer: marginal ancestral state posteriors
+// ---------------------------------------------------------------------------
+struct PosteriorK20Args {
+  double *post;   // [node][site][20]
+};
+
+struct PosteriorK20 {
+  using Args = PosteriorK20Args;
+  const Args c;
+  double *const exchange;   // [child][rate][t][lane]
+  const unsigned R;
+  unsigned node[2] = {0u, 0u};
+  __device__ __forceinline__ PosteriorK20(const Args &c, double *exchange, unsigned R) : c(c), exchange(exchange), R(R) {}
+
+  // this wave's terms w_r U L of one node
+  __device__ __forceinline__ void put(const K20Lane &ln, int ch, const double (&u)[5], const double (&l)[5]) const {
+    double *o = exchange + ((size_t)ch * R + ln.r) * kK20TileDoubles + ln.lane;
+#pragma unroll
+    for (int t = 0; t < 5; ++t) o[64 * t] = ln.w * u[t] * l[t];
+  }
+  // (behind a barrier) one wave: the rates in order, the states of a site in one fixed order, the division
+  __device__ __forceinline__ void sum_and_store(const K20WalkArgs &a, const K20Lane &ln, int ch, unsigned nd) const {
+    double q[5] = {0, 0, 0, 0, 0};
+    for (unsigned r = 0; r < R; ++r) {
+      const double *o = exchange + ((size_t)ch * R + r) * kK20TileDoubles + ln.lane;
+#pragma unroll
+      for (int t = 0; t < 5; ++t) q[t] += o[64 * t];
+    }
+    double den = ((q[0] + q[1]) + (q[2] + q[3])) + q[4];
+    den += __shfl_xor(den, 16);
+    den += __shfl_xor(den, 32);
+    if (!ln.active) return;
+    double *o = c.post + ((size_t)nd * a.sites + ln.site) * kK20States;
+#pragma unroll
+    for (unsigned t = 0; t < 5; ++t) o[k20p_state_of(ln.grp, t)] = q[t] / den;
+  }
+  __device__ __forceinline__ void begin(const K20WalkArgs &a, const K20Lane &ln, size_t tile_at) const {   // the root: U = pi
+    double l[5];
+    load_tile(a.clv + (size_t)(a.prog[0].parent_clv - a.tips) * a.clv_stride + tile_at, ln.ll, l);
+    put(ln, 0, ln.pi, l);
+    __syncthreads();
+    if (ln.r == 0u) sum_and_store(a, ln, 0, 0u);
+  }
+  __device__ __forceinline__ void op_begin(const K20Lane &, unsigned) const {}
+  __device__ __forceinline__ void branch(const K20Lane &, int, const double (&)[5], const double (&)[5],
+                                         const double (&)[5]) const {}
+  __device__ __forceinline__ void outer(const K20Lane &ln, int ch, unsigned nd, const double (&uc)[5], const double (&l)[5]) {
+    node[ch] = nd;
+    put(ln, ch, uc, l);
+  }
+  // every wave of the workgroup comes here with the same two flags
+  __device__ __forceinline__ void op_end(const K20WalkArgs &a, const K20Lane &ln, bool inner0, bool inner1) const {
+    if (!inner0 && !inner1) return;
+    __syncthreads();
+    if (inner0 && ln.r == 0u) sum_and_store(a, ln, 0, node[0]);
+    if (inner1 && ln.r == 1u % R) sum_and_store(a, ln, 1, node[1]);
+  }
+  __device__ __forceinline__ void end(const K20Lane &) const {}
+};
+
+// state[row] = the smallest index among the largest of post[row][0..K), prob[row] = that posterior.
+// A workgroup's 256 rows come through LDS: the loads are contiguous over the workgroup (a lane
+// reading its own row would stride 8 K bytes from its neighbour: measured 0.66 ms for c3's 318 MB),
+// then one lane scans one row, rows an odd number of doubles apart so that they spread over the banks.
+constexpr unsigned kArgmaxRows = 256;
+__host__ __device__ constexpr unsigned argmax_pitch(unsigned K) { return K | 1u; }
+
+__global__ void __launch_bounds__(kArgmaxRows)
+ancestral_argmax_kernel(const double *__restrict__ post, size_t rows, unsigned K, uint8_t *__restrict__ state,
+                        double *__restrict__ prob) {
+  extern __shared__ __attribute__((aligned(16))) double argmax_lds[];   // [256][argmax_pitch(K)]
+  const size_t row0 = (size_t)blockIdx.x * kArgmaxRows;
+  const unsigned n = rows - row0 < kArgmaxRows ? (unsigned)(rows - row0) : kArgmaxRows;   // rows of this workgroup
+  const unsigned pitch = argmax_pitch(K);
+  const double *src = post + row0 * K;
+  for (unsigned e = threadIdx.x; e < n * K; e += kArgmaxRows) argmax_lds[(e / K) * pitch + e % K] = src[e];
+  __syncthreads();
+  if (threadIdx.x >= n) return;
+  const size_t row = row0 + threadIdx.x;
+  const double *p = argmax_lds + threadIdx.x * pitch;
+  double best = p[0];
+  unsigned at = 0;
+  for (unsigned j = 1; j < K; ++j) {
+    const double v = p[j];
+    if (v > best) { best = v; at = j; }
+  }
+  state[row] = (uint8_t)at;
+  prob[row] = best;
+}
+
+}  // namespace
+
+hipError_t launch_outer_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                    double *d_work, double *d_post) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const unsigned R = p->rate_cats;
+  if (!p->mfma_layout || R > kK20MaxRates) return hipErrorInvalidValue;
+  K20WalkArgs a;
+  a.clv = p->d_clv; a.clv_stride = p->clv_doubles();
+  a.tipcodes = p->d_tipcodes; a.tip_stride = p->tip_stride();
+  a.tiptab = p->d_tiptab; a.ncodes_cap = p->ncodes_cap;
+  a.pmfma = p->d_pmat_mfma; a.freqs = p->d_freqs; a.fidx = d_fidx; a.rate_w = p->d_rate_weights;
+  a.tips = p->tips; a.sites = p->sites; a.tiles = p->clv_tiles(); a.R = R;
+  a.work = d_work; a.prog = d_prog; a.nops = nops;
+  const PosteriorK20Args ca{d_post};
+  const size_t lds = k20_preorder_lds_bytes(R);
+  if (R <= 4) {
+    preorder_k20_walk<256, PosteriorK20><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+  } else {
+    {   // six categories and up pass the 64 KB a kernel may ask for by default
+      static std::mutex lds_mu;
+      static bool lds_allowed = false;
+      std::lock_guard<std::mutex> guard(lds_mu);
+      if (!lds_allowed) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&preorder_k20_walk<512, PosteriorK20>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)k20_preorder_lds_bytes(kK20MaxRates));
+        if (e != hipSuccess) return e;
+        lds_allowed = true;
+      }
+    }
+    preorder_k20_walk<512, PosteriorK20><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_ancestral_argmax(rdamd_partition *p, const double *d_post, size_t rows, unsigned K, uint8_t *d_state,
+                                   double *d_prob) {
+  if (rows == 0) return hipSuccess;
+  const size_t blocks = (rows + 255) / 256;
+  if (blocks > 0x7FFFFFFFu) return hipErrorInvalidValue;
+  const size_t lds = (size_t)kArgmaxRows * argmax_pitch(K) * sizeof(double);
+  if (lds > 64 * 1024) return hipErrorInvalidValue;   // (no caller: 2, 4 and 20 states reach here, 43 KB at most)
+  ancestral_argmax_kernel<<<(unsigned)blocks, kArgmaxRows, lds, p->stream>>>(d_post, rows, K, d_state, d_prob);
+  return hipGetLastError();
+}
+
+}  // namespace rdamd

@@ -544,6 +544,58 @@ void model_t::ancestral(const root_location_t &rl, const std::vector<partition_p
   });
 }
 
+// Ancestral sequences at one root: ancestral's traversal, then rdamd_ancestral_sequences per
+// partition, the partitions' columns side by side in every node's row.  Saves and restores what
+// ancestral does.
+void model_t::ancestral_sequences(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                                  std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
+                                  std::vector<unsigned> *node_children, uint8_t *state, double *prob, double *post) {
+  refuse_site_group("ancestral_sequences", "per-site output of a site-sharded model is not supported");
+  const size_t P = _partitions.size(), total = pattern_count();
+  if (params) require_fit(*params, "ancestral_sequences", "");
+  for (size_t p = 1; p < P; ++p)
+    if (rdamd_partition_states(_partitions[p]) != rdamd_partition_states(_partitions[0]))
+      throw std::invalid_argument("ancestral_sequences: partitions " + std::to_string(p) + " and 0 have different state "
+                                  "counts; the outputs have one");
+  with_saved_parameters(true, [] {}, [&] {
+    if (params) set_model_params(*params);
+    auto sched = _tree.generate_operations(rl);
+    const auto &ops = std::get<0>(sched);
+    const unsigned n_ops = (unsigned)ops.size();
+    if (node_clv) node_clv->resize(n_ops);
+    if (node_parent) node_parent->resize(n_ops);
+    if (node_children) node_children->resize(2 * (size_t)n_ops);
+    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, node_clv ? node_clv->data() : nullptr,
+                                       node_parent ? node_parent->data() : nullptr,
+                                       node_children ? node_children->data() : nullptr) != RDAMD_SUCCESS)
+      fail("marginal_ancestral_nodes");
+    update_pmatrices(std::get<1>(sched), std::get<2>(sched));
+    ++_n_full;
+    size_t at = 0;   // first pattern of the partition in the concatenated list
+    std::vector<uint8_t> part_state;
+    std::vector<double> part_prob, part_post;
+    for (size_t p = 0; p < P; ++p) {
+      rdamd_partition_t *part = _partitions[p];
+      const size_t sites = rdamd_partition_sites(part), K = rdamd_partition_states(part);
+      rdamd_update_clvs(part, ops.data(), n_ops);
+      if (rdamd_errno()) fail("update_clvs");
+      if (state) part_state.resize((size_t)n_ops * sites);
+      if (prob) part_prob.resize((size_t)n_ops * sites);
+      if (post) part_post.resize((size_t)n_ops * sites * K);
+      if (rdamd_ancestral_sequences(part, ops.data(), n_ops, _param_indicies[p].data(), state ? part_state.data() : nullptr,
+                                    prob ? part_prob.data() : nullptr, post ? part_post.data() : nullptr) != RDAMD_SUCCESS)
+        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+      for (size_t k = 0; k < n_ops; ++k) {
+        if (state) std::copy(part_state.begin() + k * sites, part_state.begin() + (k + 1) * sites, state + k * total + at);
+        if (prob) std::copy(part_prob.begin() + k * sites, part_prob.begin() + (k + 1) * sites, prob + k * total + at);
+        if (post)
+          std::copy(part_post.begin() + k * sites * K, part_post.begin() + (k + 1) * sites * K, post + (k * total + at) * K);
+      }
+      at += sites;
+    }
+  });
+}
+
 // Branch-length derivatives at one root, and (bounds given) the lengths that maximise lnL there.
 // One evaluation at lengths x: update_pmatrices on the schedule's matrix indices with x, a
 // materialising traversal, the root lnL, and rdamd_branch_derivatives per partition, summed in

@@ -147,6 +147,14 @@ public:
   void ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                  std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
                  std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate);
+  // Ancestral sequences at one root (rdamd_model_ancestral_sequences): the likeliest state of every
+  // inner node and pattern, state[nodes][pattern_count()], with its posterior prob[...] and, on
+  // request, the table post[nodes][pattern_count()][states]; any output may be null.  Takes 20-state
+  // partitions too (rdamd_ancestral_sequences); all partitions must have one state count.  Nodes,
+  // params, saving and restoring as ancestral.
+  void ancestral_sequences(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
+                           std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
+                           std::vector<unsigned> *node_children, uint8_t *state, double *prob, double *post);
 
   // First and second derivatives of lnL in every branch length at one root, and the lengths that
   // maximise lnL there (include/root_digger_amd.h, rdamd_model_branch_derivatives /

@@ -433,6 +433,28 @@ static std::vector<rdamd::partition_parameters_t> one_root_params(const rdamd_mo
     }
   return params;
 }
+int rdamd_model_ancestral_sequences(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
+                                    const double *values, unsigned int *n_nodes, unsigned int *node_clv,
+                                    int *node_parent, unsigned int *node_children, uint8_t *state_out,
+                                    double *prob_out, double *post_out) {
+  GUARD(RDAMD_FAILURE, {
+    if (refuse_site_sharded(m, "rdamd_model_ancestral_sequences")) return RDAMD_FAILURE;
+    if ((counts == nullptr) != (values == nullptr))
+      throw std::invalid_argument("rdamd_model_ancestral_sequences: counts and values come together");
+    if (!rl) throw std::invalid_argument("rdamd_model_ancestral_sequences: null argument");
+    std::vector<rdamd::partition_parameters_t> params;
+    if (counts) params = one_root_params(m, counts, values);
+    std::vector<unsigned> clv, children;
+    std::vector<int> parent;
+    m->model->ancestral_sequences(to_cpp(rl), counts ? &params : nullptr, &clv, &parent, &children, state_out, prob_out,
+                                  post_out);
+    if (n_nodes) *n_nodes = (unsigned)clv.size();
+    if (node_clv) std::copy(clv.begin(), clv.end(), node_clv);
+    if (node_parent) std::copy(parent.begin(), parent.end(), node_parent);
+    if (node_children) std::copy(children.begin(), children.end(), node_children);
+    return RDAMD_SUCCESS;
+  })
+}
 static void copy_branch_result(const rdamd::model_t::branch_lengths_t &r, unsigned int *n_nodes, unsigned int *node_clv,
                                int *node_parent, unsigned int *node_children, double *lengths_out, double *d1_out,
                                double *d2_out) {

@@ -450,14 +450,33 @@ static bool outer_refused(const rdamd_partition *p, const char *what) {
   return false;
 }
 
-// What rdamd_marginal_ancestral and rdamd_branch_derivatives share, in two steps: preorder_admitted,
-// then preorder_run.  (RateIndices: a per-rate-category index vector of the caller and its name.)
+// ... and the shapes rdamd_ancestral_sequences does not take: it walks 4-state, binary and matrix-core
+// 20-state partitions
+static bool sequences_refused(const rdamd_partition *p, const char *what) {
+  if (p->sparse) {
+    set_error(63, "%s: partitions with RDAMD_ATTRIB_SPARSE_CLVS are not supported (the pass reads every inner CLV of a "
+                  "materialising traversal)", what);
+    return true;
+  }
+  if (p->states == 4 || p->mfma_layout) return false;
+  if (p->states == 20)
+    set_error(63, "%s: 20-state partitions with %u rate categories are not supported (the matrix-core layout the walk "
+                  "reads holds up to 8 categories and CLVs under 2 GB)", what, p->rate_cats);
+  else
+    set_error(63, "%s: %u-state partitions are not supported (ancestral sequences are computed for 2, 4 and 20 states)",
+              what, p->api_states);
+  return true;
+}
+
+// What the entry points of the pre-order pass share, in two steps: preorder_admitted, then
+// preorder_run.  (RateIndices: a per-rate-category index vector of the caller and its name.)
 struct RateIndices { const unsigned *host; const char *name; };
 
-// the refusals and the plan; false: refused, the error set in the name of entry point `what`
+// the refusals (by shape: `refused`) and the plan; false: refused, the error set in the name of entry point `what`
 static bool preorder_admitted(const rdamd_partition *p, const char *what, const rdamd_operation_t *ops, unsigned n_ops,
-                              bool null_argument, std::initializer_list<RateIndices> indices, OuterPlan *plan) {
-  if (outer_refused(p, what)) return false;
+                              bool null_argument, std::initializer_list<RateIndices> indices, OuterPlan *plan,
+                              bool (*refused)(const rdamd_partition *, const char *) = outer_refused) {
+  if (refused(p, what)) return false;
   if (null_argument) {
     set_error(64, "%s: null argument", what);
     return false;
@@ -1178,6 +1197,49 @@ int rdamd_marginal_ancestral(rdamd_partition_t *p, const rdamd_operation_t *ops,
   };
   if (preorder_run(p, plan, indices, &g_ancestral_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
   RDAMD_HIP_TRY(hipMemcpy(post_out, post.d, sizeof(double) * post_doubles, hipMemcpyDeviceToHost), RDAMD_FAILURE);
+  return RDAMD_SUCCESS;
+}
+
+// ---- ancestral sequences: the likeliest state of every inner node and column (4-state and binary
+// partitions: the posterior launch above; matrix-core 20-state ones: kernels_preorder_k20.hip), then the arg-max
+static thread_local double g_sequences_ms = 0.0;
+
+double rdamd_ancestral_sequences_last_ms(void) { return g_sequences_ms; }
+
+int rdamd_ancestral_sequences(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                              const unsigned int *freqs_indices, uint8_t *state_out, double *prob_out, double *post_out) {
+  clear_error();
+  g_sequences_ms = 0.0;
+  const std::initializer_list<RateIndices> indices = {{freqs_indices, "freqs"}};
+  OuterPlan plan;
+  if (!preorder_admitted(p, "rdamd_ancestral_sequences", ops, n_ops, !ops || !freqs_indices, indices, &plan,
+                         sequences_refused))
+    return RDAMD_FAILURE;
+  if (p->sites == 0) return RDAMD_SUCCESS;
+  const unsigned K = p->api_states;
+  const size_t rows = (size_t)n_ops * p->sites;
+  DeviceArray<double> post, prob;   // the table stays on the device unless the caller asks for it
+  DeviceArray<uint8_t> state;
+  const auto allocate = [&] {
+    hipError_t e = post.alloc(rows * K);
+    if (e == hipSuccess) e = prob.alloc(rows);
+    if (e == hipSuccess) e = state.alloc(rows);
+    if (e == hipSuccess) e = flush_tiptab(p);
+    return e;
+  };
+  const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    hipError_t e = p->mfma_layout ? launch_outer_program_k20(p, d_prog, n_ops, d_indices[0], d_work, post.d)
+                                  : launch_outer_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_work, post.d);
+    if (e == hipSuccess) e = launch_ancestral_argmax(p, post.d, rows, K, state.d, prob.d);
+    return e;
+  };
+  if (preorder_run(p, plan, indices, &g_sequences_ms, allocate, launch) != RDAMD_SUCCESS) return RDAMD_FAILURE;
+  hipError_t e = hipSuccess;
+  if (state_out) e = hipMemcpy(state_out, state.d, rows, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && prob_out) e = hipMemcpy(prob_out, prob.d, sizeof(double) * rows, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && post_out) e = hipMemcpy(post_out, post.d, sizeof(double) * rows * K, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) g_sequences_ms = 0.0;
+  RDAMD_HIP_TRY(e, RDAMD_FAILURE);
   return RDAMD_SUCCESS;
 }
 

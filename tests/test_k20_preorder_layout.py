@@ -1,0 +1,25 @@
+"""The 20-state pre-order walk's index arithmetic (csrc/k20_preorder.hpp), without a GPU:
+tests/cpp/k20_preorder_check.cpp emulates the four-block 4x4x4 FP64 MFMA by its lane map and forms
+the forward product P c and the transposed product P^T t through the header's gather functions from
+ONE MFMA-ready copy of a random asymmetric matrix -- both must equal the dense products in every
+lane, exactly (small integers), and swapped-index variants must not.  Also the walk's LDS bound at
+1 to 8 rate categories.  Built plainly and as a stand-alone AddressSanitizer + UBSan program."""
+import os
+import subprocess
+
+import pytest
+
+import util
+
+SRC = os.path.join(util.ROOT, "tests", "cpp", "k20_preorder_check.cpp")
+INCLUDES = ["-I", os.path.join(util.ROOT, "root_digger_amd", "csrc")]
+
+
+@pytest.mark.parametrize("flags", [[], ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],
+                         ids=["plain", "asan_ubsan"])
+def test_k20_preorder_gathers(tmp_path, flags):
+    exe = str(tmp_path / "k20_preorder_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror"] + flags + INCLUDES + [SRC, "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.startswith("k20 preorder OK"), (out.stdout[-2000:], out.stderr[-2000:])
+    assert int(out.stdout.split()[-1]) > 90000
