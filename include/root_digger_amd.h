@@ -1075,15 +1075,35 @@ int rdamd_model_ancestral_sequences(rdamd_model_t *m, const rdamd_root_location_
 int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
                              const unsigned int *params_indices, const unsigned int *freqs_indices,
                              double *d1_out, double *d2_out);
-/* device time of the two launches of this thread's last rdamd_branch_derivatives call,
- * milliseconds between two HIP events (0 after a failed call); for measurements */
+/* device time of the two launches of this thread's last rdamd_branch_derivatives or
+ * rdamd_branch_length_derivatives call, milliseconds between two HIP events (0 after a failed
+ * call); for measurements */
 double rdamd_branch_last_ms(void);
+/* The same derivatives -- for DNA, binary AND protein data.  Arguments, outputs, precondition and the
+ * definitions above are those of rdamd_branch_derivatives.  4-state and binary partitions run
+ * rdamd_branch_derivatives' two launches (d1_out and d2_out have its bits).  Matrix-core 20-state
+ * partitions (20 states, up to 8 rate categories) run the walk of rdamd_ancestral_sequences with a
+ * derivative consumer: a wave is 16 sites of one rate category, z = Q_r y and z2 = Q_r z are 25
+ * v_mfma_f64_4x4x4_4b_f64 each, their A operand a matrix-core copy of Q_r that the call builds on the
+ * host and uploads; with d2_out NULL z2 is not formed.  The sums are made in one fixed order without
+ * floating-point atomics -- the states of a site, the rate categories in their order, the 16 sites
+ * of a tile, then the tiles by increasing number in a second small launch --: two calls with the
+ * same inputs return the same bits.  Tip children have branches here too.  Zero sites: zeros and
+ * success.  Refused (error 63, nothing launched, the shape named): partitions with
+ * RDAMD_ATTRIB_SPARSE_CLVS, state counts other than 2, 4 and 20, 20 states with more than 8 rate
+ * categories (the plain CLV layout).  Errors 64, 10, 7 and 65 as for rdamd_branch_derivatives.
+ * rdamd_branch_last_ms reports this call's two launches. */
+int rdamd_branch_length_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                                    const unsigned int *params_indices, const unsigned int *freqs_indices,
+                                    double *d1_out, double *d2_out);
 /* The same for one root of a model.  Parameters in the checkpoint's layout exactly as
  * rdamd_model_ancestral takes them.  Outputs, any of which may be NULL: *n_nodes, node_clv,
  * node_parent, node_children as there; lengths_out[n][2]: the schedule's current length of branch
  * (k, c); d1_out[n][2], d2_out[n][2]: summed over partitions in partition order; *lnl_out: the
  * log-likelihood at that root.  The model's parameters, its rooting and the conditional
- * likelihoods of that rooting are as before when the call returns.  Refused (error 61) for a model
+ * likelihoods of that rooting are as before when the call returns.  Every partition goes through
+ * rdamd_branch_length_derivatives: DNA, binary and protein models are served, and a partition whose
+ * shape that call refuses fails this one and is named in the message.  Refused (error 61) for a model
  * that sums over a site group. */
 int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t *rl,
                                    const uint64_t *counts, const double *values, unsigned int *n_nodes,
@@ -1094,7 +1114,7 @@ int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t
  * model or its tree: the lengths are an output (lengths_out[n][2], nodes as above), with d1_out /
  * d2_out at those lengths; on return the model is bit for bit what it was.  Each evaluation at
  * lengths x is rdamd_update_prob_matrices on the schedule's matrix indices with x, a materialising
- * traversal, the root lnL, and rdamd_branch_derivatives per partition.
+ * traversal, the root lnL, and rdamd_branch_length_derivatives per partition.
  * The method is a projected L-BFGS (memory 8) whose initial metric is the diagonal Newton one:
  * a branch is free unless it sits at a bound with the gradient pointing out; curvature
  * c_b = -d2_b where d2_b < 0, else |d1_b| / max(x_b, min_len) (1 where that is 0); it stops with

@@ -308,6 +308,7 @@ _sig("rdamd_model_ancestral_sequences", C.c_int, _vp, C.POINTER(RootLocation), _
 _sig("rdamd_tree_newick_ancestral", _vp, _vp, _u, _pu)
 _sig("rdamd_tree_newick_branch_lengths", _vp, _vp, _u, _pu, _pd)
 _sig("rdamd_branch_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd)
+_sig("rdamd_branch_length_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd)
 _sig("rdamd_branch_last_ms", C.c_double)
 _sig("rdamd_model_gradient", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pd, _pd)
 _sig("rdamd_branch_pair_sums",C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd, _pd)
@@ -827,6 +828,21 @@ class Partition:
         d2 = np.zeros((len(ops), 2), dtype=np.float64)
         if lib.rdamd_branch_derivatives(self._h, ops, len(ops), _uptr(pi), _uptr(fi), _dptr(d1), _dptr(d2)) != 1:
             _fail("branch_derivatives")
+        return d1, d2
+
+    def branch_length_derivatives(self, ops, params_indices=None, freqs_indices=None, second=True):
+        """branch_derivatives for 4-state, binary AND matrix-core 20-state partitions
+        (rdamd_branch_length_derivatives) -> (d1[len(ops)][2], d2[len(ops)][2]); second=False: d2 is not
+        computed and None is returned in its place.  Call update_prob_matrices and update_clvs on this
+        list first."""
+        ops = _op_array(ops)
+        pi = self.params_indices if params_indices is None else np.ascontiguousarray(params_indices, dtype=np.uint32)
+        fi = pi if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        d1 = np.zeros((len(ops), 2), dtype=np.float64)
+        d2 = np.zeros((len(ops), 2), dtype=np.float64) if second else None
+        if lib.rdamd_branch_length_derivatives(self._h, ops, len(ops), _uptr(pi), _uptr(fi), _dptr(d1),
+                                               _dptr(d2) if second else None) != 1:
+            _fail("branch_length_derivatives")
         return d1, d2
 
     def branch_pair_sums(self, ops, freqs_indices=None, workspace_bytes=0):

@@ -304,6 +304,24 @@ hipError_t launch_site_rates(rdamd_partition *p, unsigned clv_phys_index, const 
 hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
                                 const unsigned *d_pidx, const unsigned *d_fidx, double *d_work, double *d_partials,
                                 unsigned *d_bad_sites, double *d_out);
+// the two site terms of a branch from the sums over rates, for both walks' derivative consumers;
+// false: the site has no likelihood
+__device__ __forceinline__ bool site_terms(double f0, double f1, double f2, double weight, double *d1, double *d2) {
+  if (!(f0 > 0.0) || !isfinite(f0) || !isfinite(f1) || !isfinite(f2)) { *d1 = 0.0; *d2 = 0.0; return false; }
+  const double g = f1 / f0;
+  *d1 = weight * g;
+  *d2 = weight * (f2 / f0 - g * g);
+  return true;
+}
+// its second launch alone: d_out[e] = d_partials[b][e] added by increasing b < blocks, e < entries
+hipError_t launch_brlen_sum(rdamd_partition *p, const double *d_partials, unsigned blocks, unsigned entries, double *d_out);
+// kernels_preorder_k20.hip: the same two launches over a 20-state partition in the matrix-core operand
+// layout, one workgroup per tile: d_qcopy: [rate][400], the MFMA-ready copy (k20_preorder.hpp,
+// k20_pack_copy) of the normalised rate matrix of every category; d_partials: [clv_tiles][nops][4];
+// second = false: d2 is not formed (those entries of d_out are not to be read)
+hipError_t launch_brlen_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                    double *d_work, const double *d_qcopy, double *d_partials, unsigned *d_bad_sites,
+                                    bool second, double *d_out);
 
 // pair sums over the same program, in passes of at most blocks_per_pass (>= 1) whole workgroups:
 // doubles of one workgroup's row of partials (= of d_out: [nops][2][R][16] pair sums, then [R][5]:

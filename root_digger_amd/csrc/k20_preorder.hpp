@@ -1,8 +1,10 @@
 // The 20-state pre-order walk's index arithmetic (kernels_preorder_k20.hip): where a lane finds its
 // A operand of the forward product P L and of the transposed product P^T t in the ONE MFMA-ready
-// copy of a P-matrix, and the sizes of the walk's workspace and LDS.  Pure constexpr arithmetic over
-// plain numbers -- no HIP, no partition -- so that tests/cpp/k20_preorder_check.cpp can emulate the
-// matrix cores' lane map on the host and prove both gathers before any GPU run.
+// copy of a P-matrix, the sizes of the walk's workspace and LDS, the host-side packing of such a copy
+// (the derivative consumer's rate matrices) and that consumer's LDS layout.  Plain arithmetic over
+// plain numbers -- no HIP, no partition -- so that tests/cpp/k20_preorder_check.cpp and
+// tests/cpp/k20_qcopy_check.cpp can emulate the matrix cores' lane map on the host and prove the
+// gathers and the packing before any GPU run.
 //
 // Lanes (kernels_clv_mfma.hip): col = lane % 16 is the site of the wave's tile, grp = lane / 16; a
 // vector of 20 states lives as five doubles per lane, operand t = state k20p_state_of(grp, t).
@@ -48,6 +50,17 @@ constexpr unsigned k20_a_transposed(unsigned rg, unsigned ks, unsigned col, unsi
   return k20_copy_index(ks, rg, col & 3u, grp);
 }
 
+// The MFMA-ready copy of a dense row-major 20 x 20 matrix, built on the host: what pmat_to_mfma_kernel
+// makes of a P-matrix on the device, for the matrices that never pass through it (the derivative
+// consumer's normalised rate matrices).  m: [20][20], copy: [kK20CopyDoubles].
+inline void k20_pack_copy(const double *m, double *copy) {
+  for (unsigned rg = 0; rg < kK20Groups; ++rg)
+    for (unsigned ks = 0; ks < kK20Steps; ++ks)
+      for (unsigned k = 0; k < 4u; ++k)
+        for (unsigned i = 0; i < 4u; ++i)
+          copy[k20_copy_index(rg, ks, k, i)] = m[k20p_state_of(i, rg) * kK20States + k20p_state_of(k, ks)];
+}
+
 // workspace of a program with `slots` slots: outer vectors in the operand layout, whole tiles
 constexpr size_t k20_preorder_workspace_doubles(size_t slots, size_t rate_cats, size_t tiles) {
   return slots * rate_cats * tiles * kK20TileDoubles;
@@ -64,5 +77,24 @@ constexpr size_t k20_preorder_lds_bytes(size_t rate_cats) {
 }
 constexpr size_t kK20LdsLimit = 160 * 1024;   // one CU's LDS on gfx950
 static_assert(k20_preorder_lds_bytes(kK20MaxRates) <= kK20LdsLimit, "the walk's LDS fits a CU at 8 rate categories");
+
+// The derivative consumer's use of the exchange area, in doubles from its start: the R staged copies
+// of the rate matrices ([rate][400]), then the per-rate terms w f0, w rho f1, w rho^2 f2 of both
+// children of an operation, double-buffered by operation parity ([parity][child][rate][3][16 sites])
+constexpr size_t k20_brlen_term_doubles(size_t rate_cats) { return 2 * 2 * rate_cats * 3 * 16; }
+constexpr size_t k20_brlen_terms_at(size_t rate_cats) { return rate_cats * kK20CopyDoubles; }
+constexpr size_t k20_brlen_term_index(size_t rate_cats, unsigned parity, unsigned child, unsigned rate, unsigned term,
+                                      unsigned site_in_tile) {
+  return k20_brlen_terms_at(rate_cats) + (((parity * 2u + child) * rate_cats + rate) * 3u + term) * 16u + site_in_tile;
+}
+constexpr size_t k20_brlen_exchange_doubles(size_t rate_cats) {
+  return k20_brlen_terms_at(rate_cats) + k20_brlen_term_doubles(rate_cats);
+}
+constexpr bool k20_brlen_fits_exchange() {
+  for (size_t r = 1; r <= kK20MaxRates; ++r)
+    if (k20_brlen_exchange_doubles(r) * sizeof(double) > k20_preorder_exchange_bytes(r)) return false;
+  return true;
+}
+static_assert(k20_brlen_fits_exchange(), "the derivative consumer lives in the exchange area: the walk's LDS does not grow");
 
 }  // namespace rdamd

@@ -411,14 +411,7 @@ struct PosteriorGeneric {
 // ---------------------------------------------------------------------------
 // Consumer: first and second derivative of lnL in every branch length
 // ---------------------------------------------------------------------------
-// the two site terms of a branch from the sums over rates; false: the site has no likelihood
-__device__ __forceinline__ bool site_terms(double f0, double f1, double f2, double weight, double *d1, double *d2) {
-  if (!(f0 > 0.0) || !isfinite(f0) || !isfinite(f1) || !isfinite(f2)) { *d1 = 0.0; *d2 = 0.0; return false; }
-  const double g = f1 / f0;
-  *d1 = weight * g;
-  *d2 = weight * (f2 / f0 - g * g);
-  return true;
-}
+// (site_terms, the two site terms of a branch from the sums over rates: common.hpp, shared with kernels_preorder_k20.hip)
 
 // The four waves' sums of operation k wait in wsum[k & 1] (written before the operation's barrier)
 // and are added in wave order after it, by the first four threads of the workgroup.
@@ -1037,8 +1030,11 @@ hipError_t launch_brlen_program(rdamd_partition *p, const OuterOp *d_prog, unsig
   const DerivativeArgs ca{p->d_q, d_pidx, p->d_rates, p->d_pattern_weights, d_partials, d_bad_sites};
   const hipError_t e = launch_walk<DerivativeDna, DerivativeGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca);
   if (e != hipSuccess) return e;
-  const unsigned entries = nops * 4;
-  brlen_sum_kernel<<<(entries + 255) / 256, 256, 0, p->stream>>>(d_partials, preorder_blocks(p), entries, d_out);
+  return launch_brlen_sum(p, d_partials, preorder_blocks(p), nops * 4, d_out);
+}
+
+hipError_t launch_brlen_sum(rdamd_partition *p, const double *d_partials, unsigned blocks, unsigned entries, double *d_out) {
+  brlen_sum_kernel<<<(entries + 255) / 256, 256, 0, p->stream>>>(d_partials, blocks, entries, d_out);
   return hipGetLastError();
 }
 

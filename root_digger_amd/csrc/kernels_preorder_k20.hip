@@ -1,6 +1,7 @@
 // The pre-order pass for 20-state partitions in the matrix-core operand layout
 // (rdamd_partition::mfma_layout): the OUTER vectors of kernels_preorder.hip on
-// v_mfma_f64_4x4x4_4b_f64, and their first consumer, the marginal ancestral state posteriors.
+// v_mfma_f64_4x4x4_4b_f64, and their consumers: the marginal ancestral state posteriors, and the
+// first and second derivative of lnL in every branch length.
 //
 // New here -- the reference computes no ancestral states; this extends the traversal it makes with
 // corax_update_clvs (src/model.cpp:402) by the complementary pass, for protein data.  Definitions as
@@ -39,6 +40,30 @@
 // atomics, vector stores only, equal inputs give equal bits.  The next operation writes the area
 // only behind its own flag barrier, which every wave reaches after its sums.
 //
+// A consumer that sets kTipBranches is told of tip children too (kernels_preorder.hip's switch): a tip
+// has a branch and no outer vector, so `branch` gets y = its table row and t = up (.) pl_sibling and
+// the walk goes on to the next child.  With the switch off the walk compiles to what it was.
+//
+// The derivatives (DerivativeK20; definitions: include/root_digger_amd.h, "Analytic branch-length
+// derivatives"): per branch, site and rate  z = Q_r y,  z2 = Q_r z,  25 MFMAs each through the
+// forward product, A = an MFMA-ready copy of the normalised rate matrix of set params_indices[r] --
+// built on the host (k20_preorder.hpp, k20_pack_copy; proven by tests/cpp/k20_qcopy_check.cpp),
+// uploaded in the call frame, staged into LDS by each wave once, in `begin`.  rho_r enters through
+// w_r rho_r and w_r rho_r^2.  With d2_out NULL a template flag drops the second product.
+// Fixed-order sums, no floating-point atomics: t.y, t.z, t.z2 over the lane's five states in one
+// order, the four lane groups by __shfl_xor 16, then 32; each wave leaves its three terms per site
+// in LDS, and behind the walk's barrier of the operation wave 0 adds the rates in rate order (lanes
+// 0-15: child 0, 16-31: child 1), forms the site terms by site_terms' rule (a site whose f0 is 0 or
+// not finite gives zeros and bumps the integer bad_sites counter), adds the tile's 16 sites by a
+// butterfly (a lane past S adds zeros) and writes partials[tile][operation][4]; brlen_sum_kernel
+// (kernels_preorder.hip) then adds the tiles by increasing number.  Equal inputs give equal bits.
+// LDS hazard: `branch` runs before the operation's barrier, and wave 0 adds operation k's terms while
+// the other waves already write those of operation k + 1.  The terms are DOUBLE-BUFFERED by
+// operation parity, as the flags are; no barrier was added.  Parity p is written again in operation
+// k + 2, behind the barrier of operation k + 1, which wave 0 reaches after its reads.
+// LDS: the copies (R x 3 200 B) and the terms (R x 1 536 B) live in the exchange area (R x 5 120 B):
+// k20_preorder_lds_bytes is unchanged (static_assert in k20_preorder.hpp).
+//
 // Sites past the end: loads are clamped as the forward kernel clamps them (ls, ll: a lane past S reads
 // the last site's data, never a tile's padding, which no kernel writes); such lanes store nothing.
 //
@@ -51,7 +76,11 @@
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage):
 //   preorder_k20_walk<256, PosteriorK20>   VGPRs 190   SGPRs 98   scratch 0 B   2 waves per SIMD
 //   preorder_k20_walk<512, PosteriorK20>   VGPRs 190   SGPRs 98   scratch 0 B   2 waves per SIMD
-//   LDS (dynamic, k20_preorder_lds_bytes): R x 11 520 B + 128 B -- 46 208 B at R = 4, 92 288 B at R = 8
+//   preorder_k20_walk<256, DerivativeK20<true>>    VGPRs 194   SGPRs 96   scratch 0 B   2 waves per SIMD
+//   preorder_k20_walk<512, DerivativeK20<true>>    VGPRs 192   SGPRs 96   scratch 0 B   2 waves per SIMD
+//   preorder_k20_walk<256, DerivativeK20<false>>   VGPRs 170   SGPRs 96   scratch 0 B   2 waves per SIMD
+//   preorder_k20_walk<512, DerivativeK20<false>>   VGPRs 168   SGPRs 96   scratch 0 B   3 waves per SIMD
+//   LDS (dynamic, k20_preorder_lds_bytes, every consumer): R x 11 520 B + 128 B -- 46 208 B at R = 4, 92 288 B at R = 8
 // (the four products of an operation are unrolled side by side: 100 A operands in flight)
 #include <mutex>
 
@@ -215,11 +244,14 @@ preorder_k20_walk(K20WalkArgs a, typename Consumer::Args ca) {
     unsigned bits = 0u;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      if (!op.inner[c]) continue;
+      if (!op.inner[c] && !Consumer::kTipBranches) continue;   // (wave-uniform)
       double t[5];
 #pragma unroll
       for (int i = 0; i < 5; ++i) t[i] = up[i] * pl[1 - c][i];   // the parent's vector masked by the sibling
       con.branch(ln, c, t, pl[c], l[c]);
+      if constexpr (Consumer::kTipBranches) {
+        if (!op.inner[c]) continue;   // a tip has a branch and no outer vector
+      }
       k20_product<true>(stage + (unsigned)c * kK20CopyDoubles, col, grp, t, uc[c]);
       const double m = fmax(fmax(fmax(uc[c][0], uc[c][1]), fmax(uc[c][2], uc[c][3])), uc[c][4]);
       // across the four lane groups that hold the other states of a site (bit s = site s of the wave)
@@ -262,6 +294,7 @@ struct PosteriorK20Args {
 
 struct PosteriorK20 {
   using Args = PosteriorK20Args;
+  static constexpr bool kTipBranches = false;
   const Args c;
   double *const exchange;   // [child][rate][t][lane]
   const unsigned R;
@@ -314,6 +347,104 @@ struct PosteriorK20 {
   __device__ __forceinline__ void end(const K20Lane &) const {}
 };
 
+// ---------------------------------------------------------------------------
+// Consumer: first and second derivative of lnL in every branch length
+// ---------------------------------------------------------------------------
+struct DerivativeK20Args {
+  const double *qcopy;        // [rate][400]: the MFMA-ready copy of the rate matrix of set params_indices[rate]
+  const double *rates;
+  const unsigned *pattern_w;
+  double *partials;           // [tile][nops][4]: d1, d2 of child 0, d1, d2 of child 1
+  unsigned *bad_sites;        // sites whose likelihood is 0 or not finite
+};
+
+// kSecond = false: no z2 = Q z; the d2 entries of the partials are then formed from f2 = 0 and nobody reads them
+template <bool kSecond>
+struct DerivativeK20 {
+  using Args = DerivativeK20Args;
+  static constexpr bool kTipBranches = true;
+  const Args c;
+  double *const exchange;   // k20_preorder.hpp: [rate][400] rate-matrix copies, then [parity][child][rate][3][16] terms
+  const unsigned R;
+  double w1 = 0.0, w2 = 0.0, weight = 0.0;
+  unsigned k = 0;           // the operation under way
+  bool site_bad = false;
+  __device__ __forceinline__ DerivativeK20(const Args &c, double *exchange, unsigned R) : c(c), exchange(exchange), R(R) {}
+
+  // each wave stages the copy of its own rate's matrix, once; the walk's wave barrier of the first
+  // operation stands between these writes and the first read
+  __device__ __forceinline__ void begin(const K20WalkArgs &a, const K20Lane &ln, size_t) {
+    const double rho = c.rates[ln.r];
+    w1 = ln.w * rho; w2 = w1 * rho;
+    weight = (double)c.pattern_w[ln.active ? ln.site : a.sites - 1u];
+    const double2 *src = reinterpret_cast<const double2 *>(c.qcopy + (size_t)ln.r * kK20CopyDoubles);
+    double2 *dst = reinterpret_cast<double2 *>(exchange + (size_t)ln.r * kK20CopyDoubles);
+#pragma unroll
+    for (unsigned e = 0; e < 4; ++e) {
+      const unsigned at = ln.lane + 64u * e;
+      if (at < kK20CopyDoubles / 2u) dst[at] = src[at];
+    }
+  }
+  __device__ __forceinline__ void op_begin(const K20Lane &, unsigned op) { k = op; }
+  // this rate's three terms of branch (k, ch), every site of the tile: the five states of the lane in
+  // one fixed order, then the lane groups 16 and 32 apart
+  __device__ __forceinline__ void branch(const K20Lane &ln, int ch, const double (&t)[5], const double (&y)[5],
+                                         const double (&)[5]) const {
+    const double *qc = exchange + (size_t)ln.r * kK20CopyDoubles;
+    double z[5];
+    k20_product<false>(qc, ln.col, ln.grp, y, z);
+    double p0 = ((t[0] * y[0] + t[1] * y[1]) + (t[2] * y[2] + t[3] * y[3])) + t[4] * y[4];
+    double p1 = ((t[0] * z[0] + t[1] * z[1]) + (t[2] * z[2] + t[3] * z[3])) + t[4] * z[4];
+    double p2 = 0.0;
+    if constexpr (kSecond) {
+      double z2[5];
+      k20_product<false>(qc, ln.col, ln.grp, z, z2);
+      p2 = ((t[0] * z2[0] + t[1] * z2[1]) + (t[2] * z2[2] + t[3] * z2[3])) + t[4] * z2[4];
+    }
+    p0 += __shfl_xor(p0, 16); p0 += __shfl_xor(p0, 32);
+    p1 += __shfl_xor(p1, 16); p1 += __shfl_xor(p1, 32);
+    if constexpr (kSecond) { p2 += __shfl_xor(p2, 16); p2 += __shfl_xor(p2, 32); }
+    if (ln.grp == 0u) {
+      double *f = exchange + k20_brlen_term_index(R, k & 1u, (unsigned)ch, ln.r, 0u, ln.col);
+      f[0] = ln.w * p0; f[16] = w1 * p1; f[32] = w2 * p2;
+    }
+  }
+  __device__ __forceinline__ void outer(const K20Lane &, int, unsigned, const double (&)[5], const double (&)[5]) const {}
+  // Behind the walk's barrier of operation k the terms of all rates are there.  Wave 0 adds them in
+  // rate order -- lanes 0-15 child 0, lanes 16-31 child 1, one site each --, forms the site terms,
+  // adds the 16 sites of the tile by a butterfly and writes the tile's four partials.  The other
+  // waves go on to operation k + 1 and write the OTHER parity; the parity of operation k is written
+  // again only behind the barrier of operation k + 1, which wave 0 reaches after these reads.
+  __device__ __forceinline__ void op_end(const K20WalkArgs &a, const K20Lane &ln, bool, bool) {
+    if (ln.r != 0u) return;   // (wave-uniform)
+    const unsigned ch = (ln.lane >> 4) & 1u;
+    double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+    for (unsigned r = 0; r < R; ++r) {
+      const double *f = exchange + k20_brlen_term_index(R, k & 1u, ch, r, 0u, ln.col);
+      f0 += f[0]; f1 += f[16]; f2 += f[32];
+    }
+    double d1, d2;
+    const bool ok = site_terms(f0, f1, f2, weight, &d1, &d2);
+    if (!ln.active) { d1 = 0.0; d2 = 0.0; }   // (a lane past S formed its terms from the last site's data)
+    else if (!ok && ln.lane < 32u) site_bad = true;
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+      d1 += __shfl_xor(d1, off);
+      d2 += __shfl_xor(d2, off);
+    }
+    if (ln.lane < 32u && ln.col == 0u) {
+      double *o = c.partials + ((size_t)ln.tile * a.nops + k) * 4u + 2u * ch;
+      o[0] = d1; o[1] = d2;
+    }
+  }
+  // a site is counted once, whichever of its branches found it
+  __device__ __forceinline__ void end(const K20Lane &ln) const {
+    if (ln.r != 0u) return;
+    const bool other = __shfl_xor((int)site_bad, 16) != 0;
+    if (ln.lane < 16u && (site_bad || other)) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
 // state[row] = the smallest index among the largest of post[row][0..K), prob[row] = that posterior.
 // A workgroup's 256 rows come through LDS: the loads are contiguous over the workgroup (a lane
 // reading its own row would stride 8 K bytes from its neighbour: measured 0.66 ms for c3's 318 MB),
@@ -346,9 +477,10 @@ ancestral_argmax_kernel(const double *__restrict__ post, size_t rows, unsigned K
 
 }  // namespace
 
-hipError_t launch_outer_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
-                                    double *d_work, double *d_post) {
-  if (nops == 0 || p->sites == 0) return hipSuccess;
+// the walk of one consumer over the whole program, one workgroup per tile
+template <class Consumer>
+static hipError_t launch_k20_walk(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx, double *d_work,
+                           const typename Consumer::Args &ca) {
   const unsigned R = p->rate_cats;
   if (!p->mfma_layout || R > kK20MaxRates) return hipErrorInvalidValue;
   K20WalkArgs a;
@@ -358,26 +490,42 @@ hipError_t launch_outer_program_k20(rdamd_partition *p, const OuterOp *d_prog, u
   a.pmfma = p->d_pmat_mfma; a.freqs = p->d_freqs; a.fidx = d_fidx; a.rate_w = p->d_rate_weights;
   a.tips = p->tips; a.sites = p->sites; a.tiles = p->clv_tiles(); a.R = R;
   a.work = d_work; a.prog = d_prog; a.nops = nops;
-  const PosteriorK20Args ca{d_post};
   const size_t lds = k20_preorder_lds_bytes(R);
   if (R <= 4) {
-    preorder_k20_walk<256, PosteriorK20><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+    preorder_k20_walk<256, Consumer><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
   } else {
     {   // six categories and up pass the 64 KB a kernel may ask for by default
       static std::mutex lds_mu;
-      static bool lds_allowed = false;
+      static bool lds_allowed = false;   // (one per consumer)
       std::lock_guard<std::mutex> guard(lds_mu);
       if (!lds_allowed) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&preorder_k20_walk<512, PosteriorK20>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&preorder_k20_walk<512, Consumer>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)k20_preorder_lds_bytes(kK20MaxRates));
         if (e != hipSuccess) return e;
         lds_allowed = true;
       }
     }
-    preorder_k20_walk<512, PosteriorK20><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+    preorder_k20_walk<512, Consumer><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
   }
   return hipGetLastError();
+}
+
+hipError_t launch_outer_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                    double *d_work, double *d_post) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  return launch_k20_walk<PosteriorK20>(p, d_prog, nops, d_fidx, d_work, PosteriorK20Args{d_post});
+}
+
+hipError_t launch_brlen_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                    double *d_work, const double *d_qcopy, double *d_partials, unsigned *d_bad_sites,
+                                    bool second, double *d_out) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  const DerivativeK20Args ca{d_qcopy, p->d_rates, p->d_pattern_weights, d_partials, d_bad_sites};
+  const hipError_t e = second ? launch_k20_walk<DerivativeK20<true>>(p, d_prog, nops, d_fidx, d_work, ca)
+                              : launch_k20_walk<DerivativeK20<false>>(p, d_prog, nops, d_fidx, d_work, ca);
+  if (e != hipSuccess) return e;
+  return launch_brlen_sum(p, d_partials, p->clv_tiles(), nops * 4u, d_out);
 }
 
 hipError_t launch_ancestral_argmax(rdamd_partition *p, const double *d_post, size_t rows, unsigned K, uint8_t *d_state,

@@ -598,7 +598,7 @@ void model_t::ancestral_sequences(const root_location_t &rl, const std::vector<p
 
 // Branch-length derivatives at one root, and (bounds given) the lengths that maximise lnL there.
 // One evaluation at lengths x: update_pmatrices on the schedule's matrix indices with x, a
-// materialising traversal, the root lnL, and rdamd_branch_derivatives per partition, summed in
+// materialising traversal, the root lnL, and rdamd_branch_length_derivatives per partition, summed in
 // partition order.  Saves and restores what ancestral does.
 model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                                                   const branch_bounds_t *bounds) {
@@ -649,8 +649,8 @@ model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, con
         lh += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
                                                _param_indicies[p].data(), nullptr);
         if (rdamd_errno()) fail("compute_root_loglikelihood");
-        if (rdamd_branch_derivatives(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
-                                     part_d1.data(), part_d2.data()) != RDAMD_SUCCESS)
+        if (rdamd_branch_length_derivatives(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
+                                            part_d1.data(), part_d2.data()) != RDAMD_SUCCESS)
           throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
         for (size_t b = 0; b < at.size(); ++b) { g[b] += part_d1[b]; h[b] += part_d2[b]; }
       }

@@ -13,6 +13,7 @@
 #include "clades.hpp"
 #include "clv_plan.hpp"
 #include "common.hpp"
+#include "k20_preorder.hpp"
 #include "outer_plan.hpp"
 #include "subst_map.hpp"
 #include "tip_encode.hpp"
@@ -450,9 +451,10 @@ static bool outer_refused(const rdamd_partition *p, const char *what) {
   return false;
 }
 
-// ... and the shapes rdamd_ancestral_sequences does not take: it walks 4-state, binary and matrix-core
-// 20-state partitions
-static bool sequences_refused(const rdamd_partition *p, const char *what) {
+// ... and the shapes rdamd_ancestral_sequences and rdamd_branch_length_derivatives do not take: they
+// walk 4-state, binary and matrix-core 20-state partitions (`result`: what the entry point computes,
+// for the message)
+static bool walks_refused(const rdamd_partition *p, const char *what, const char *result) {
   if (p->sparse) {
     set_error(63, "%s: partitions with RDAMD_ATTRIB_SPARSE_CLVS are not supported (the pass reads every inner CLV of a "
                   "materialising traversal)", what);
@@ -463,9 +465,13 @@ static bool sequences_refused(const rdamd_partition *p, const char *what) {
     set_error(63, "%s: 20-state partitions with %u rate categories are not supported (the matrix-core layout the walk "
                   "reads holds up to 8 categories and CLVs under 2 GB)", what, p->rate_cats);
   else
-    set_error(63, "%s: %u-state partitions are not supported (ancestral sequences are computed for 2, 4 and 20 states)",
-              what, p->api_states);
+    set_error(63, "%s: %u-state partitions are not supported (%s are computed for 2, 4 and 20 states)", what, p->api_states,
+              result);
   return true;
+}
+static bool sequences_refused(const rdamd_partition *p, const char *what) { return walks_refused(p, what, "ancestral sequences"); }
+static bool derivatives_refused(const rdamd_partition *p, const char *what) {
+  return walks_refused(p, what, "branch-length derivatives");
 }
 
 // What the entry points of the pre-order pass share, in two steps: preorder_admitted, then
@@ -1255,30 +1261,52 @@ unsigned int rdamd_marginal_ancestral_workspace_slots(const rdamd_operation_t *o
 
 double rdamd_branch_last_ms(void) { return g_branch_ms; }
 
-int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
-                             const unsigned int *params_indices, const unsigned int *freqs_indices,
-                             double *d1_out, double *d2_out) {
+// rdamd_branch_derivatives and rdamd_branch_length_derivatives: one body, the entry point's name
+// (`what`) and the shapes it refuses (`refused`) apart.  A matrix-core 20-state partition, which only
+// the second admits, runs kernels_preorder_k20.hip's consumer; every other shape the launch it always ran.
+static int branch_derivatives_call(rdamd_partition_t *p, const char *what, bool (*refused)(const rdamd_partition *, const char *),
+                                   const rdamd_operation_t *ops, unsigned int n_ops, const unsigned int *params_indices,
+                                   const unsigned int *freqs_indices, double *d1_out, double *d2_out) {
   clear_error();
   g_branch_ms = 0.0;
   const std::initializer_list<RateIndices> indices = {{params_indices, "params"}, {freqs_indices, "freqs"}};
   OuterPlan plan;
-  if (!preorder_admitted(p, "rdamd_branch_derivatives", ops, n_ops, !ops || !params_indices || !freqs_indices || !d1_out,
-                         indices, &plan))
+  if (!preorder_admitted(p, what, ops, n_ops, !ops || !params_indices || !freqs_indices || !d1_out, indices, &plan, refused))
     return RDAMD_FAILURE;
   const size_t entries = (size_t)n_ops * 4;
   std::fill(d1_out, d1_out + 2 * (size_t)n_ops, 0.0);
   if (d2_out) std::fill(d2_out, d2_out + 2 * (size_t)n_ops, 0.0);
   if (p->sites == 0) return RDAMD_SUCCESS;
+  const bool k20 = p->mfma_layout;
   DeviceArray<double> partials, sums;   // [workgroup][entry] and [entry]
   DeviceArray<unsigned> bad_sites;      // the count of sites without a likelihood
+  // 20 states: the MFMA-ready copy of the rate matrix of every category, from the rate matrices as flush_q builds them
+  DeviceArray<double> qcopy;
+  std::vector<double> h_qcopy;
+  if (k20) {
+    const unsigned R = p->rate_cats, K = p->states;
+    std::vector<double> q((size_t)K * K);
+    h_qcopy.resize((size_t)R * kK20CopyDoubles);
+    for (unsigned r = 0; r < R; ++r) {
+      const unsigned m = params_indices[r];
+      build_q_host(K, p->subst[m].data(), p->freqs[m].data(), q.data());
+      k20_pack_copy(q.data(), h_qcopy.data() + (size_t)r * kK20CopyDoubles);
+    }
+  }
   const auto allocate = [&] {
-    hipError_t e = partials.alloc(entries * preorder_blocks(p));
+    hipError_t e = partials.alloc(entries * (k20 ? p->clv_tiles() : preorder_blocks(p)));
     if (e == hipSuccess) e = sums.alloc(entries);
     if (e == hipSuccess) e = bad_sites.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(bad_sites.d, 0, sizeof(unsigned), p->stream);
+    if (e == hipSuccess && k20) e = qcopy.alloc(h_qcopy.size());
+    if (e == hipSuccess && k20) e = hipMemcpy(qcopy.d, h_qcopy.data(), sizeof(double) * h_qcopy.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && k20) e = flush_tiptab(p);
     return e;
   };
   const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    if (k20)
+      return launch_brlen_program_k20(p, d_prog, n_ops, d_indices[1], d_work, qcopy.d, partials.d, bad_sites.d,
+                                      d2_out != nullptr, sums.d);
     return launch_brlen_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_indices[1], d_work, partials.d, bad_sites.d,
                                 sums.d);
   };
@@ -1287,8 +1315,8 @@ int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops,
   RDAMD_HIP_TRY(hipMemcpy(&bad, bad_sites.d, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   if (bad) {
     g_branch_ms = 0.0;   // (a call that returns nothing reports no time)
-    set_error(65, "rdamd_branch_derivatives: %u of %u sites have a likelihood that is 0 or not finite; no derivative "
-                  "is returned", bad, p->sites);
+    set_error(65, "%s: %u of %u sites have a likelihood that is 0 or not finite; no derivative is returned", what, bad,
+              p->sites);
     return RDAMD_FAILURE;
   }
   std::vector<double> host(entries);
@@ -1299,6 +1327,20 @@ int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops,
       if (d2_out) d2_out[2 * k + c] = host[4 * k + 2 * c + 1];
     }
   return RDAMD_SUCCESS;
+}
+
+int rdamd_branch_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                             const unsigned int *params_indices, const unsigned int *freqs_indices,
+                             double *d1_out, double *d2_out) {
+  return branch_derivatives_call(p, "rdamd_branch_derivatives", outer_refused, ops, n_ops, params_indices, freqs_indices,
+                                 d1_out, d2_out);
+}
+
+int rdamd_branch_length_derivatives(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                                    const unsigned int *params_indices, const unsigned int *freqs_indices,
+                                    double *d1_out, double *d2_out) {
+  return branch_derivatives_call(p, "rdamd_branch_length_derivatives", derivatives_refused, ops, n_ops, params_indices,
+                                 freqs_indices, d1_out, d2_out);
 }
 
 static thread_local double g_pair_sums_ms = 0.0;
