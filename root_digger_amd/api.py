@@ -1083,6 +1083,36 @@ def _flatten_params(params):
     return counts, np.ascontiguousarray(values if values.size else np.zeros(1))
 
 
+def _one_root_params(params):
+    """_flatten_params of one root's per-partition dicts; (None, None) for None"""
+    return _flatten_params(list(params)) if params is not None else (None, None)
+
+
+def _param_args(counts, values):
+    """the (counts, values) argument pair of the rdamd_model_* analyses; both null when not given"""
+    return (counts.ctypes.data_as(_pu64) if counts is not None else None,
+            _dptr(values) if values is not None else None)
+
+
+class _NodeArrays:
+    """The node arrays the rdamd_model_* analyses fill: n inner nodes in pre-order."""
+
+    def __init__(self, n):
+        self.n, self.count = n, C.c_uint(0)
+        self.clv = np.zeros(n, dtype=np.uint32)
+        self.parent = np.zeros(n, dtype=np.int32)
+        self.children = np.zeros((n, 2), dtype=np.uint32)
+
+    def args(self):
+        """the arguments n_nodes, node_clv, node_parent, node_children"""
+        return C.byref(self.count), _uptr(self.clv), self.parent.ctypes.data_as(_pi), _uptr(self.children)
+
+    def arrays(self):
+        """after the call: (node_clv, node_parent, node_children)"""
+        assert self.count.value == self.n
+        return self.clv, self.parent, self.children
+
+
 PARAM_TYPES = ("emperical", "estimate", "equal", "user")          # src/util.hpp:37
 RATE_CATEGORIES = ("MEDIAN", "MEAN", "FREE")                       # :48
 ASC_TYPES = ("lewis", "fels", "stam")                              # :72
@@ -1725,10 +1755,7 @@ class Model:
             if len(params) != n:
                 raise ValueError("one parameter set per root is required")
             counts, values = _flatten_params([pp for per_root in params for pp in per_root])
-        self._ok(lib.rdamd_model_site_lnls(self._h, n, arr,
-                                           counts.ctypes.data_as(_pu64) if counts is not None else None,
-                                           _dptr(values) if values is not None else None, _dptr(out)),
-                 "site_lnls")
+        self._ok(lib.rdamd_model_site_lnls(self._h, n, arr, *_param_args(counts, values), _dptr(out)), "site_lnls")
         return out
 
     def partition_shape(self, p):
@@ -1737,6 +1764,16 @@ class Model:
         self._ok(lib.rdamd_model_partition_shape(self._h, p, C.byref(a), C.byref(b), C.byref(c)), "partition_shape")
         return a.value, b.value, c.value
 
+    def _shapes(self):
+        """partition_shape of every partition, looked up once (a model's partitions do not change)"""
+        if getattr(self, "_shape_cache", None) is None:
+            self._shape_cache = [self.partition_shape(p) for p in range(self.partition_count())]
+        return self._shape_cache
+
+    def _total(self):
+        """patterns of all partitions together"""
+        return sum(sh[0] for sh in self._shapes())
+
     def ancestral(self, rl, params=None):
         """Marginal ancestral states and site rates at root rl (rdamd_model_ancestral) ->
         (node_clv[n], node_parent[n], node_children[n][2], post[n][P_total][states],
@@ -1744,25 +1781,15 @@ class Model:
         concatenated.  cat: [P_total][R], or -- partitions with different category counts -- the list of
         the partitions' [patterns][R] arrays.  params: the per-partition dicts Checkpoint.read_results
         returns for one root; None: the model's current parameters."""
-        shapes = [self.partition_shape(p) for p in range(self.partition_count())]
-        total = sum(sh[0] for sh in shapes)
-        n = self._tree.tip_count() - 1
-        clv = np.zeros(n, dtype=np.uint32)
-        parent = np.zeros(n, dtype=np.int32)
-        children = np.zeros((n, 2), dtype=np.uint32)
-        post = np.zeros((n, total, self.states), dtype=np.float64)
+        shapes, total = self._shapes(), self._total()
+        nodes = _NodeArrays(self._tree.tip_count() - 1)
+        post = np.zeros((nodes.n, total, self.states), dtype=np.float64)
         cat = np.zeros(max(1, sum(sh[0] * sh[2] for sh in shapes)), dtype=np.float64)
         mean = np.zeros(total, dtype=np.float64)
-        counts = values = None
-        if params is not None:
-            counts, values = _flatten_params(list(params))
-        nn = C.c_uint(0)
-        self._ok(lib.rdamd_model_ancestral(self._h, C.byref(rl),
-                                           counts.ctypes.data_as(_pu64) if counts is not None else None,
-                                           _dptr(values) if values is not None else None, C.byref(nn), _uptr(clv),
-                                           parent.ctypes.data_as(_pi), _uptr(children), _dptr(post), _dptr(cat),
-                                           _dptr(mean)), "ancestral")
-        assert nn.value == n
+        counts, values = _one_root_params(params)
+        self._ok(lib.rdamd_model_ancestral(self._h, C.byref(rl), *_param_args(counts, values), *nodes.args(), _dptr(post),
+                                           _dptr(cat), _dptr(mean)), "ancestral")
+        clv, parent, children = nodes.arrays()
         if len({sh[2] for sh in shapes}) == 1:
             cat = cat[:total * shapes[0][2]].reshape(total, shapes[0][2])
         else:
@@ -1775,49 +1802,30 @@ class Model:
         node_parent[n], node_children[n][2], state uint8 [n][P_total], prob[n][P_total]), plus
         post[n][P_total][states] with posteriors=True; nodes as ancestral_nodes orders them, patterns of
         all partitions concatenated.  DNA, binary and protein models; params as ancestral takes them."""
-        total = sum(self.partition_shape(p)[0] for p in range(self.partition_count()))
-        n = self._tree.tip_count() - 1
-        clv = np.zeros(n, dtype=np.uint32)
-        parent = np.zeros(n, dtype=np.int32)
-        children = np.zeros((n, 2), dtype=np.uint32)
-        state = np.zeros((n, total), dtype=np.uint8)
-        prob = np.zeros((n, total), dtype=np.float64)
-        post = np.zeros((n, total, self.states), dtype=np.float64) if posteriors else None
-        counts = values = None
-        if params is not None:
-            counts, values = _flatten_params(list(params))
-        nn = C.c_uint(0)
-        self._ok(lib.rdamd_model_ancestral_sequences(self._h, C.byref(rl),
-                                                     counts.ctypes.data_as(_pu64) if counts is not None else None,
-                                                     _dptr(values) if values is not None else None, C.byref(nn),
-                                                     _uptr(clv), parent.ctypes.data_as(_pi), _uptr(children),
+        total = self._total()
+        nodes = _NodeArrays(self._tree.tip_count() - 1)
+        state = np.zeros((nodes.n, total), dtype=np.uint8)
+        prob = np.zeros((nodes.n, total), dtype=np.float64)
+        post = np.zeros((nodes.n, total, self.states), dtype=np.float64) if posteriors else None
+        counts, values = _one_root_params(params)
+        self._ok(lib.rdamd_model_ancestral_sequences(self._h, C.byref(rl), *_param_args(counts, values), *nodes.args(),
                                                      state.ctypes.data_as(C.POINTER(C.c_ubyte)), _dptr(prob),
                                                      _dptr(post) if posteriors else None), "ancestral_sequences")
-        assert nn.value == n
-        return (clv, parent, children, state, prob) + ((post,) if posteriors else ())
+        return nodes.arrays() + (state, prob) + ((post,) if posteriors else ())
 
     def branch_derivatives(self, rl, params=None):
         """Derivatives of lnL in every branch length at root rl (rdamd_model_branch_derivatives) ->
         (node_clv[n], node_parent[n], node_children[n][2], lengths[n][2], d1[n][2], d2[n][2], lnl):
         nodes as ancestral_nodes orders them, branch (k, c) above child c of node k, summed over the
         partitions.  params as Model.ancestral takes them."""
-        n = self._tree.tip_count() - 1
-        clv = np.zeros(n, dtype=np.uint32)
-        parent = np.zeros(n, dtype=np.int32)
-        children = np.zeros((n, 2), dtype=np.uint32)
-        lengths, d1, d2 = (np.zeros((n, 2), dtype=np.float64) for _ in range(3))
-        counts = values = None
-        if params is not None:
-            counts, values = _flatten_params(list(params))
-        nn, lnl = C.c_uint(0), C.c_double(0.0)
-        self._ok(lib.rdamd_model_branch_derivatives(self._h, C.byref(rl),
-                                                    counts.ctypes.data_as(_pu64) if counts is not None else None,
-                                                    _dptr(values) if values is not None else None, C.byref(nn),
-                                                    _uptr(clv), parent.ctypes.data_as(_pi), _uptr(children),
+        nodes = _NodeArrays(self._tree.tip_count() - 1)
+        lengths, d1, d2 = (np.zeros((nodes.n, 2), dtype=np.float64) for _ in range(3))
+        counts, values = _one_root_params(params)
+        lnl = C.c_double(0.0)
+        self._ok(lib.rdamd_model_branch_derivatives(self._h, C.byref(rl), *_param_args(counts, values), *nodes.args(),
                                                     _dptr(lengths), _dptr(d1), _dptr(d2), C.byref(lnl)),
                  "branch_derivatives")
-        assert nn.value == n
-        return clv, parent, children, lengths, d1, d2, lnl.value
+        return nodes.arrays() + (lengths, d1, d2, lnl.value)
 
     def gradient(self, rl, params):
         """The exact gradient of lnL at root rl (rdamd_model_gradient) -> (grad, lnl).  params: the
@@ -1825,12 +1833,11 @@ class Model:
         the optimiser's variables -- substitution rates, unnormalised frequencies, alpha, a FREE
         partition's unnormalised weights --, which the model does not keep); grad: a list of dicts of
         the same keys and shapes.  Nothing is applied to the model."""
-        params = list(params)
-        counts, values = _flatten_params(params)
+        counts, values = _flatten_params(list(params))
         grad = np.zeros_like(values)
         lnl = C.c_double(0.0)
-        self._ok(lib.rdamd_model_gradient(self._h, C.byref(rl), counts.ctypes.data_as(_pu64), _dptr(values), _dptr(grad),
-                                          C.byref(lnl)), "gradient")
+        self._ok(lib.rdamd_model_gradient(self._h, C.byref(rl), *_param_args(counts, values), _dptr(grad), C.byref(lnl)),
+                 "gradient")
         out, at = [], 0
         for row in np.asarray(counts).reshape(-1, 4):
             d = {}
@@ -1848,23 +1855,21 @@ class Model:
         lnl.  params: the per-partition dicts Checkpoint.read_results returns for one root (required).
         Nothing is applied to the model."""
         counts, values = _flatten_params(list(params))
-        n = self._tree.tip_count() - 1
-        total = sum(self.partition_shape(p)[0] for p in range(self.partition_count()))
+        nodes, total = _NodeArrays(self._tree.tip_count() - 1), self._total()
+        n = nodes.n
         ks = [int(round((1 + (1 + 4 * int(c)) ** 0.5) / 2)) for c in np.asarray(counts).reshape(-1, 4)[:, 0]]
-        out = {"node_clv": np.zeros(n, dtype=np.uint32), "node_parent": np.zeros(n, dtype=np.int32),
-               "node_children": np.zeros((n, 2), dtype=np.uint32), "lengths": np.zeros((n, 2))}
+        out = {"node_clv": nodes.clv, "node_parent": nodes.parent, "node_children": nodes.children,
+               "lengths": np.zeros((n, 2))}
         typed = np.zeros(max(1, sum(n * 2 * k * k for k in ks)))
         for key in ("change", "count", "top_prob"):
             out[key] = np.zeros((n, 2, total))
         out["top_pair"] = np.zeros((n, 2, total), dtype=np.uint8)
-        nn, lnl = C.c_uint(0), C.c_double(0.0)
-        self._ok(lib.rdamd_model_substitutions(self._h, C.byref(rl), counts.ctypes.data_as(_pu64), _dptr(values), C.byref(nn),
-                                               _uptr(out["node_clv"]), out["node_parent"].ctypes.data_as(_pi),
-                                               _uptr(out["node_children"]), _dptr(out["lengths"]), _dptr(typed),
-                                               _dptr(out["change"]), _dptr(out["count"]),
-                                               out["top_pair"].ctypes.data_as(_pub), _dptr(out["top_prob"]), C.byref(lnl)),
-                 "substitutions")
-        assert nn.value == n
+        lnl = C.c_double(0.0)
+        self._ok(lib.rdamd_model_substitutions(self._h, C.byref(rl), *_param_args(counts, values), *nodes.args(),
+                                               _dptr(out["lengths"]), _dptr(typed), _dptr(out["change"]),
+                                               _dptr(out["count"]), out["top_pair"].ctypes.data_as(_pub),
+                                               _dptr(out["top_prob"]), C.byref(lnl)), "substitutions")
+        nodes.arrays()
         cuts = np.cumsum([0] + [n * 2 * k * k for k in ks])
         out["typed"] = [typed[cuts[i]:cuts[i + 1]].reshape(n, 2, k, k).copy() for i, k in enumerate(ks)]
         out["lnl"] = lnl.value
@@ -1876,14 +1881,11 @@ class Model:
         lnl_before, lnl_after, iterations, evaluations, converged.  Nothing is applied to the model."""
         n = self._tree.tip_count() - 1
         lengths, d1, d2 = (np.zeros((n, 2), dtype=np.float64) for _ in range(3))
-        counts = values = None
-        if params is not None:
-            counts, values = _flatten_params(list(params))
+        counts, values = _one_root_params(params)
         before, after = C.c_double(0.0), C.c_double(0.0)
         its, evals, conv = C.c_uint(0), C.c_uint(0), C.c_int(0)
         self._ok(lib.rdamd_model_optimize_branch_lengths(
-            self._h, C.byref(rl), counts.ctypes.data_as(_pu64) if counts is not None else None,
-            _dptr(values) if values is not None else None, min_len, max_len, atol, max_iters, _dptr(lengths),
+            self._h, C.byref(rl), *_param_args(counts, values), min_len, max_len, atol, max_iters, _dptr(lengths),
             _dptr(d1), _dptr(d2), C.byref(before), C.byref(after), C.byref(its), C.byref(evals), C.byref(conv)),
             "optimize_branch_lengths")
         return {"lengths": lengths, "d1": d1, "d2": d2, "lnl_before": before.value, "lnl_after": after.value,

@@ -8,12 +8,12 @@
 #include "brlen_opt.hpp"
 #include "checkpoint.hpp"
 #include "lockstep.hpp"
+#include "root_frame.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <limits>
 #include <numeric>
-#include <unordered_map>
 
 namespace rdamd {
 
@@ -377,7 +377,7 @@ size_t model_t::pattern_count() const {
   return n;
 }
 
-// What site_lnls and ancestral change for the duration of a call and put back: the partitions'
+// What the analyses at a root change for the duration of a call and put back: the partitions'
 // parameters, the rooting, and (by one compute_lh) the conditional likelihoods of that rooting.
 struct model_t::saved_parameters_t {
   struct part_t { std::vector<double> subst, freqs, rates, rate_weights; };
@@ -413,7 +413,9 @@ struct model_t::saved_parameters_t {
   }
 };
 
-// The analyses at a root (site_lnls, ancestral, branch_lengths) need every column on this rank.
+// The analyses at a root (model.hpp) need every column on this rank.
+static const char *const kNoPerSiteOutput = "per-site output of a site-sharded model is not supported";
+static const char *const kNoDerivatives = "derivatives of a site-sharded model are not supported";
 void model_t::refuse_site_group(const char *who, const char *unsupported) const {
   if (site_sharded() || (_lockstep && _lockstep->sums_over_site_group()))
     throw std::invalid_argument(std::string(who) + ": this model sums over a site group and holds one block of the "
@@ -453,12 +455,74 @@ void model_t::with_saved_parameters(bool rooting_back_on_failure, Restore restor
   saved.restore_rooting(*this);
 }
 
+// What an analysis at one root starts from: compute_lh's schedule there and its frame.
+struct model_t::at_root_t {
+  const std::vector<rdamd_operation_t> &ops;
+  const std::vector<unsigned> &pmi;   // the schedule's matrix list
+  const std::vector<double> &brl;     // ... and its lengths
+  RootFrame frame;
+};
+
+// One analysis at root rl, for `who`: the refusals (check: the analysis's own, after the common
+// ones), then, under with_saved_parameters, the parameters, the schedule and its frame (nodes: with
+// the node arrays), handed to body.
+template <class Check, class Body>
+void model_t::at_root(const root_location_t &rl, const std::vector<partition_parameters_t> *params, const char *who,
+                      const char *unsupported, bool nodes, Check check, Body body) {
+  refuse_site_group(who, unsupported);
+  if (params) require_fit(*params, who, "");
+  check();
+  with_saved_parameters(true, [] {}, [&] {
+    if (params) set_model_params(*params);
+    auto sched = _tree.generate_operations(rl);
+    at_root_t at{std::get<0>(sched), std::get<1>(sched), std::get<2>(sched),
+                 root_frame(std::get<0>(sched), std::get<1>(sched), std::get<2>(sched), nodes)};
+    if (at.frame.bad_op >= 0)
+      throw std::runtime_error("marginal_ancestral_nodes: rdamd_marginal_ancestral_nodes: operation " +
+                               std::to_string(at.frame.bad_op) + ": " + at.frame.why);
+    body(at);
+  });
+}
+
+// One evaluation of a schedule: its matrices at `lengths`, then per partition the traversal, the
+// root lnL where wanted (returned, summed in partition order) and each(p, at), `at` the partition's
+// first pattern in the concatenated list; what each refuses (not RDAMD_SUCCESS) is thrown.
+template <class Each>
+double model_t::evaluate_partitions(const std::vector<rdamd_operation_t> &ops, const std::vector<unsigned> &pmi,
+                                    const std::vector<double> &lengths, bool root_lnl, Each each) {
+  update_pmatrices(pmi, lengths);
+  ++_n_full;
+  double lh = 0.0;
+  size_t at = 0;
+  for (size_t p = 0; p < _partitions.size(); ++p) {
+    rdamd_update_clvs(_partitions[p], ops.data(), (unsigned)ops.size());
+    if (rdamd_errno()) fail("update_clvs");
+    if (root_lnl) {
+      lh += rdamd_compute_root_loglikelihood(_partitions[p], _tree.root_clv_index(), _tree.root_scaler_index(),
+                                             _param_indicies[p].data(), nullptr);
+      if (rdamd_errno()) fail("compute_root_loglikelihood");
+    }
+    if (each(p, at) != RDAMD_SUCCESS) throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+    at += rdamd_partition_sites(_partitions[p]);
+  }
+  return lh;
+}
+
+// x / sum x, as set_model_params applies frequencies and free weights
+static model_params_t normalised(model_params_t x, double *sum = nullptr) {
+  double s = 0.0;
+  for (double f : x) s += f;
+  for (double &f : x) f /= s;
+  if (sum) *sum = s;
+  return x;
+}
+
 // The path compute_lh takes, with the root kernel's per-site output switched on.  That output is
 // weight x lnL; the partitions carry unit weights for the duration of the call (exact, and a
 // pattern of weight 0 keeps its lnL), so the rows are unweighted.
 void model_t::site_lnls(const std::vector<root_location_t> &rls,
                         const std::vector<std::vector<partition_parameters_t>> *params, double *out) {
-  refuse_site_group("site_lnls", "per-site output of a site-sharded model is not supported");
+  refuse_site_group("site_lnls", kNoPerSiteOutput);
   if (params && params->size() != rls.size())
     throw std::invalid_argument("site_lnls: one parameter set per root is required");
   const size_t P = _partitions.size(), total = pattern_count();
@@ -480,188 +544,120 @@ void model_t::site_lnls(const std::vector<root_location_t> &rls,
         set_model_params((*params)[i]);
       }
       auto sched = _tree.generate_operations(rls[i]);
-      const auto &ops = std::get<0>(sched);
-      update_pmatrices(std::get<1>(sched), std::get<2>(sched));
-      ++_n_full;
-      double *row = out + i * total;
-      for (size_t p = 0; p < P; ++p) {
-        rdamd_update_clvs(_partitions[p], ops.data(), (unsigned)ops.size());
-        if (rdamd_errno()) fail("update_clvs");
-        if (rdamd_partition_sites(_partitions[p]) == 0) continue;
+      evaluate_partitions(std::get<0>(sched), std::get<1>(sched), std::get<2>(sched), false, [&](size_t p, size_t at) {
+        if (rdamd_partition_sites(_partitions[p]) == 0) return RDAMD_SUCCESS;
         rdamd_compute_root_loglikelihood(_partitions[p], _tree.root_clv_index(), _tree.root_scaler_index(),
-                                         _param_indicies[p].data(), row);
+                                         _param_indicies[p].data(), out + i * total + at);
         if (rdamd_errno()) fail("compute_root_loglikelihood");
-        row += rdamd_partition_sites(_partitions[p]);
-      }
+        return RDAMD_SUCCESS;
+      });
     }
   });
+}
+
+static void copy_nodes(const RootFrame &f, model_t::nodes_t *out) {
+  if (!out) return;
+  out->node_clv = f.node_clv;
+  out->node_parent = f.node_parent;
+  out->node_children = f.node_children;
 }
 
 // Marginal ancestral states and site rates at one root: compute_lh's traversal, then the pre-order
 // pass and the site-rate kernel per partition (rdamd_marginal_ancestral, rdamd_site_rate_posteriors).
-// Saves and restores what site_lnls does.
-void model_t::ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
-                        std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
-                        std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate) {
-  refuse_site_group("ancestral", "per-site output of a site-sharded model is not supported");
-  const size_t P = _partitions.size(), total = pattern_count();
-  if (params) require_fit(*params, "ancestral", "");
-  with_saved_parameters(true, [] {}, [&] {
-    if (params) set_model_params(*params);
-    auto sched = _tree.generate_operations(rl);
-    const auto &ops = std::get<0>(sched);
-    const unsigned n_ops = (unsigned)ops.size();
-    if (node_clv) node_clv->resize(n_ops);
-    if (node_parent) node_parent->resize(n_ops);
-    if (node_children) node_children->resize(2 * (size_t)n_ops);
-    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, node_clv ? node_clv->data() : nullptr,
-                                       node_parent ? node_parent->data() : nullptr,
-                                       node_children ? node_children->data() : nullptr) != RDAMD_SUCCESS)
-      fail("marginal_ancestral_nodes");
-    update_pmatrices(std::get<1>(sched), std::get<2>(sched));
-    ++_n_full;
-    size_t at = 0;   // first pattern of the partition in the concatenated list
+void model_t::ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params, nodes_t *nodes,
+                        double *post, double *cat, double *mean_rate) {
+  at_root(rl, params, "ancestral", kNoPerSiteOutput, true, [] {}, [&](const at_root_t &r) {
+    copy_nodes(r.frame, nodes);
+    const size_t total = pattern_count();
+    const unsigned n_ops = (unsigned)r.ops.size();
     std::vector<double> part_post;
-    for (size_t p = 0; p < P; ++p) {
+    evaluate_partitions(r.ops, r.pmi, r.brl, false, [&](size_t p, size_t at) {
       rdamd_partition_t *part = _partitions[p];
       const size_t sites = rdamd_partition_sites(part), K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part);
-      rdamd_update_clvs(part, ops.data(), n_ops);
-      if (rdamd_errno()) fail("update_clvs");
       if (post) {
         part_post.resize((size_t)n_ops * sites * K);
-        if (rdamd_marginal_ancestral(part, ops.data(), n_ops, _param_indicies[p].data(), part_post.data()) != RDAMD_SUCCESS)
-          throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
-        for (size_t k = 0; k < n_ops; ++k)
-          std::copy(part_post.begin() + k * sites * K, part_post.begin() + (k + 1) * sites * K, post + (k * total + at) * K);
+        if (rdamd_marginal_ancestral(part, r.ops.data(), n_ops, _param_indicies[p].data(), part_post.data()) != RDAMD_SUCCESS)
+          return RDAMD_FAILURE;
+        scatter_columns(part_post.data(), n_ops, sites, K, total, at, post);
       }
       if ((cat || mean_rate) &&
           rdamd_site_rate_posteriors(part, _tree.root_clv_index(), _tree.root_scaler_index(), _param_indicies[p].data(),
                                      cat, mean_rate ? mean_rate + at : nullptr) != RDAMD_SUCCESS)
-        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+        return RDAMD_FAILURE;
       if (cat) cat += sites * R;
-      at += sites;
-    }
+      return RDAMD_SUCCESS;
+    });
   });
 }
 
 // Ancestral sequences at one root: ancestral's traversal, then rdamd_ancestral_sequences per
-// partition, the partitions' columns side by side in every node's row.  Saves and restores what
-// ancestral does.
+// partition, the partitions' columns side by side in every node's row.
 void model_t::ancestral_sequences(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
-                                  std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
-                                  std::vector<unsigned> *node_children, uint8_t *state, double *prob, double *post) {
-  refuse_site_group("ancestral_sequences", "per-site output of a site-sharded model is not supported");
-  const size_t P = _partitions.size(), total = pattern_count();
-  if (params) require_fit(*params, "ancestral_sequences", "");
-  for (size_t p = 1; p < P; ++p)
-    if (rdamd_partition_states(_partitions[p]) != rdamd_partition_states(_partitions[0]))
-      throw std::invalid_argument("ancestral_sequences: partitions " + std::to_string(p) + " and 0 have different state "
-                                  "counts; the outputs have one");
-  with_saved_parameters(true, [] {}, [&] {
-    if (params) set_model_params(*params);
-    auto sched = _tree.generate_operations(rl);
-    const auto &ops = std::get<0>(sched);
-    const unsigned n_ops = (unsigned)ops.size();
-    if (node_clv) node_clv->resize(n_ops);
-    if (node_parent) node_parent->resize(n_ops);
-    if (node_children) node_children->resize(2 * (size_t)n_ops);
-    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, node_clv ? node_clv->data() : nullptr,
-                                       node_parent ? node_parent->data() : nullptr,
-                                       node_children ? node_children->data() : nullptr) != RDAMD_SUCCESS)
-      fail("marginal_ancestral_nodes");
-    update_pmatrices(std::get<1>(sched), std::get<2>(sched));
-    ++_n_full;
-    size_t at = 0;   // first pattern of the partition in the concatenated list
+                                  nodes_t *nodes, uint8_t *state, double *prob, double *post) {
+  const auto one_state_count = [&] {
+    for (size_t p = 1; p < _partitions.size(); ++p)
+      if (rdamd_partition_states(_partitions[p]) != rdamd_partition_states(_partitions[0]))
+        throw std::invalid_argument("ancestral_sequences: partitions " + std::to_string(p) + " and 0 have different state "
+                                    "counts; the outputs have one");
+  };
+  at_root(rl, params, "ancestral_sequences", kNoPerSiteOutput, true, one_state_count, [&](const at_root_t &r) {
+    copy_nodes(r.frame, nodes);
+    const size_t total = pattern_count();
+    const unsigned n_ops = (unsigned)r.ops.size();
     std::vector<uint8_t> part_state;
     std::vector<double> part_prob, part_post;
-    for (size_t p = 0; p < P; ++p) {
+    evaluate_partitions(r.ops, r.pmi, r.brl, false, [&](size_t p, size_t at) {
       rdamd_partition_t *part = _partitions[p];
       const size_t sites = rdamd_partition_sites(part), K = rdamd_partition_states(part);
-      rdamd_update_clvs(part, ops.data(), n_ops);
-      if (rdamd_errno()) fail("update_clvs");
       if (state) part_state.resize((size_t)n_ops * sites);
       if (prob) part_prob.resize((size_t)n_ops * sites);
       if (post) part_post.resize((size_t)n_ops * sites * K);
-      if (rdamd_ancestral_sequences(part, ops.data(), n_ops, _param_indicies[p].data(), state ? part_state.data() : nullptr,
+      if (rdamd_ancestral_sequences(part, r.ops.data(), n_ops, _param_indicies[p].data(), state ? part_state.data() : nullptr,
                                     prob ? part_prob.data() : nullptr, post ? part_post.data() : nullptr) != RDAMD_SUCCESS)
-        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
-      for (size_t k = 0; k < n_ops; ++k) {
-        if (state) std::copy(part_state.begin() + k * sites, part_state.begin() + (k + 1) * sites, state + k * total + at);
-        if (prob) std::copy(part_prob.begin() + k * sites, part_prob.begin() + (k + 1) * sites, prob + k * total + at);
-        if (post)
-          std::copy(part_post.begin() + k * sites * K, part_post.begin() + (k + 1) * sites * K, post + (k * total + at) * K);
-      }
-      at += sites;
-    }
+        return RDAMD_FAILURE;
+      if (state) scatter_columns(part_state.data(), n_ops, sites, 1, total, at, state);
+      if (prob) scatter_columns(part_prob.data(), n_ops, sites, 1, total, at, prob);
+      if (post) scatter_columns(part_post.data(), n_ops, sites, K, total, at, post);
+      return RDAMD_SUCCESS;
+    });
   });
 }
 
 // Branch-length derivatives at one root, and (bounds given) the lengths that maximise lnL there.
-// One evaluation at lengths x: update_pmatrices on the schedule's matrix indices with x, a
-// materialising traversal, the root lnL, and rdamd_branch_length_derivatives per partition, summed in
-// partition order.  Saves and restores what ancestral does.
+// One evaluation at lengths x: the schedule's matrices at x, a materialising traversal, the root lnL
+// and rdamd_branch_length_derivatives per partition, summed in partition order.
 model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
                                                   const branch_bounds_t *bounds) {
-  refuse_site_group("branch_lengths", "derivatives of a site-sharded model are not supported");
-  const size_t P = _partitions.size();
-  if (params) require_fit(*params, "branch_lengths", "");
-  if (bounds && !(bounds->min_len > 0.0 && bounds->min_len < bounds->max_len && std::isfinite(bounds->max_len) &&
-                  bounds->atol > 0.0))
-    throw std::invalid_argument("branch_lengths: 0 < min_len < max_len < inf and atol > 0 are required");
+  const auto sound_bounds = [&] {
+    if (bounds && !(bounds->min_len > 0.0 && bounds->min_len < bounds->max_len && std::isfinite(bounds->max_len) &&
+                    bounds->atol > 0.0))
+      throw std::invalid_argument("branch_lengths: 0 < min_len < max_len < inf and atol > 0 are required");
+  };
   branch_lengths_t out;
-  with_saved_parameters(true, [] {}, [&] {
-    if (params) set_model_params(*params);
-    auto sched = _tree.generate_operations(rl);
-    const auto &ops = std::get<0>(sched);
-    const auto &pmi = std::get<1>(sched);
-    const auto &brl = std::get<2>(sched);
-    const unsigned n_ops = (unsigned)ops.size();
-    out.node_clv.resize(n_ops);
-    out.node_parent.resize(n_ops);
-    out.node_children.resize(2 * (size_t)n_ops);
-    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, out.node_clv.data(), out.node_parent.data(),
-                                       out.node_children.data()) != RDAMD_SUCCESS)
-      fail("marginal_ancestral_nodes");
-    // branch (k, c) -> its place in the schedule's matrix list
-    std::unordered_map<unsigned, size_t> place;
-    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
-    std::vector<size_t> at(2 * (size_t)n_ops);
-    std::vector<double> x(at.size());
-    for (unsigned k = 0; k < n_ops; ++k) {
-      const rdamd_operation_t &o = ops[n_ops - 1 - k];
-      at[2 * k] = place.at(o.child1_matrix_index);
-      at[2 * k + 1] = place.at(o.child2_matrix_index);
-      x[2 * k] = brl[at[2 * k]];
-      x[2 * k + 1] = brl[at[2 * k + 1]];
-    }
-    std::vector<double> lens(brl), part_d1(at.size()), part_d2(at.size());
+  at_root(rl, params, "branch_lengths", kNoDerivatives, true, sound_bounds, [&](const at_root_t &r) {
+    copy_nodes(r.frame, &out);
+    const unsigned n_ops = (unsigned)r.ops.size();
+    const std::vector<size_t> &at = r.frame.place;
+    const std::vector<double> &x = r.frame.lengths;
+    std::vector<double> lens(r.brl), part_d1(at.size()), part_d2(at.size());
     const auto eval = [&](const std::vector<double> &len, double *f, std::vector<double> &g, std::vector<double> &h) {
       for (size_t b = 0; b < at.size(); ++b) lens[at[b]] = len[b];
-      update_pmatrices(pmi, lens);
-      ++_n_full;
       std::fill(g.begin(), g.end(), 0.0);
       std::fill(h.begin(), h.end(), 0.0);
-      double lh = 0.0;
-      for (size_t p = 0; p < P; ++p) {
-        rdamd_partition_t *part = _partitions[p];
-        rdamd_update_clvs(part, ops.data(), n_ops);
-        if (rdamd_errno()) fail("update_clvs");
-        lh += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
-                                               _param_indicies[p].data(), nullptr);
-        if (rdamd_errno()) fail("compute_root_loglikelihood");
-        if (rdamd_branch_length_derivatives(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
-                                            part_d1.data(), part_d2.data()) != RDAMD_SUCCESS)
-          throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+      *f = evaluate_partitions(r.ops, r.pmi, lens, true, [&](size_t p, size_t) {
+        if (rdamd_branch_length_derivatives(_partitions[p], r.ops.data(), n_ops, _param_indicies[p].data(),
+                                            _param_indicies[p].data(), part_d1.data(), part_d2.data()) != RDAMD_SUCCESS)
+          return RDAMD_FAILURE;
         for (size_t b = 0; b < at.size(); ++b) { g[b] += part_d1[b]; h[b] += part_d2[b]; }
-      }
-      *f = lh;
+        return RDAMD_SUCCESS;
+      });
     };
     if (bounds) {
-      rdamd::BrlenOptResult r = rdamd::optimize_branch_lengths(x, bounds->min_len, bounds->max_len, bounds->atol,
-                                                               bounds->max_iters, eval);
-      out.lengths = std::move(r.x); out.d1 = std::move(r.g); out.d2 = std::move(r.h);
-      out.lnl_before = r.f_before; out.lnl_after = r.f_after;
-      out.iterations = r.iterations; out.evaluations = r.evaluations; out.converged = r.converged;
+      rdamd::BrlenOptResult res = rdamd::optimize_branch_lengths(x, bounds->min_len, bounds->max_len, bounds->atol,
+                                                                 bounds->max_iters, eval);
+      out.lengths = std::move(res.x); out.d1 = std::move(res.g); out.d2 = std::move(res.h);
+      out.lnl_before = res.f_before; out.lnl_after = res.f_after;
+      out.iterations = res.iterations; out.evaluations = res.evaluations; out.converged = res.converged;
     } else {
       out.d1.resize(x.size());
       out.d2.resize(x.size());
@@ -678,56 +674,25 @@ model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, con
 // d lnL / d (subst, pi, rho, w) with pi and w as the partition holds them (rdamd_gradient_from_pair_sums);
 // the chain rule to the optimiser's variables is closed-form for pi = x / sum x and w = u / sum u,
 // and a central difference of the host's own rdamd_compute_gamma_cats (step 1e-6 max(1, alpha))
-// for rho(alpha).
+// for rho(alpha).  (No node arrays: nothing here is per node.)
 std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
                                                       const std::vector<partition_parameters_t> &params, double *lnl) {
-  refuse_site_group("gradient", "derivatives of a site-sharded model are not supported");
-  const size_t P = _partitions.size();
-  require_fit(params, "gradient", "");
-  std::vector<partition_parameters_t> out(P);
-  with_saved_parameters(true, [] {}, [&] {
-    set_model_params(params);
-    auto sched = _tree.generate_operations(rl);
-    const auto &ops = std::get<0>(sched);
-    const auto &pmi = std::get<1>(sched);
-    const auto &brl = std::get<2>(sched);
-    const unsigned n_ops = (unsigned)ops.size();
-    std::unordered_map<unsigned, size_t> place;
-    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
-    std::vector<double> lengths(2 * (size_t)n_ops);
-    for (unsigned k = 0; k < n_ops; ++k) {
-      const rdamd_operation_t &o = ops[n_ops - 1 - k];
-      lengths[2 * k] = brl[place.at(o.child1_matrix_index)];
-      lengths[2 * k + 1] = brl[place.at(o.child2_matrix_index)];
-    }
-    update_pmatrices(pmi, brl);
-    ++_n_full;
-    double lh = 0.0;
-    for (size_t p = 0; p < P; ++p) {
+  std::vector<partition_parameters_t> out(_partitions.size());
+  at_root(rl, &params, "gradient", kNoDerivatives, false, [] {}, [&](const at_root_t &r) {
+    const unsigned n_ops = (unsigned)r.ops.size();
+    const double lh = evaluate_partitions(r.ops, r.pmi, r.brl, true, [&](size_t p, size_t) {
       rdamd_partition_t *part = _partitions[p];
       const unsigned K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part);
       const partition_parameters_t &pp = params[p];
       const bool free_rates = _rate_category_types[p] == rate_category::FREE;
-      rdamd_update_clvs(part, ops.data(), n_ops);
-      if (rdamd_errno()) fail("update_clvs");
-      lh += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
-                                             _param_indicies[p].data(), nullptr);
-      if (rdamd_errno()) fail("compute_root_loglikelihood");
       std::vector<double> pair((size_t)n_ops * 2 * R * K * K), root((size_t)R * K), cat(R);
-      if (rdamd_branch_pair_sums(part, ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), root.data(),
+      if (rdamd_branch_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), root.data(),
                                  cat.data()) != RDAMD_SUCCESS)
-        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+        return RDAMD_FAILURE;
       // pi and w as set_model_params applied them
-      model_params_t pi(pp.freqs), w(_rate_weights[p]);
       double xsum = 0.0, usum = 1.0;
-      for (double f : pi) xsum += f;
-      for (double &f : pi) f /= xsum;
-      if (free_rates) {
-        w = pp.gamma_weights;
-        usum = 0.0;
-        for (double f : w) usum += f;
-        for (double &f : w) f /= usum;
-      }
+      const model_params_t pi = normalised(pp.freqs, &xsum);
+      const model_params_t w = free_rates ? normalised(pp.gamma_weights, &usum) : _rate_weights[p];
       std::vector<double> d_pi(K), d_rho(R), d_w(R);
       partition_parameters_t &g = out[p];
       g.subst_rates.assign(pp.subst_rates.size(), 0.0);
@@ -735,27 +700,28 @@ std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
       g.gamma_alpha.assign(pp.gamma_alpha.size(), 0.0);
       g.gamma_weights.assign(pp.gamma_weights.size(), 0.0);
       const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
-      if (rdamd_gradient_from_pair_sums(K, R, 1, n_ops, pair.data(), root.data(), cat.data(), lengths.data(),
+      if (rdamd_gradient_from_pair_sums(K, R, 1, n_ops, pair.data(), root.data(), cat.data(), r.frame.lengths.data(),
                                         pp.subst_rates.data(), pi.data(), zeros.data(), zeros.data(), _rate_rates[p].data(),
                                         w.data(), g.subst_rates.data(), d_pi.data(), d_rho.data(), d_w.data()) != RDAMD_SUCCESS)
-        throw std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg());
+        return RDAMD_FAILURE;
       double mean = 0.0;
       for (unsigned i = 0; i < K; ++i) mean += pi[i] * d_pi[i];
       for (unsigned i = 0; i < K; ++i) g.freqs[i] = (d_pi[i] - mean) / xsum;
       if (free_rates) {
         mean = 0.0;
-        for (unsigned r = 0; r < R; ++r) mean += w[r] * d_w[r];
-        for (unsigned r = 0; r < R; ++r) g.gamma_weights[r] = (d_w[r] - mean) / usum;
+        for (unsigned i = 0; i < R; ++i) mean += w[i] * d_w[i];
+        for (unsigned i = 0; i < R; ++i) g.gamma_weights[i] = (d_w[i] - mean) / usum;
       } else if (!pp.gamma_alpha.empty()) {
         const double alpha = pp.gamma_alpha[0], h = 1e-6 * std::max(1.0, alpha);
         std::vector<double> up(R), down(R);
         rdamd_compute_gamma_cats(alpha + h, R, up.data(), RDAMD_GAMMA_RATES_MEDIAN);
         rdamd_compute_gamma_cats(alpha - h, R, down.data(), RDAMD_GAMMA_RATES_MEDIAN);
         double ga = 0.0;
-        for (unsigned r = 0; r < R; ++r) ga += d_rho[r] * (up[r] - down[r]) / (2.0 * h);
+        for (unsigned i = 0; i < R; ++i) ga += d_rho[i] * (up[i] - down[i]) / (2.0 * h);
         g.gamma_alpha[0] = ga;
       }
-    }
+      return RDAMD_SUCCESS;
+    });
     if (lnl) *lnl = lh;
   });
   return out;
@@ -765,83 +731,48 @@ std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
 // host assembly of subst_map.hpp in place of the gradient's and the walk's fourth consumer after it.
 model_t::substitutions_t model_t::substitutions(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
                                                 bool per_site) {
-  refuse_site_group("substitutions", "per-site output of a site-sharded model is not supported");
-  const size_t P = _partitions.size(), total = pattern_count();
-  require_fit(params, "substitutions", "");
   substitutions_t out;
-  with_saved_parameters(true, [] {}, [&] {
-    set_model_params(params);
-    auto sched = _tree.generate_operations(rl);
-    const auto &ops = std::get<0>(sched);
-    const auto &pmi = std::get<1>(sched);
-    const auto &brl = std::get<2>(sched);
-    const unsigned n_ops = (unsigned)ops.size();
-    out.node_clv.resize(n_ops);
-    out.node_parent.resize(n_ops);
-    out.node_children.resize(2 * (size_t)n_ops);
-    if (rdamd_marginal_ancestral_nodes(ops.data(), n_ops, out.node_clv.data(), out.node_parent.data(),
-                                       out.node_children.data()) != RDAMD_SUCCESS)
-      fail("marginal_ancestral_nodes");
-    std::unordered_map<unsigned, size_t> place;
-    for (size_t i = 0; i < pmi.size(); ++i) place[pmi[i]] = i;
-    const size_t branches = 2 * (size_t)n_ops;
-    out.lengths.resize(branches);
-    for (unsigned k = 0; k < n_ops; ++k) {
-      const rdamd_operation_t &o = ops[n_ops - 1 - k];
-      out.lengths[2 * k] = brl[place.at(o.child1_matrix_index)];
-      out.lengths[2 * k + 1] = brl[place.at(o.child2_matrix_index)];
-    }
+  at_root(rl, &params, "substitutions", kNoPerSiteOutput, true, [] {}, [&](const at_root_t &r) {
+    copy_nodes(r.frame, &out);
+    out.lengths = r.frame.lengths;
+    const size_t total = pattern_count(), branches = out.lengths.size();
+    const unsigned n_ops = (unsigned)r.ops.size();
     if (per_site) {
       out.change.assign(branches * total, 0.0);
       out.count.assign(branches * total, 0.0);
       out.top_prob.assign(branches * total, 0.0);
       out.top_pair.assign(branches * total, 0);
     }
-    update_pmatrices(pmi, brl);
-    ++_n_full;
-    size_t at = 0;   // first pattern of the partition in the concatenated list
     std::vector<double> pair, change, count, top_prob;
     std::vector<unsigned char> top_pair;
-    for (size_t p = 0; p < P; ++p) {
+    out.lnl = evaluate_partitions(r.ops, r.pmi, r.brl, true, [&](size_t p, size_t at) {
       rdamd_partition_t *part = _partitions[p];
       const size_t K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part), sites = rdamd_partition_sites(part);
-      const auto refused = [&] { return std::runtime_error("partition " + std::to_string(p) + ": " + rdamd_errmsg()); };
-      rdamd_update_clvs(part, ops.data(), n_ops);
-      if (rdamd_errno()) fail("update_clvs");
-      out.lnl += rdamd_compute_root_loglikelihood(part, _tree.root_clv_index(), _tree.root_scaler_index(),
-                                                  _param_indicies[p].data(), nullptr);
-      if (rdamd_errno()) fail("compute_root_loglikelihood");
       pair.assign(branches * R * K * K, 0.0);
-      if (rdamd_branch_pair_sums(part, ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), nullptr, nullptr) !=
+      if (rdamd_branch_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), nullptr, nullptr) !=
           RDAMD_SUCCESS)
-        throw refused();
-      model_params_t pi(params[p].freqs);   // as set_model_params applied them
-      double xsum = 0.0;
-      for (double f : pi) xsum += f;
-      for (double &f : pi) f /= xsum;
+        return RDAMD_FAILURE;
+      const model_params_t pi = normalised(params[p].freqs);   // as set_model_params applied them
       const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
       const size_t typed_at = out.typed.size();
       out.typed.resize(typed_at + branches * K * K);
       if (rdamd_substitution_counts_from_pair_sums((unsigned)K, (unsigned)R, 1, n_ops, pair.data(), out.lengths.data(),
                                                    params[p].subst_rates.data(), pi.data(), zeros.data(),
                                                    _rate_rates[p].data(), out.typed.data() + typed_at) != RDAMD_SUCCESS)
-        throw refused();
-      if (per_site) {
-        change.resize(branches * sites); count.resize(branches * sites);
-        top_prob.resize(branches * sites); top_pair.resize(branches * sites);
-        if (rdamd_branch_substitutions(part, ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
-                                       out.lengths.data(), change.data(), count.data(), top_pair.data(), top_prob.data(),
-                                       nullptr) != RDAMD_SUCCESS)
-          throw refused();
-        for (size_t b = 0; b < branches; ++b) {
-          std::copy(change.begin() + b * sites, change.begin() + (b + 1) * sites, out.change.begin() + b * total + at);
-          std::copy(count.begin() + b * sites, count.begin() + (b + 1) * sites, out.count.begin() + b * total + at);
-          std::copy(top_prob.begin() + b * sites, top_prob.begin() + (b + 1) * sites, out.top_prob.begin() + b * total + at);
-          std::copy(top_pair.begin() + b * sites, top_pair.begin() + (b + 1) * sites, out.top_pair.begin() + b * total + at);
-        }
-      }
-      at += sites;
-    }
+        return RDAMD_FAILURE;
+      if (!per_site) return RDAMD_SUCCESS;
+      change.resize(branches * sites); count.resize(branches * sites);
+      top_prob.resize(branches * sites); top_pair.resize(branches * sites);
+      if (rdamd_branch_substitutions(part, r.ops.data(), n_ops, _param_indicies[p].data(), _param_indicies[p].data(),
+                                     out.lengths.data(), change.data(), count.data(), top_pair.data(), top_prob.data(),
+                                     nullptr) != RDAMD_SUCCESS)
+        return RDAMD_FAILURE;
+      scatter_columns(change.data(), branches, sites, 1, total, at, out.change.data());
+      scatter_columns(count.data(), branches, sites, 1, total, at, out.count.data());
+      scatter_columns(top_prob.data(), branches, sites, 1, total, at, out.top_prob.data());
+      scatter_columns(top_pair.data(), branches, sites, 1, total, at, out.top_pair.data());
+      return RDAMD_SUCCESS;
+    });
   });
   return out;
 }

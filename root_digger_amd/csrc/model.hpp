@@ -140,30 +140,31 @@ public:
   void site_lnls(const std::vector<root_location_t> &rls,
                  const std::vector<std::vector<partition_parameters_t>> *params, double *out);
   size_t pattern_count() const;
+  // the inner nodes in pre-order (root first), as rdamd_marginal_ancestral_nodes orders them
+  struct nodes_t {
+    std::vector<unsigned> node_clv, node_children;   // [nodes], [nodes][2]
+    std::vector<int> node_parent;                    // [nodes]; -1: the root
+  };
   // Marginal ancestral states and site rates at one root (include/root_digger_amd.h,
-  // rdamd_model_ancestral): node arrays in pre-order (root first), post[nodes][pattern_count()][states],
+  // rdamd_model_ancestral): nodes, post[nodes][pattern_count()][states],
   // cat: the partitions' [patterns][R] blocks back to back, mean_rate[pattern_count()]; any output may
   // be null.  params (optional): applied with set_model_params.  Saves and restores like site_lnls.
-  void ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
-                 std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
-                 std::vector<unsigned> *node_children, double *post, double *cat, double *mean_rate);
+  void ancestral(const root_location_t &rl, const std::vector<partition_parameters_t> *params, nodes_t *nodes,
+                 double *post, double *cat, double *mean_rate);
   // Ancestral sequences at one root (rdamd_model_ancestral_sequences): the likeliest state of every
   // inner node and pattern, state[nodes][pattern_count()], with its posterior prob[...] and, on
   // request, the table post[nodes][pattern_count()][states]; any output may be null.  Takes 20-state
   // partitions too (rdamd_ancestral_sequences); all partitions must have one state count.  Nodes,
   // params, saving and restoring as ancestral.
   void ancestral_sequences(const root_location_t &rl, const std::vector<partition_parameters_t> *params,
-                           std::vector<unsigned> *node_clv, std::vector<int> *node_parent,
-                           std::vector<unsigned> *node_children, uint8_t *state, double *prob, double *post);
+                           nodes_t *nodes, uint8_t *state, double *prob, double *post);
 
   // First and second derivatives of lnL in every branch length at one root, and the lengths that
   // maximise lnL there (include/root_digger_amd.h, rdamd_model_branch_derivatives /
   // rdamd_model_optimize_branch_lengths; the method: brlen_opt.hpp).  Nodes as ancestral orders them,
   // branch (k, c) above child c of node k.  Nothing is applied to the model or its tree; saves and
   // restores like site_lnls.
-  struct branch_lengths_t {
-    std::vector<unsigned> node_clv, node_children;
-    std::vector<int> node_parent;
+  struct branch_lengths_t : nodes_t {
     std::vector<double> lengths, d1, d2;   // [nodes][2]
     double lnl_before = 0.0, lnl_after = 0.0;
     unsigned iterations = 0, evaluations = 0;
@@ -186,9 +187,7 @@ public:
   // [nodes][2][K][K] block per partition back to back; change, count, top_prob, top_pair:
   // [nodes][2][pattern_count()], partitions concatenated.  The per-site arrays are filled only when
   // per_site is set.  Saves and restores what branch_lengths does.
-  struct substitutions_t {
-    std::vector<unsigned> node_clv, node_children;
-    std::vector<int> node_parent;
+  struct substitutions_t : nodes_t {
     std::vector<double> lengths, typed, change, count, top_prob;
     std::vector<unsigned char> top_pair;
     double lnl = 0.0;
@@ -344,12 +343,23 @@ public:
   rdamd_partition_t   *partition(size_t i) { return _partitions[i]; }
 
 private:
-  // model.cpp: what the analyses at a root (site_lnls, ancestral, branch_lengths) share
+  // model.cpp: what the analyses at a root (site_lnls, ancestral, ancestral_sequences, branch_lengths,
+  // gradient, substitutions) share
   struct saved_parameters_t;   // what they put back
   void refuse_site_group(const char *who, const char *unsupported) const;
   void require_fit(const std::vector<partition_parameters_t> &set, const char *who, const std::string &which) const;
   template <class Restore, class Body>
   void with_saved_parameters(bool rooting_back_on_failure, Restore restore_more, Body body);
+  // all but site_lnls (many roots, its own saving): the refusals, the saving, the parameters, the
+  // schedule of one root and its frame (root_frame.hpp), handed to body
+  struct at_root_t;
+  template <class Check, class Body>
+  void at_root(const root_location_t &rl, const std::vector<partition_parameters_t> *params, const char *who,
+               const char *unsupported, bool nodes, Check check, Body body);
+  // all six: one evaluation of a schedule, partition by partition
+  template <class Each>
+  double evaluate_partitions(const std::vector<rdamd_operation_t> &ops, const std::vector<unsigned> &pmi,
+                             const std::vector<double> &lengths, bool root_lnl, Each each);
   std::pair<root_location_t, double> brents(root_location_t beg, dlh_t d_beg,
                                             root_location_t end, dlh_t d_end, double atol);
   void set_tip_states(size_t p, const msa_t &msa);   // :302-325

@@ -354,29 +354,46 @@ int rdamd_msa_pattern_probe(const char *msa_filename, const uint64_t *map, unsig
     return RDAMD_SUCCESS;
   })
 }
+// The prologue of the analyses at a root, and their parameters: n_roots sets in the checkpoint's
+// layout (per root counts[n_partitions][4], values) into *sets, which stays empty when none are
+// given.  `required`: null if the parameters are optional, else why they are not (the refusal's
+// second half); null_argument: one of the caller's other required pointers is null.  false: refused
+// (a site-sharded model; the error is set).
+using param_set_t = std::vector<rdamd::partition_parameters_t>;
+static bool root_params(const rdamd_model_t *m, const char *who, bool null_argument, const char *required,
+                        const uint64_t *counts, const double *values, unsigned n_roots, std::vector<param_set_t> *sets) {
+  if (refuse_site_sharded(m, who)) return false;
+  if (required && (null_argument || !counts || !values))
+    throw std::invalid_argument(std::string(who) + ": null argument (the parameters are required: " + required + ")");
+  if ((counts == nullptr) != (values == nullptr))
+    throw std::invalid_argument(std::string(who) + ": counts and values come together");
+  if (null_argument) throw std::invalid_argument(std::string(who) + ": null argument");
+  for (unsigned i = 0; counts && i < n_roots; ++i) {
+    sets->emplace_back(m->model->partition_count());
+    for (rdamd::partition_parameters_t &pp : sets->back())
+      for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
+        v->assign(values, values + *counts);
+        values += *counts++;
+      }
+  }
+  return true;
+}
+static void copy_nodes(const rdamd::model_t::nodes_t &r, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
+                       unsigned int *node_children) {
+  if (n_nodes) *n_nodes = (unsigned)r.node_clv.size();
+  if (node_clv) std::copy(r.node_clv.begin(), r.node_clv.end(), node_clv);
+  if (node_parent) std::copy(r.node_parent.begin(), r.node_parent.end(), node_parent);
+  if (node_children) std::copy(r.node_children.begin(), r.node_children.end(), node_children);
+}
+
 int rdamd_model_site_lnls(rdamd_model_t *m, unsigned int n, const rdamd_root_location_t *rls,
                           const uint64_t *counts, const double *values, double *out_patterns) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_site_lnls")) return RDAMD_FAILURE;
-    if ((counts == nullptr) != (values == nullptr))
-      throw std::invalid_argument("rdamd_model_site_lnls: counts and values come together");
-    if (n && (!rls || !out_patterns)) throw std::invalid_argument("rdamd_model_site_lnls: null argument");
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_site_lnls", n && (!rls || !out_patterns), nullptr, counts, values, n, &params))
+      return RDAMD_FAILURE;
     std::vector<root_location_t> roots;
     for (unsigned i = 0; i < n; ++i) roots.push_back(to_cpp(&rls[i]));
-    std::vector<std::vector<rdamd::partition_parameters_t>> params;
-    if (counts) {
-      const size_t P = m->model->partition_count();
-      for (unsigned i = 0; i < n; ++i) {
-        params.emplace_back(P);
-        for (size_t p = 0; p < P; ++p) {
-          rdamd::partition_parameters_t &pp = params.back()[p];
-          for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
-            v->assign(values, values + *counts);
-            values += *counts++;
-          }
-        }
-      }
-    }
     m->model->site_lnls(roots, counts ? &params : nullptr, out_patterns);
     return RDAMD_SUCCESS;
   })
@@ -398,70 +415,28 @@ int rdamd_model_ancestral(rdamd_model_t *m, const rdamd_root_location_t *rl, con
                           const double *values, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
                           unsigned int *node_children, double *post_out, double *cat_out, double *mean_rate_out) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_ancestral")) return RDAMD_FAILURE;
-    if ((counts == nullptr) != (values == nullptr))
-      throw std::invalid_argument("rdamd_model_ancestral: counts and values come together");
-    if (!rl) throw std::invalid_argument("rdamd_model_ancestral: null argument");
-    std::vector<rdamd::partition_parameters_t> params;
-    if (counts) {
-      params.resize(m->model->partition_count());
-      for (rdamd::partition_parameters_t &pp : params)
-        for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
-          v->assign(values, values + *counts);
-          values += *counts++;
-        }
-    }
-    std::vector<unsigned> clv, children;
-    std::vector<int> parent;
-    m->model->ancestral(to_cpp(rl), counts ? &params : nullptr, &clv, &parent, &children, post_out, cat_out, mean_rate_out);
-    if (n_nodes) *n_nodes = (unsigned)clv.size();
-    if (node_clv) std::copy(clv.begin(), clv.end(), node_clv);
-    if (node_parent) std::copy(parent.begin(), parent.end(), node_parent);
-    if (node_children) std::copy(children.begin(), children.end(), node_children);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_ancestral", !rl, nullptr, counts, values, 1, &params)) return RDAMD_FAILURE;
+    rdamd::model_t::nodes_t nodes;
+    m->model->ancestral(to_cpp(rl), counts ? &params[0] : nullptr, &nodes, post_out, cat_out, mean_rate_out);
+    copy_nodes(nodes, n_nodes, node_clv, node_parent, node_children);
     return RDAMD_SUCCESS;
   })
-}
-
-// one root's parameters in the checkpoint's layout (counts[n_partitions][4], values)
-static std::vector<rdamd::partition_parameters_t> one_root_params(const rdamd_model_t *m, const uint64_t *counts,
-                                                                  const double *values) {
-  std::vector<rdamd::partition_parameters_t> params(m->model->partition_count());
-  for (rdamd::partition_parameters_t &pp : params)
-    for (rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights}) {
-      v->assign(values, values + *counts);
-      values += *counts++;
-    }
-  return params;
 }
 int rdamd_model_ancestral_sequences(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                                     const double *values, unsigned int *n_nodes, unsigned int *node_clv,
                                     int *node_parent, unsigned int *node_children, uint8_t *state_out,
                                     double *prob_out, double *post_out) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_ancestral_sequences")) return RDAMD_FAILURE;
-    if ((counts == nullptr) != (values == nullptr))
-      throw std::invalid_argument("rdamd_model_ancestral_sequences: counts and values come together");
-    if (!rl) throw std::invalid_argument("rdamd_model_ancestral_sequences: null argument");
-    std::vector<rdamd::partition_parameters_t> params;
-    if (counts) params = one_root_params(m, counts, values);
-    std::vector<unsigned> clv, children;
-    std::vector<int> parent;
-    m->model->ancestral_sequences(to_cpp(rl), counts ? &params : nullptr, &clv, &parent, &children, state_out, prob_out,
-                                  post_out);
-    if (n_nodes) *n_nodes = (unsigned)clv.size();
-    if (node_clv) std::copy(clv.begin(), clv.end(), node_clv);
-    if (node_parent) std::copy(parent.begin(), parent.end(), node_parent);
-    if (node_children) std::copy(children.begin(), children.end(), node_children);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_ancestral_sequences", !rl, nullptr, counts, values, 1, &params)) return RDAMD_FAILURE;
+    rdamd::model_t::nodes_t nodes;
+    m->model->ancestral_sequences(to_cpp(rl), counts ? &params[0] : nullptr, &nodes, state_out, prob_out, post_out);
+    copy_nodes(nodes, n_nodes, node_clv, node_parent, node_children);
     return RDAMD_SUCCESS;
   })
 }
-static void copy_branch_result(const rdamd::model_t::branch_lengths_t &r, unsigned int *n_nodes, unsigned int *node_clv,
-                               int *node_parent, unsigned int *node_children, double *lengths_out, double *d1_out,
-                               double *d2_out) {
-  if (n_nodes) *n_nodes = (unsigned)r.node_clv.size();
-  if (node_clv) std::copy(r.node_clv.begin(), r.node_clv.end(), node_clv);
-  if (node_parent) std::copy(r.node_parent.begin(), r.node_parent.end(), node_parent);
-  if (node_children) std::copy(r.node_children.begin(), r.node_children.end(), node_children);
+static void copy_branch_result(const rdamd::model_t::branch_lengths_t &r, double *lengths_out, double *d1_out, double *d2_out) {
   if (lengths_out) std::copy(r.lengths.begin(), r.lengths.end(), lengths_out);
   if (d1_out) std::copy(r.d1.begin(), r.d1.end(), d1_out);
   if (d2_out) std::copy(r.d2.begin(), r.d2.end(), d2_out);
@@ -471,14 +446,11 @@ int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t
                                    int *node_parent, unsigned int *node_children, double *lengths_out,
                                    double *d1_out, double *d2_out, double *lnl_out) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_branch_derivatives")) return RDAMD_FAILURE;
-    if ((counts == nullptr) != (values == nullptr))
-      throw std::invalid_argument("rdamd_model_branch_derivatives: counts and values come together");
-    if (!rl) throw std::invalid_argument("rdamd_model_branch_derivatives: null argument");
-    std::vector<rdamd::partition_parameters_t> params;
-    if (counts) params = one_root_params(m, counts, values);
-    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params : nullptr, nullptr);
-    copy_branch_result(r, n_nodes, node_clv, node_parent, node_children, lengths_out, d1_out, d2_out);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_branch_derivatives", !rl, nullptr, counts, values, 1, &params)) return RDAMD_FAILURE;
+    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params[0] : nullptr, nullptr);
+    copy_nodes(r, n_nodes, node_clv, node_parent, node_children);
+    copy_branch_result(r, lengths_out, d1_out, d2_out);
     if (lnl_out) *lnl_out = r.lnl_before;
     return RDAMD_SUCCESS;
   })
@@ -486,13 +458,13 @@ int rdamd_model_branch_derivatives(rdamd_model_t *m, const rdamd_root_location_t
 int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts, const double *values,
                          double *grad_out, double *lnl_out) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_gradient")) return RDAMD_FAILURE;
-    if (!rl || !counts || !values || !grad_out)
-      throw std::invalid_argument("rdamd_model_gradient: null argument (the parameters are required: the gradient is "
-                                  "taken in the optimiser's variables, which the model does not keep)");
-    const std::vector<rdamd::partition_parameters_t> params = one_root_params(m, counts, values);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_gradient", !rl || !grad_out,
+                     "the gradient is taken in the optimiser's variables, which the model does not keep", counts, values, 1,
+                     &params))
+      return RDAMD_FAILURE;
     double lnl = 0.0;
-    const std::vector<rdamd::partition_parameters_t> g = m->model->gradient(to_cpp(rl), params, &lnl);
+    const param_set_t g = m->model->gradient(to_cpp(rl), params[0], &lnl);
     for (const rdamd::partition_parameters_t &pp : g)
       for (const rdamd::model_params_t *v : {&pp.subst_rates, &pp.freqs, &pp.gamma_alpha, &pp.gamma_weights})
         grad_out = std::copy(v->begin(), v->end(), grad_out);
@@ -505,17 +477,14 @@ int rdamd_model_substitutions(rdamd_model_t *m, const rdamd_root_location_t *rl,
                               unsigned int *node_children, double *lengths_out, double *typed_out, double *change_out,
                               double *count_out, unsigned char *top_pair_out, double *top_prob_out, double *lnl_out) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_substitutions")) return RDAMD_FAILURE;
-    if (!rl || !counts || !values)
-      throw std::invalid_argument("rdamd_model_substitutions: null argument (the parameters are required: the typed counts "
-                                  "are made from the substitution rates, which the model does not keep)");
-    const std::vector<rdamd::partition_parameters_t> params = one_root_params(m, counts, values);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_substitutions", !rl,
+                     "the typed counts are made from the substitution rates, which the model does not keep", counts, values, 1,
+                     &params))
+      return RDAMD_FAILURE;
     const bool per_site = change_out || count_out || top_pair_out || top_prob_out;
-    const rdamd::model_t::substitutions_t r = m->model->substitutions(to_cpp(rl), params, per_site);
-    if (n_nodes) *n_nodes = (unsigned)r.node_clv.size();
-    if (node_clv) std::copy(r.node_clv.begin(), r.node_clv.end(), node_clv);
-    if (node_parent) std::copy(r.node_parent.begin(), r.node_parent.end(), node_parent);
-    if (node_children) std::copy(r.node_children.begin(), r.node_children.end(), node_children);
+    const rdamd::model_t::substitutions_t r = m->model->substitutions(to_cpp(rl), params[0], per_site);
+    copy_nodes(r, n_nodes, node_clv, node_parent, node_children);
     if (lengths_out) std::copy(r.lengths.begin(), r.lengths.end(), lengths_out);
     if (typed_out) std::copy(r.typed.begin(), r.typed.end(), typed_out);
     if (change_out) std::copy(r.change.begin(), r.change.end(), change_out);
@@ -532,15 +501,11 @@ int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_locat
                                         double *lnl_before, double *lnl_after, unsigned int *iterations,
                                         unsigned int *evaluations, int *converged) {
   GUARD(RDAMD_FAILURE, {
-    if (refuse_site_sharded(m, "rdamd_model_optimize_branch_lengths")) return RDAMD_FAILURE;
-    if ((counts == nullptr) != (values == nullptr))
-      throw std::invalid_argument("rdamd_model_optimize_branch_lengths: counts and values come together");
-    if (!rl) throw std::invalid_argument("rdamd_model_optimize_branch_lengths: null argument");
-    std::vector<rdamd::partition_parameters_t> params;
-    if (counts) params = one_root_params(m, counts, values);
+    std::vector<param_set_t> params;
+    if (!root_params(m, "rdamd_model_optimize_branch_lengths", !rl, nullptr, counts, values, 1, &params)) return RDAMD_FAILURE;
     const rdamd::model_t::branch_bounds_t bounds{min_len, max_len, atol, max_iters};
-    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params : nullptr, &bounds);
-    copy_branch_result(r, nullptr, nullptr, nullptr, nullptr, lengths_out, d1_out, d2_out);
+    const rdamd::model_t::branch_lengths_t r = m->model->branch_lengths(to_cpp(rl), counts ? &params[0] : nullptr, &bounds);
+    copy_branch_result(r, lengths_out, d1_out, d2_out);
     if (lnl_before) *lnl_before = r.lnl_before;
     if (lnl_after) *lnl_after = r.lnl_after;
     if (iterations) *iterations = r.iterations;
