@@ -1168,8 +1168,26 @@ int rdamd_model_optimize_branch_lengths(rdamd_model_t *m, const rdamd_root_locat
 int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
                            const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
                            double *root_out, double *cat_out);
-/* device time of the launches of this thread's last rdamd_branch_pair_sums call, milliseconds
- * between two HIP events (0 after a failed call); for measurements */
+/* The same sums for every shape the pre-order walk takes: the same arguments, outputs and errors.
+ * 4-state and binary partitions run the launches of rdamd_branch_pair_sums and return its bits.
+ * 20-state partitions in the matrix-core CLV layout (up to 8 rate categories) run the pair-sum
+ * consumer of the 20-state walk (csrc/kernels_preorder_k20.hip): a wave is (16 sites, one rate), and
+ * its sum over the 16 sites is a 20 x 16 by 16 x 20 product, 25 FP64 MFMAs whose four blocks are the
+ * four quads of sites.  Order of a sum: the MFMA's own accumulation over the four sites of a quad;
+ * the four quads by lanes 4 apart, then 8 apart; one partial per (tile of 16 sites, entry); a second
+ * kernel that continues each entry's running sum by increasing tile.  M and W: each wave its own
+ * rate, froot and f0 added over the rates in rate order, the 16 sites of a tile by a butterfly (lanes
+ * 1, 2, 4, 8 apart), then the tiles likewise.  No floating-point atomics.  The walk runs in passes
+ * over contiguous ranges of whole tiles so that the partials of one pass take at most
+ * workspace_bytes (0: 1 GiB for 20 states, 256 MiB otherwise; never less than one tile per pass);
+ * the result is bit for bit independent of the number of passes.  The sums inherit the 2^-510 limit
+ * stated above.  Error 63, the shape named in the message: RDAMD_ATTRIB_SPARSE_CLVS, 20 states with
+ * more than 8 rate categories (the plain CLV layout), any state count other than 2, 4 and 20. */
+int rdamd_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                    const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
+                    double *root_out, double *cat_out);
+/* device time of the launches of this thread's last rdamd_branch_pair_sums or rdamd_pair_sums call,
+ * milliseconds between two HIP events (0 after a failed call); for measurements */
 double rdamd_pair_sums_last_ms(void);
 /* The exact gradient from the pair sums: plain host code, a pure function of its arguments, no
  * device needed.  states K in {2, ..., 64}; pair[n_ops][2][R][K][K], root[R][K], cat[R] as above;
@@ -1207,10 +1225,12 @@ int rdamd_gradient_from_pair_sums(unsigned int states, unsigned int rate_cats, u
  *   the unnormalised category weights u of a FREE partition, w = u / sum u; a FREE partition's rates
  *     are inert, so its alpha entry is 0; the weight entries of any other partition are 0.
  * Each evaluation is rdamd_update_prob_matrices, a materialising traversal, the root lnL (*lnl_out,
- * may be NULL), rdamd_branch_pair_sums per partition and rdamd_gradient_from_pair_sums.  The model's
+ * may be NULL), rdamd_pair_sums per partition and rdamd_gradient_from_pair_sums: DNA, binary and
+ * protein models are served (a protein partition: 380 rates, 20 frequencies and alpha from one pass
+ * of the walk, where a one-sided difference takes 381 evaluations).  The model's
  * parameters, its rooting and the conditional likelihoods of that rooting are as before when the
  * call returns.  Refused (error 61) for a model that sums over a site group; a partition whose shape
- * rdamd_branch_pair_sums refuses fails the call and is named in the message. */
+ * rdamd_pair_sums refuses fails the call and is named in the message. */
 int rdamd_model_gradient(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                          const double *values, double *grad_out, double *lnl_out);
 
@@ -1286,11 +1306,14 @@ int rdamd_substitution_counts_from_pair_sums(unsigned int states, unsigned int r
  * top_prob_out[n][2][P_total] and top_pair_out[n][2][P_total] (bytes) with the patterns of all
  * partitions concatenated in partition order (rdamd_model_site_patterns); *lnl_out: the
  * log-likelihood at that root.  Each partition: rdamd_update_prob_matrices, a materialising
- * traversal, rdamd_branch_pair_sums, rdamd_substitution_counts_from_pair_sums and
- * rdamd_branch_substitutions.  The model's parameters, its rooting and the conditional likelihoods
- * of that rooting are as before when the call returns.  Refused (error 61) for a model that sums
- * over a site group; a partition whose shape rdamd_branch_substitutions refuses fails the call and
- * is named in the message. */
+ * traversal, rdamd_pair_sums, rdamd_substitution_counts_from_pair_sums and -- unless change_out,
+ * count_out, top_pair_out and top_prob_out are all NULL -- rdamd_branch_substitutions.  With those
+ * four NULL the call serves every shape rdamd_pair_sums takes, protein models among them: typed_out
+ * then holds the expected i -> j counts over 20 x 20 amino-acid pairs and the dwell times.  The
+ * per-site outputs are for 4-state and binary partitions.  The model's parameters, its rooting and
+ * the conditional likelihoods of that rooting are as before when the call returns.  Refused (error
+ * 61) for a model that sums over a site group; a partition whose shape rdamd_pair_sums or (per-site
+ * outputs) rdamd_branch_substitutions refuses fails the call and is named in the message. */
 int rdamd_model_substitutions(rdamd_model_t *m, const rdamd_root_location_t *rl, const uint64_t *counts,
                               const double *values, unsigned int *n_nodes, unsigned int *node_clv, int *node_parent,
                               unsigned int *node_children, double *lengths_out, double *typed_out, double *change_out,

@@ -312,6 +312,7 @@ _sig("rdamd_branch_length_derivatives", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _
 _sig("rdamd_branch_last_ms", C.c_double)
 _sig("rdamd_model_gradient", C.c_int, _vp, C.POINTER(RootLocation), _pu64, _pd, _pd, _pd)
 _sig("rdamd_branch_pair_sums",C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd, _pd)
+_sig("rdamd_pair_sums", C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd, _pd)
 _sig("rdamd_pair_sums_last_ms", C.c_double)
 _sig("rdamd_gradient_from_pair_sums", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pd, _pd, _pd, _pd,
      _pd, _pd)
@@ -861,6 +862,22 @@ class Partition:
             _fail("branch_pair_sums")
         return pair, root, cat
 
+    def pair_sums(self, ops, freqs_indices=None, workspace_bytes=0):
+        """branch_pair_sums for every shape the pre-order walk takes (rdamd_pair_sums): 4-state and binary
+        partitions get branch_pair_sums' bits, matrix-core 20-state partitions (up to 8 rate categories)
+        the 20-state walk's consumer.  workspace_bytes bounds the partial sums of one pass (0: 1 GiB at
+        20 states, 256 MiB otherwise); the result does not depend on it by a bit."""
+        ops = _op_array(ops)
+        fi = self.params_indices if freqs_indices is None else np.ascontiguousarray(freqs_indices, dtype=np.uint32)
+        R, K = self.rate_cats, self.states
+        pair = np.zeros((len(ops), 2, R, K, K), dtype=np.float64)
+        root = np.zeros((R, K), dtype=np.float64)
+        cat = np.zeros(R, dtype=np.float64)
+        if lib.rdamd_pair_sums(self._h, ops, len(ops), _uptr(fi), int(workspace_bytes), _dptr(pair), _dptr(root),
+                               _dptr(cat)) != 1:
+            _fail("pair_sums")
+        return pair, root, cat
+
     def branch_substitutions(self, ops, lengths, params_indices=None, freqs_indices=None, joint=False):
         """Substitutions mapped onto the branches, per site (rdamd_branch_substitutions) -> dict with
         change, count, top_prob [len(ops)][2][sites] (float64), top_pair [len(ops)][2][sites] (uint8, the
@@ -1252,7 +1269,7 @@ def branch_last_ms():
 
 
 def pair_sums_last_ms():
-    """device milliseconds of the launches of this thread's last branch_pair_sums call"""
+    """device milliseconds of the launches of this thread's last branch_pair_sums or pair_sums call"""
     return float(lib.rdamd_pair_sums_last_ms())
 
 
@@ -1847,12 +1864,14 @@ class Model:
             out.append(d)
         return out, lnl.value
 
-    def substitutions(self, rl, params):
+    def substitutions(self, rl, params, per_site=True):
         """Substitutions mapped onto the branches at root rl (rdamd_model_substitutions) -> dict with
         node_clv[n], node_parent[n], node_children[n][2], lengths[n][2], typed (the list of the
         partitions' [n][2][K][K] arrays: expected i -> j counts off the diagonal, dwell times on it),
         change, count, top_prob, top_pair [n][2][P_total] (patterns of all partitions concatenated) and
         lnl.  params: the per-partition dicts Checkpoint.read_results returns for one root (required).
+        per_site=False leaves the four per-site arrays out (of the call and of the result): that serves
+        protein models, whose per-site outputs rdamd_branch_substitutions does not compute.
         Nothing is applied to the model."""
         counts, values = _flatten_params(list(params))
         nodes, total = _NodeArrays(self._tree.tip_count() - 1), self._total()
@@ -1861,14 +1880,15 @@ class Model:
         out = {"node_clv": nodes.clv, "node_parent": nodes.parent, "node_children": nodes.children,
                "lengths": np.zeros((n, 2))}
         typed = np.zeros(max(1, sum(n * 2 * k * k for k in ks)))
-        for key in ("change", "count", "top_prob"):
-            out[key] = np.zeros((n, 2, total))
-        out["top_pair"] = np.zeros((n, 2, total), dtype=np.uint8)
+        if per_site:
+            for key in ("change", "count", "top_prob"):
+                out[key] = np.zeros((n, 2, total))
+            out["top_pair"] = np.zeros((n, 2, total), dtype=np.uint8)
+        sites = [_dptr(out["change"]), _dptr(out["count"]), out["top_pair"].ctypes.data_as(_pub),
+                 _dptr(out["top_prob"])] if per_site else [None] * 4
         lnl = C.c_double(0.0)
         self._ok(lib.rdamd_model_substitutions(self._h, C.byref(rl), *_param_args(counts, values), *nodes.args(),
-                                               _dptr(out["lengths"]), _dptr(typed), _dptr(out["change"]),
-                                               _dptr(out["count"]), out["top_pair"].ctypes.data_as(_pub),
-                                               _dptr(out["top_prob"]), C.byref(lnl)), "substitutions")
+                                               _dptr(out["lengths"]), _dptr(typed), *sites, C.byref(lnl)), "substitutions")
         nodes.arrays()
         cuts = np.cumsum([0] + [n * 2 * k * k for k in ks])
         out["typed"] = [typed[cuts[i]:cuts[i + 1]].reshape(n, 2, k, k).copy() for i, k in enumerate(ks)]

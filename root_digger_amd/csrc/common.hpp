@@ -313,6 +313,12 @@ __device__ __forceinline__ bool site_terms(double f0, double f1, double f2, doub
   *d2 = weight * (f2 / f0 - g * g);
   return true;
 }
+// weight / f, and whether f is a likelihood: the site factor of both walks' pair-sum consumers
+__device__ __forceinline__ bool site_factor(double f, double weight, double *g) {
+  const bool ok = f > 0.0 && isfinite(f);
+  *g = ok ? weight / f : 0.0;
+  return ok;
+}
 // its second launch alone: d_out[e] = d_partials[b][e] added by increasing b < blocks, e < entries
 hipError_t launch_brlen_sum(rdamd_partition *p, const double *d_partials, unsigned blocks, unsigned entries, double *d_out);
 // kernels_preorder_k20.hip: the same two launches over a 20-state partition in the matrix-core operand
@@ -332,6 +338,16 @@ size_t pair_sum_stage_doubles(const rdamd_partition *p, unsigned blocks);
 hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,
                                    const unsigned *d_fidx, double *d_work, double *d_partials, double *d_stage,
                                    unsigned blocks_per_pass, unsigned *d_bad_sites, double *d_out);
+// its second launch alone: d_out[e] = (first: 0, else d_out[e]) + d_partials[b][e] added by increasing b < blocks
+hipError_t launch_pair_sum_fold(rdamd_partition *p, const double *d_partials, unsigned blocks, size_t entries, bool first,
+                                double *d_out);
+// kernels_preorder_k20.hip: the pair sums of a 20-state partition in the matrix-core operand layout, in
+// passes of at most tiles_per_pass (>= 1) whole tiles, one workgroup per tile; a row of partials and
+// d_out: k20_pair_sum_entries doubles ([nops][2][R][20][20] pair sums, then [R][21]: M[r][0..19], W[r]);
+// d_partials: [tiles_per_pass] rows
+hipError_t launch_pair_sum_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                       double *d_work, double *d_partials, unsigned tiles_per_pass, unsigned *d_bad_sites,
+                                       double *d_out);
 
 // substitutions mapped onto the branches of the same program, per site: d_cmat: the count matrices
 // [nops][2][R][16] of program operation k's two children (subst_map.hpp); the outputs, any of which

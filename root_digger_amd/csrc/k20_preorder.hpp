@@ -1,10 +1,11 @@
 // The 20-state pre-order walk's index arithmetic (kernels_preorder_k20.hip): where a lane finds its
 // A operand of the forward product P L and of the transposed product P^T t in the ONE MFMA-ready
 // copy of a P-matrix, the sizes of the walk's workspace and LDS, the host-side packing of such a copy
-// (the derivative consumer's rate matrices) and that consumer's LDS layout.  Plain arithmetic over
-// plain numbers -- no HIP, no partition -- so that tests/cpp/k20_preorder_check.cpp and
-// tests/cpp/k20_qcopy_check.cpp can emulate the matrix cores' lane map on the host and prove the
-// gathers and the packing before any GPU run.
+// (the derivative consumer's rate matrices), that consumer's LDS layout, and the pair-sum consumer's
+// re-deal of its two operands, its LDS layout and its row of partial sums.  Plain arithmetic over
+// plain numbers -- no HIP, no partition -- so that tests/cpp/k20_preorder_check.cpp,
+// tests/cpp/k20_qcopy_check.cpp and tests/cpp/k20_pairsum_check.cpp can emulate the matrix cores'
+// lane map on the host and prove the gathers, the packing and the re-deal before any GPU run.
 //
 // Lanes (kernels_clv_mfma.hip): col = lane % 16 is the site of the wave's tile, grp = lane / 16; a
 // vector of 20 states lives as five doubles per lane, operand t = state k20p_state_of(grp, t).
@@ -96,5 +97,45 @@ constexpr bool k20_brlen_fits_exchange() {
   return true;
 }
 static_assert(k20_brlen_fits_exchange(), "the derivative consumer lives in the exchange area: the walk's LDS does not grow");
+
+// The pair-sum consumer.  A wave's sum over its 16 sites, N[i][j] = sum_s T[i][s] L[s][j], is a
+// 20 x 16 by 16 x 20 product whose reduction dimension is the SITE, and a lane holds five states of
+// ONE site: both operands are re-dealt.  With the four blocks of an MFMA taken as the four quads of
+// sites (block b: sites 4 b .. 4 b + 3), lane (col, grp) supplies
+//   A[i = col % 4][k = grp] = T[state_of(col % 4, ib)][site 4 (col / 4) + grp]
+//   B[k = grp][n = col % 4] = L[site 4 (col / 4) + grp][state_of(col % 4, jb)]
+// for ib, jb = 0..4: operand ib (jb) of the lane that holds that site and those states, which is
+// the SAME lane for both operands and all five indices -- (col % 4, grp) transposed inside the quad.
+// So the re-deal is one fixed lane permutation (its own inverse) of ten doubles and takes no LDS.
+constexpr unsigned k20_pair_source_lane(unsigned lane) {
+  const unsigned col = lane & 15u, grp = lane >> 4;
+  return 16u * (col & 3u) + 4u * (col >> 2) + grp;
+}
+// MFMA (ib, jb) leaves in lane (col, grp) the quad's share of N[state_of(grp, ib)][state_of(col % 4, jb)];
+// the four quads are folded over col / 4 (lanes 4 apart, then 8 apart).  The entry, i * 20 + j:
+constexpr unsigned k20_pair_entry(unsigned lane, unsigned ib, unsigned jb) {
+  return k20p_state_of(lane >> 4, ib) * kK20States + k20p_state_of(lane & 3u, jb);
+}
+// a tile's row of partial sums (= the result): [nops][2][R][20][20] pair sums, then [R][21]: M[r][0..19], W[r]
+constexpr size_t k20_pair_sum_entries(size_t nops, size_t rate_cats) {
+  return nops * 2 * rate_cats * kK20States * kK20States + rate_cats * (kK20States + 1);
+}
+constexpr size_t k20_pair_root_at(size_t nops, size_t rate_cats) { return nops * 2 * rate_cats * kK20States * kK20States; }
+// Its use of the exchange area, in doubles from the start: the per-rate terms w_r t.(P_a L_a) of both
+// children of an operation, double-buffered by operation parity ([parity][child][rate][16 sites]),
+// then the per-rate terms w_r pi.L_root of the root ([rate][16 sites])
+constexpr size_t k20_pair_term_index(size_t rate_cats, unsigned parity, unsigned child, unsigned rate, unsigned site_in_tile) {
+  return ((parity * 2u + child) * rate_cats + rate) * 16u + site_in_tile;
+}
+constexpr size_t k20_pair_root_index(size_t rate_cats, unsigned rate, unsigned site_in_tile) {
+  return (4u * rate_cats + rate) * 16u + site_in_tile;
+}
+constexpr size_t k20_pair_exchange_doubles(size_t rate_cats) { return 5 * rate_cats * 16; }
+constexpr bool k20_pair_fits_exchange() {
+  for (size_t r = 1; r <= kK20MaxRates; ++r)
+    if (k20_pair_exchange_doubles(r) * sizeof(double) > k20_preorder_exchange_bytes(r)) return false;
+  return true;
+}
+static_assert(k20_pair_fits_exchange(), "the pair-sum consumer lives in the exchange area: the walk's LDS does not grow");
 
 }  // namespace rdamd

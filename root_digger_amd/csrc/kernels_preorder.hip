@@ -567,13 +567,6 @@ __host__ __device__ inline size_t pair_sum_entries(unsigned nops, unsigned R) {
   return (size_t)nops * 2 * R * 16 + (size_t)R * 5;
 }
 
-// weight / f, and whether f is a likelihood
-__device__ __forceinline__ bool site_factor(double f, double weight, double *g) {
-  const bool ok = f > 0.0 && isfinite(f);
-  *g = ok ? weight / f : 0.0;
-  return ok;
-}
-
 template <int R>
 struct PairSumDna {
   using Args = PairSumArgs;
@@ -1057,11 +1050,16 @@ hipError_t launch_pair_sum_program(rdamd_partition *p, const OuterOp *d_prog, un
     const PairSumArgs ca{p->d_pattern_weights + site0, d_partials, d_bad_sites, d_stage, R};
     hipError_t e = launch_walk<PairSumDna, PairSumGeneric>(p, d_prog, nops, slots, d_fidx, d_work, ca, site0, sites);
     if (e != hipSuccess) return e;
-    pair_sum_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, p->stream>>>(d_partials, nb, entries, b0 == 0, d_out);
-    e = hipGetLastError();
+    e = launch_pair_sum_fold(p, d_partials, nb, entries, b0 == 0, d_out);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_pair_sum_fold(rdamd_partition *p, const double *d_partials, unsigned blocks, size_t entries, bool first,
+                                double *d_out) {
+  pair_sum_kernel<<<(unsigned)((entries + 255) / 256), 256, 0, p->stream>>>(d_partials, blocks, entries, first, d_out);
+  return hipGetLastError();
 }
 
 hipError_t launch_subst_program(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, unsigned slots,

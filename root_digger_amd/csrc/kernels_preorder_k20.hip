@@ -1,7 +1,7 @@
 // The pre-order pass for 20-state partitions in the matrix-core operand layout
 // (rdamd_partition::mfma_layout): the OUTER vectors of kernels_preorder.hip on
-// v_mfma_f64_4x4x4_4b_f64, and their consumers: the marginal ancestral state posteriors, and the
-// first and second derivative of lnL in every branch length.
+// v_mfma_f64_4x4x4_4b_f64, and their consumers: the marginal ancestral state posteriors, the
+// first and second derivative of lnL in every branch length, and the branch pair sums.
 //
 // New here -- the reference computes no ancestral states; this extends the traversal it makes with
 // corax_update_clvs (src/model.cpp:402) by the complementary pass, for protein data.  Definitions as
@@ -64,6 +64,14 @@
 // LDS: the copies (R x 3 200 B) and the terms (R x 1 536 B) live in the exchange area (R x 5 120 B):
 // k20_preorder_lds_bytes is unchanged (static_assert in k20_preorder.hpp).
 //
+// The pair sums (PairSumK20; definitions: include/root_digger_amd.h, "Branch pair sums"): the comment
+// above the consumer has the scheme.  It needs a tip child's 0/1 vector, which the walk makes from the
+// tip's code and the partition's code masks for a consumer that sets kTipVectors (off: the walk
+// compiles to what it was), and it runs in passes over ranges of whole tiles: workgroup b of a launch
+// walks tile tile0 + b and writes row b of the pass's partials.  Its two operands are re-dealt by a
+// lane permutation (k20_preorder.hpp; proven by tests/cpp/k20_pairsum_check.cpp), not through LDS:
+// its LDS is 80 doubles per rate in the exchange area.
+//
 // Sites past the end: loads are clamped as the forward kernel clamps them (ls, ll: a lane past S reads
 // the last site's data, never a tile's padding, which no kernel writes); such lanes store nothing.
 //
@@ -80,8 +88,11 @@
 //   preorder_k20_walk<512, DerivativeK20<true>>    VGPRs 192   SGPRs 96   scratch 0 B   2 waves per SIMD
 //   preorder_k20_walk<256, DerivativeK20<false>>   VGPRs 170   SGPRs 96   scratch 0 B   2 waves per SIMD
 //   preorder_k20_walk<512, DerivativeK20<false>>   VGPRs 168   SGPRs 96   scratch 0 B   3 waves per SIMD
+//   preorder_k20_walk<256, PairSumK20>     VGPRs 196   SGPRs 95   scratch 0 B   2 waves per SIMD
+//   preorder_k20_walk<512, PairSumK20>     VGPRs 198   SGPRs 95   scratch 0 B   2 waves per SIMD
 //   LDS (dynamic, k20_preorder_lds_bytes, every consumer): R x 11 520 B + 128 B -- 46 208 B at R = 4, 92 288 B at R = 8
 // (the four products of an operation are unrolled side by side: 100 A operands in flight)
+#include <algorithm>
 #include <mutex>
 
 #include "common.hpp"
@@ -124,6 +135,8 @@ struct K20WalkArgs {
   double *work;               // [slot][rate][tile][320]
   const OuterOp *prog;
   unsigned nops;
+  unsigned tile0;             // the launch's first tile: workgroup b walks tile tile0 + b
+  const uint64_t *codemask;   // [code]: bit j set = state j is allowed (a consumer with kTipVectors)
 };
 
 struct K20Lane {
@@ -174,7 +187,7 @@ preorder_k20_walk(K20WalkArgs a, typename Consumer::Args ca) {
   ln.lane = threadIdx.x & 63u;
   ln.r = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave = rate
   ln.col = ln.lane & 15u; ln.grp = ln.lane >> 4;
-  ln.tile = blockIdx.x;
+  ln.tile = a.tile0 + blockIdx.x;
   ln.site = ln.tile * 16u + ln.col;
   ln.active = ln.site < S;
   const unsigned ls = ln.active ? ln.site : S - 1u;   // clamped for loads
@@ -231,8 +244,14 @@ preorder_k20_walk(K20WalkArgs a, typename Consumer::Args ca) {
         const double2 p23 = *reinterpret_cast<const double2 *>(row + 8u + grp * 2u);
         pl[c][0] = p01.x; pl[c][1] = p01.y; pl[c][2] = p23.x; pl[c][3] = p23.y;
         pl[c][4] = row[16u + grp];
+        if constexpr (Consumer::kTipVectors) {   // the tip's 0/1 vector over the lane's five states
+          const uint64_t mask = a.codemask[code];
 #pragma unroll
-        for (int t = 0; t < 5; ++t) l[c][t] = 0.0;   // (never read: a tip has no outer vector here)
+          for (unsigned t = 0; t < 5; ++t) l[c][t] = (double)((mask >> k20p_state_of(grp, t)) & 1u);
+        } else {
+#pragma unroll
+          for (int t = 0; t < 5; ++t) l[c][t] = 0.0;   // (never read: a tip has no outer vector here)
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();   // the staged copies are read by other lanes of this wave than wrote them
@@ -294,7 +313,7 @@ struct PosteriorK20Args {
 
 struct PosteriorK20 {
   using Args = PosteriorK20Args;
-  static constexpr bool kTipBranches = false;
+  static constexpr bool kTipBranches = false, kTipVectors = false;
   const Args c;
   double *const exchange;   // [child][rate][t][lane]
   const unsigned R;
@@ -362,7 +381,7 @@ struct DerivativeK20Args {
 template <bool kSecond>
 struct DerivativeK20 {
   using Args = DerivativeK20Args;
-  static constexpr bool kTipBranches = true;
+  static constexpr bool kTipBranches = true, kTipVectors = false;
   const Args c;
   double *const exchange;   // k20_preorder.hpp: [rate][400] rate-matrix copies, then [parity][child][rate][3][16] terms
   const unsigned R;
@@ -445,6 +464,122 @@ struct DerivativeK20 {
   }
 };
 
+// ---------------------------------------------------------------------------
+// Consumer: pair sums -- the derivative of lnL in every entry of every P-matrix
+// ---------------------------------------------------------------------------
+// Definitions: kernels_preorder.hip, above PairSumDna, with 20 states.  Per branch each wave leaves
+// w_r t.(P_a L_a) per site in LDS (`branch`, before the operation's barrier; double-buffered by
+// operation parity as the derivative consumer's terms are, for the same hazard) and keeps t and L_a
+// in registers.  Behind the barrier (op_end) every wave adds the rates in rate order, scales its t by
+// weight_s w_r / f0(s) (0 for a site without a likelihood and for a lane past S), re-deals both
+// vectors by the lane permutation k20_pair_source_lane so that the SITE becomes the reduction
+// dimension, and forms the wave's 20 x 20 sum over its 16 sites as 25 MFMAs, the four blocks of each
+// being the four quads of sites.  Order of a sum: the MFMA's own over the four sites of a quad, the
+// quads by __shfl_xor 4, then 8, one partial per (tile, entry), pair_sum_kernel over the tiles by
+// increasing number.  M, W: each wave its own rate, froot summed over the rates in rate order through
+// LDS in `begin`, the 16 sites by a butterfly (1, 2, 4, 8).  No floating-point atomics, vector stores only.
+struct PairSumK20Args {
+  const unsigned *pattern_w;
+  double *partials;           // [tile of the pass][k20_pair_sum_entries]
+  unsigned *bad_sites;        // sites whose likelihood is 0 or not finite
+};
+
+struct PairSumK20 {
+  using Args = PairSumK20Args;
+  static constexpr bool kTipBranches = true, kTipVectors = true;
+  const Args c;
+  double *const exchange;   // k20_preorder.hpp: [parity][child][rate][16] branch terms, then [rate][16] root terms
+  const unsigned R;
+  double weight = 0.0;
+  double ts[2][5], ls[2][5];   // t and L_a of the operation's two branches, until its barrier has passed
+  double *row = nullptr;       // this tile's row of partials
+  unsigned k = 0;
+  bool site_bad = false;
+  __device__ __forceinline__ PairSumK20(const Args &c, double *exchange, unsigned R) : c(c), exchange(exchange), R(R) {}
+
+  // the five states of the lane in one fixed order, then the lane groups 16 and 32 apart
+  static __device__ __forceinline__ double site_dot(const double (&x)[5], const double (&y)[5]) {
+    double p = ((x[0] * y[0] + x[1] * y[1]) + (x[2] * y[2] + x[3] * y[3])) + x[4] * y[4];
+    p += __shfl_xor(p, 16);
+    p += __shfl_xor(p, 32);
+    return p;
+  }
+  // weight / (the terms of all rates in rate order) of the lane's site; 0 for a lane past S
+  __device__ __forceinline__ double factor(const K20Lane &ln, const double *terms) {
+    double f = 0.0, g;
+    for (unsigned q = 0; q < R; ++q) f += terms[16u * q];
+    const bool ok = site_factor(f, weight, &g);
+    if (!ln.active) g = 0.0;
+    else if (!ok) site_bad = true;
+    return g;
+  }
+  __device__ __forceinline__ void begin(const K20WalkArgs &a, const K20Lane &ln, size_t tile_at) {
+    weight = (double)c.pattern_w[ln.active ? ln.site : a.sites - 1u];
+    row = c.partials + (size_t)blockIdx.x * k20_pair_sum_entries(a.nops, R);
+    double l[5];
+    load_tile(a.clv + (size_t)(a.prog[0].parent_clv - a.tips) * a.clv_stride + tile_at, ln.ll, l);
+    const double dot = site_dot(ln.pi, l);
+    if (ln.grp == 0u) exchange[k20_pair_root_index(R, ln.r, ln.col)] = ln.w * dot;
+    __syncthreads();
+    const double g = factor(ln, exchange + k20_pair_root_index(R, 0u, ln.col));
+    const double gw = g * ln.w;
+    double m[5], wv = g * dot;
+#pragma unroll
+    for (int t = 0; t < 5; ++t) m[t] = gw * l[t];
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) {
+#pragma unroll
+      for (int t = 0; t < 5; ++t) m[t] += __shfl_xor(m[t], off);
+      wv += __shfl_xor(wv, off);
+    }
+    if (ln.col == 0u) {
+      double *o = row + k20_pair_root_at(a.nops, R) + (size_t)ln.r * (kK20States + 1u);
+#pragma unroll
+      for (unsigned t = 0; t < 5; ++t) o[k20p_state_of(ln.grp, t)] = m[t];
+      if (ln.grp == 0u) o[kK20States] = wv;
+    }
+  }
+  __device__ __forceinline__ void op_begin(const K20Lane &, unsigned op) { k = op; }
+  __device__ __forceinline__ void branch(const K20Lane &ln, int ch, const double (&t)[5], const double (&y)[5],
+                                         const double (&l)[5]) {
+    const double p0 = site_dot(t, y);
+    if (ln.grp == 0u) exchange[k20_pair_term_index(R, k & 1u, (unsigned)ch, ln.r, ln.col)] = ln.w * p0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { ts[ch][i] = t[i]; ls[ch][i] = l[i]; }
+  }
+  __device__ __forceinline__ void outer(const K20Lane &, int, unsigned, const double (&)[5], const double (&)[5]) const {}
+  // Behind the walk's barrier of operation k the terms of all rates are there; every wave reads them.
+  // Parity k & 1 is written again in operation k + 2, behind the barrier of operation k + 1, which
+  // every wave reaches after these reads.
+  __device__ __forceinline__ void op_end(const K20WalkArgs &, const K20Lane &ln, bool, bool) {
+    const int src = (int)k20_pair_source_lane(ln.lane);
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      const double gw = factor(ln, exchange + k20_pair_term_index(R, k & 1u, (unsigned)ch, 0u, ln.col)) * ln.w;
+      double av[5], bv[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        av[i] = __shfl(gw * ts[ch][i], src);
+        bv[i] = __shfl(ls[ch][i], src);
+      }
+      double *o = row + (((size_t)k * 2u + (unsigned)ch) * R + ln.r) * (kK20States * kK20States);
+#pragma unroll
+      for (unsigned ib = 0; ib < 5; ++ib)
+#pragma unroll
+        for (unsigned jb = 0; jb < 5; ++jb) {
+          double n = __builtin_amdgcn_mfma_f64_4x4x4f64(av[ib], bv[jb], 0.0, 0, 0, 0);
+          n += __shfl_xor(n, 4);
+          n += __shfl_xor(n, 8);
+          if (ln.col < 4u) o[k20_pair_entry(ln.lane, ib, jb)] = n;
+        }
+    }
+  }
+  // a site is counted once, whichever of its branches found it (every wave finds the same sites)
+  __device__ __forceinline__ void end(const K20Lane &ln) const {
+    if (ln.r == 0u && ln.lane < 16u && site_bad) atomicAdd(c.bad_sites, 1u);
+  }
+};
+
 // state[row] = the smallest index among the largest of post[row][0..K), prob[row] = that posterior.
 // A workgroup's 256 rows come through LDS: the loads are contiguous over the workgroup (a lane
 // reading its own row would stride 8 K bytes from its neighbour: measured 0.66 ms for c3's 318 MB),
@@ -477,12 +612,15 @@ ancestral_argmax_kernel(const double *__restrict__ post, size_t rows, unsigned K
 
 }  // namespace
 
-// the walk of one consumer over the whole program, one workgroup per tile
+// the walk of one consumer over the whole program, one workgroup per tile: tiles tile0 .. tile0 + ntiles - 1
+// (ntiles 0: all of them)
 template <class Consumer>
 static hipError_t launch_k20_walk(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx, double *d_work,
-                           const typename Consumer::Args &ca) {
+                           const typename Consumer::Args &ca, unsigned tile0 = 0, unsigned ntiles = 0) {
   const unsigned R = p->rate_cats;
   if (!p->mfma_layout || R > kK20MaxRates) return hipErrorInvalidValue;
+  if (ntiles == 0) ntiles = p->clv_tiles() - tile0;
+  if (tile0 >= p->clv_tiles() || ntiles > p->clv_tiles() - tile0) return hipErrorInvalidValue;
   K20WalkArgs a;
   a.clv = p->d_clv; a.clv_stride = p->clv_doubles();
   a.tipcodes = p->d_tipcodes; a.tip_stride = p->tip_stride();
@@ -490,9 +628,10 @@ static hipError_t launch_k20_walk(rdamd_partition *p, const OuterOp *d_prog, uns
   a.pmfma = p->d_pmat_mfma; a.freqs = p->d_freqs; a.fidx = d_fidx; a.rate_w = p->d_rate_weights;
   a.tips = p->tips; a.sites = p->sites; a.tiles = p->clv_tiles(); a.R = R;
   a.work = d_work; a.prog = d_prog; a.nops = nops;
+  a.tile0 = tile0; a.codemask = p->d_codemask;
   const size_t lds = k20_preorder_lds_bytes(R);
   if (R <= 4) {
-    preorder_k20_walk<256, Consumer><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+    preorder_k20_walk<256, Consumer><<<ntiles, 64 * R, lds, p->stream>>>(a, ca);
   } else {
     {   // six categories and up pass the 64 KB a kernel may ask for by default
       static std::mutex lds_mu;
@@ -506,7 +645,7 @@ static hipError_t launch_k20_walk(rdamd_partition *p, const OuterOp *d_prog, uns
         lds_allowed = true;
       }
     }
-    preorder_k20_walk<512, Consumer><<<a.tiles, 64 * R, lds, p->stream>>>(a, ca);
+    preorder_k20_walk<512, Consumer><<<ntiles, 64 * R, lds, p->stream>>>(a, ca);
   }
   return hipGetLastError();
 }
@@ -526,6 +665,23 @@ hipError_t launch_brlen_program_k20(rdamd_partition *p, const OuterOp *d_prog, u
                               : launch_k20_walk<DerivativeK20<false>>(p, d_prog, nops, d_fidx, d_work, ca);
   if (e != hipSuccess) return e;
   return launch_brlen_sum(p, d_partials, p->clv_tiles(), nops * 4u, d_out);
+}
+
+hipError_t launch_pair_sum_program_k20(rdamd_partition *p, const OuterOp *d_prog, unsigned nops, const unsigned *d_fidx,
+                                       double *d_work, double *d_partials, unsigned tiles_per_pass, unsigned *d_bad_sites,
+                                       double *d_out) {
+  if (nops == 0 || p->sites == 0) return hipSuccess;
+  if (tiles_per_pass == 0) return hipErrorInvalidValue;
+  const unsigned tiles = p->clv_tiles();
+  const size_t entries = k20_pair_sum_entries(nops, p->rate_cats);
+  const PairSumK20Args ca{p->d_pattern_weights, d_partials, d_bad_sites};
+  for (unsigned t0 = 0; t0 < tiles; t0 += tiles_per_pass) {
+    const unsigned nt = std::min(tiles_per_pass, tiles - t0);
+    hipError_t e = launch_k20_walk<PairSumK20>(p, d_prog, nops, d_fidx, d_work, ca, t0, nt);
+    if (e == hipSuccess) e = launch_pair_sum_fold(p, d_partials, nt, entries, t0 == 0, d_out);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_ancestral_argmax(rdamd_partition *p, const double *d_post, size_t rows, unsigned K, uint8_t *d_state,

@@ -686,8 +686,8 @@ std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
       const partition_parameters_t &pp = params[p];
       const bool free_rates = _rate_category_types[p] == rate_category::FREE;
       std::vector<double> pair((size_t)n_ops * 2 * R * K * K), root((size_t)R * K), cat(R);
-      if (rdamd_branch_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), root.data(),
-                                 cat.data()) != RDAMD_SUCCESS)
+      if (rdamd_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), root.data(), cat.data()) !=
+          RDAMD_SUCCESS)
         return RDAMD_FAILURE;
       // pi and w as set_model_params applied them
       double xsum = 0.0, usum = 1.0;
@@ -749,7 +749,7 @@ model_t::substitutions_t model_t::substitutions(const root_location_t &rl, const
       rdamd_partition_t *part = _partitions[p];
       const size_t K = rdamd_partition_states(part), R = rdamd_partition_rate_cats(part), sites = rdamd_partition_sites(part);
       pair.assign(branches * R * K * K, 0.0);
-      if (rdamd_branch_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), nullptr, nullptr) !=
+      if (rdamd_pair_sums(part, r.ops.data(), n_ops, _param_indicies[p].data(), 0, pair.data(), nullptr, nullptr) !=
           RDAMD_SUCCESS)
         return RDAMD_FAILURE;
       const model_params_t pi = normalised(params[p].freqs);   // as set_model_params applied them

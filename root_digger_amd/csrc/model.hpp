@@ -178,7 +178,7 @@ public:
   // substitution rates as given, the unnormalised frequency vector, alpha through the MEDIAN gamma
   // rates, the unnormalised weights of a FREE partition (whose alpha entry is 0: its rates are
   // inert).  grad has the layout of params; *lnl: the log-likelihood there.  One materialising
-  // traversal, the root lnL, rdamd_branch_pair_sums per partition and the host assembly of
+  // traversal, the root lnL, rdamd_pair_sums per partition and the host assembly of
   // param_gradient.hpp.  Saves and restores what branch_lengths does.
   std::vector<partition_parameters_t> gradient(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
                                                double *lnl);

@@ -473,6 +473,7 @@ static bool sequences_refused(const rdamd_partition *p, const char *what) { retu
 static bool derivatives_refused(const rdamd_partition *p, const char *what) {
   return walks_refused(p, what, "branch-length derivatives");
 }
+static bool pair_sums_refused(const rdamd_partition *p, const char *what) { return walks_refused(p, what, "pair sums"); }
 
 // What the entry points of the pre-order pass share, in two steps: preorder_admitted, then
 // preorder_run.  (RateIndices: a per-rate-category index vector of the caller and its name.)
@@ -1344,44 +1345,55 @@ int rdamd_branch_length_derivatives(rdamd_partition_t *p, const rdamd_operation_
 }
 
 static thread_local double g_pair_sums_ms = 0.0;
+// rdamd_pair_sums, 20 states, workspace_bytes = 0: the partial sums of one pass (a tile's row is 5.1 MB
+// on a 200-taxon tree with four categories, 256 MiB a pass of 52 workgroups; measured in
+// profiles/r20_k20_pair_sums.md: 25.2 ms at 256 MiB, 6.7 ms at 1 GiB, 5.0 ms in one pass of 3.2 GB)
+constexpr size_t kK20PairSumWorkspace = (size_t)1 << 30;
 
 double rdamd_pair_sums_last_ms(void) { return g_pair_sums_ms; }
 
-int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
-                           const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
-                           double *root_out, double *cat_out) {
+// rdamd_branch_pair_sums and rdamd_pair_sums: one body, the entry point's name (`what`) and the shapes
+// it refuses (`refused`) apart.  A matrix-core 20-state partition, which only the second admits, runs
+// kernels_preorder_k20.hip's consumer, one row of partials per tile; every other shape the launches it
+// always ran.  KW: the states of the walk's rows (the caller's KA are the first of them).
+static int pair_sums_call(rdamd_partition_t *p, const char *what, bool (*refused)(const rdamd_partition *, const char *),
+                          const rdamd_operation_t *ops, unsigned int n_ops, const unsigned int *freqs_indices,
+                          size_t workspace_bytes, double *pair_out, double *root_out, double *cat_out) {
   clear_error();
   g_pair_sums_ms = 0.0;
   const std::initializer_list<RateIndices> indices = {{freqs_indices, "freqs"}};
   OuterPlan plan;
-  if (!preorder_admitted(p, "rdamd_branch_pair_sums", ops, n_ops, !ops || !freqs_indices, indices, &plan))
-    return RDAMD_FAILURE;
+  if (!preorder_admitted(p, what, ops, n_ops, !ops || !freqs_indices, indices, &plan, refused)) return RDAMD_FAILURE;
   if (!pair_out) {
-    set_error(67, "rdamd_branch_pair_sums: pair_out is null");
+    set_error(67, "%s: pair_out is null", what);
     return RDAMD_FAILURE;
   }
+  const bool k20 = p->mfma_layout;
   const size_t R = p->rate_cats, KA = p->api_states;
   std::fill(pair_out, pair_out + (size_t)n_ops * 2 * R * KA * KA, 0.0);
   if (root_out) std::fill(root_out, root_out + R * KA, 0.0);
   if (cat_out) std::fill(cat_out, cat_out + R, 0.0);
   if (p->sites == 0 || n_ops == 0) return RDAMD_SUCCESS;
   // passes over whole workgroups: as many rows of partials as the bound holds, never less than one
-  const size_t entries = pair_sum_doubles(p, n_ops);
-  if (workspace_bytes == 0) workspace_bytes = (size_t)256 << 20;
-  const unsigned blocks = preorder_blocks(p);
+  const size_t entries = k20 ? k20_pair_sum_entries(n_ops, R) : pair_sum_doubles(p, n_ops);
+  if (workspace_bytes == 0) workspace_bytes = k20 ? kK20PairSumWorkspace : (size_t)256 << 20;
+  const unsigned blocks = k20 ? p->clv_tiles() : preorder_blocks(p);
   const unsigned per_pass =
       (unsigned)std::min<size_t>(blocks, std::max<size_t>(1, workspace_bytes / (entries * sizeof(double))));
   DeviceArray<double> partials, stage, sums;
   DeviceArray<unsigned> bad_sites;
   const auto allocate = [&] {
     hipError_t e = partials.alloc(entries * per_pass);
-    if (e == hipSuccess) e = stage.alloc(std::max<size_t>(1, pair_sum_stage_doubles(p, per_pass)));
+    if (e == hipSuccess) e = stage.alloc(std::max<size_t>(1, k20 ? 0 : pair_sum_stage_doubles(p, per_pass)));
     if (e == hipSuccess) e = sums.alloc(entries);
     if (e == hipSuccess) e = bad_sites.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(bad_sites.d, 0, sizeof(unsigned), p->stream);
+    if (e == hipSuccess && k20) e = flush_tiptab(p);
     return e;
   };
   const auto launch = [&](const OuterOp *d_prog, const unsigned *const *d_indices, double *d_work) {
+    if (k20)
+      return launch_pair_sum_program_k20(p, d_prog, n_ops, d_indices[0], d_work, partials.d, per_pass, bad_sites.d, sums.d);
     return launch_pair_sum_program(p, d_prog, n_ops, plan.slots, d_indices[0], d_work, partials.d, stage.d, per_pass,
                                    bad_sites.d, sums.d);
   };
@@ -1390,23 +1402,36 @@ int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, u
   RDAMD_HIP_TRY(hipMemcpy(&bad, bad_sites.d, sizeof bad, hipMemcpyDeviceToHost), RDAMD_FAILURE);
   if (bad) {
     g_pair_sums_ms = 0.0;   // (a call that returns nothing reports no time)
-    set_error(65, "rdamd_branch_pair_sums: %u of %u sites have a likelihood that is 0 or not finite; no sum is returned",
-              bad, p->sites);
+    set_error(65, "%s: %u of %u sites have a likelihood that is 0 or not finite; no sum is returned", what, bad, p->sites);
     return RDAMD_FAILURE;
   }
   std::vector<double> host(entries);
   RDAMD_HIP_TRY(hipMemcpy(host.data(), sums.d, sizeof(double) * entries, hipMemcpyDeviceToHost), RDAMD_FAILURE);
-  // the caller's states are the first KA of the walk's 4
+  // the caller's states are the first KA of the walk's KW (4, or 20 on the matrix cores)
+  const size_t KW = k20 ? kK20States : 4;
   for (size_t b = 0; b < (size_t)n_ops * 2 * R; ++b)
     for (size_t i = 0; i < KA; ++i)
-      for (size_t j = 0; j < KA; ++j) pair_out[(b * KA + i) * KA + j] = host[b * 16 + i * 4 + j];
-  const double *root = host.data() + (size_t)n_ops * 2 * R * 16;
+      for (size_t j = 0; j < KA; ++j) pair_out[(b * KA + i) * KA + j] = host[(b * KW + i) * KW + j];
+  const double *root = host.data() + (size_t)n_ops * 2 * R * KW * KW;
   for (size_t r = 0; r < R; ++r) {
     if (root_out)
-      for (size_t i = 0; i < KA; ++i) root_out[r * KA + i] = root[r * 5 + i];
-    if (cat_out) cat_out[r] = root[r * 5 + 4];
+      for (size_t i = 0; i < KA; ++i) root_out[r * KA + i] = root[r * (KW + 1) + i];
+    if (cat_out) cat_out[r] = root[r * (KW + 1) + KW];
   }
   return RDAMD_SUCCESS;
+}
+
+int rdamd_branch_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops,
+                           const unsigned int *freqs_indices, size_t workspace_bytes, double *pair_out,
+                           double *root_out, double *cat_out) {
+  return pair_sums_call(p, "rdamd_branch_pair_sums", outer_refused, ops, n_ops, freqs_indices, workspace_bytes, pair_out,
+                        root_out, cat_out);
+}
+
+int rdamd_pair_sums(rdamd_partition_t *p, const rdamd_operation_t *ops, unsigned int n_ops, const unsigned int *freqs_indices,
+                    size_t workspace_bytes, double *pair_out, double *root_out, double *cat_out) {
+  return pair_sums_call(p, "rdamd_pair_sums", pair_sums_refused, ops, n_ops, freqs_indices, workspace_bytes, pair_out,
+                        root_out, cat_out);
 }
 
 static thread_local double g_subst_ms = 0.0;
