@@ -1214,6 +1214,47 @@ int rdamd_gradient_from_pair_sums(unsigned int states, unsigned int rate_cats, u
                                   const double *rates, const double *weights, double *d_subst, double *d_freqs,
                                   double *d_rates, double *d_weights);
 
+/* ------------------------------------------------------------------------
+ * The adjoints of the pair sums: the one expensive step that the gradient and the typed counts share,
+ * on the host or -- for 20 states -- on the matrix cores.  NEW relative to the reference.
+ *   adjoint[k][c][r] = F_r = F((rho_r tau Q_m)^T, N[k][c][r]),  m = params_indices[r], tau = lengths[k][c]
+ * with Q_m and F as rdamd_gradient_from_pair_sums defines them.  Every F_r is computed as
+ *   s, 2^-s: ||X||_1 halved until it is at most 1/4 (at most 60 times), X = (rho_r tau Q_m)^T;
+ *   18 Taylor terms on the pair (exp, F) of X / 2^s and E / 2^s;  s squarings (P, F) -> (P P, P F + F P).
+ * rdamd_gradient_from_pair_sums is rdamd_pair_sum_adjoints on the host followed by
+ * rdamd_gradient_from_adjoints, and rdamd_substitution_counts_from_pair_sums likewise: same bits.
+ * The device route (csrc/kernels_block_exp.hip) runs one (branch, rate) problem per wave with the
+ * host's s, the same recurrences (Taylor terms as left products: T_k = X T_{k-1} / k where the host
+ * forms T_{k-1} X) and every 20 x 20 x 20 product as 20 v_mfma_f64_16x16x4_f64; it differs from the
+ * host route only in the order inside dot products of length 20.  The bits of one problem depend on
+ * nothing but that problem's inputs; two calls return the same bits.
+ * ---------------------------------------------------------------------- */
+#define RDAMD_ADJOINTS_AUTO 0   /* the device when states = 20 and a device is present, else the host */
+#define RDAMD_ADJOINTS_HOST 1   /* 2 .. 64 states; the bits of rdamd_gradient_from_pair_sums' own block exponentials */
+#define RDAMD_ADJOINTS_DEVICE 2 /* 20 states on the current device */
+/* pair[n_ops][2][R][K][K], lengths[n_ops][2], subst[rate_matrices][K K - K], freqs[rate_matrices][K],
+ * params_indices[R], rates[R] as rdamd_gradient_from_pair_sums takes them; adjoint_out[n_ops][2][R][K][K].
+ * Host pointers in and out, no partition: the device route owns its device memory, its stream and
+ * its events and leaves no state behind.  Errors, before anything runs: 64 for a NULL argument, a
+ * state count outside 2 .. 64, no rate category or rate matrix, a length or rate that is negative or
+ * not finite, or an unknown `where`; 7 for an index >= rate_matrices; 63 for RDAMD_ADJOINTS_DEVICE
+ * with a state count other than 20 or with no device present (the message says which).  Zero
+ * operations: success, nothing written. */
+int rdamd_pair_sum_adjoints(unsigned int states, unsigned int rate_cats, unsigned int rate_matrices, unsigned int n_ops,
+                            const double *pair, const double *lengths, const double *subst, const double *freqs,
+                            const unsigned int *params_indices, const double *rates, int where, double *adjoint_out);
+/* device time of the kernel of this thread's last rdamd_pair_sum_adjoints call, milliseconds between
+ * two HIP events (0 after a failed call and after one that took the host route); for measurements */
+double rdamd_pair_sum_adjoints_last_ms(void);
+/* rdamd_gradient_from_pair_sums' assembly alone: the arguments, outputs and errors of that function
+ * with adjoint[n_ops][2][R][K][K] (rdamd_pair_sum_adjoints) in place of pair.  Host only and pure. */
+int rdamd_gradient_from_adjoints(unsigned int states, unsigned int rate_cats, unsigned int rate_matrices,
+                                 unsigned int n_ops, const double *adjoint, const double *root, const double *cat,
+                                 const double *lengths, const double *subst, const double *freqs,
+                                 const unsigned int *params_indices, const unsigned int *freqs_indices,
+                                 const double *rates, const double *weights, double *d_subst, double *d_freqs,
+                                 double *d_rates, double *d_weights);
+
 /* The exact gradient of lnL at one root of a model.  counts / values: the parameters in the
  * checkpoint's layout exactly as rdamd_model_branch_derivatives takes them, here required (the
  * model does not keep the optimiser's variables).  grad_out has the layout of values and holds the
@@ -1225,7 +1266,9 @@ int rdamd_gradient_from_pair_sums(unsigned int states, unsigned int rate_cats, u
  *   the unnormalised category weights u of a FREE partition, w = u / sum u; a FREE partition's rates
  *     are inert, so its alpha entry is 0; the weight entries of any other partition are 0.
  * Each evaluation is rdamd_update_prob_matrices, a materialising traversal, the root lnL (*lnl_out,
- * may be NULL), rdamd_pair_sums per partition and rdamd_gradient_from_pair_sums: DNA, binary and
+ * may be NULL), rdamd_pair_sums per partition, rdamd_pair_sum_adjoints (RDAMD_ADJOINTS_AUTO: a
+ * protein partition's on the device, every other on the host with the bits of
+ * rdamd_gradient_from_pair_sums) and rdamd_gradient_from_adjoints: DNA, binary and
  * protein models are served (a protein partition: 380 rates, 20 frequencies and alpha from one pass
  * of the walk, where a one-sided difference takes 381 evaluations).  The model's
  * parameters, its rooting and the conditional likelihoods of that rooting are as before when the
@@ -1298,6 +1341,14 @@ int rdamd_substitution_counts_from_pair_sums(unsigned int states, unsigned int r
                                              const double *subst, const double *freqs,
                                              const unsigned int *params_indices, const double *rates,
                                              double *typed_out);
+/* rdamd_substitution_counts_from_pair_sums' assembly alone: the arguments, output and errors of that
+ * function with adjoint[n_ops][2][R][K][K] (rdamd_pair_sum_adjoints) in place of pair.  Host only
+ * and pure. */
+int rdamd_substitution_counts_from_adjoints(unsigned int states, unsigned int rate_cats, unsigned int rate_matrices,
+                                            unsigned int n_ops, const double *adjoint, const double *lengths,
+                                            const double *subst, const double *freqs,
+                                            const unsigned int *params_indices, const double *rates,
+                                            double *typed_out);
 /* All of it for one root of a model.  counts / values: the parameters in the checkpoint's layout
  * exactly as rdamd_model_gradient takes them (required).  Outputs, any of which may be NULL:
  * *n_nodes, node_clv, node_parent, node_children, lengths_out[n][2] as
@@ -1306,7 +1357,8 @@ int rdamd_substitution_counts_from_pair_sums(unsigned int states, unsigned int r
  * top_prob_out[n][2][P_total] and top_pair_out[n][2][P_total] (bytes) with the patterns of all
  * partitions concatenated in partition order (rdamd_model_site_patterns); *lnl_out: the
  * log-likelihood at that root.  Each partition: rdamd_update_prob_matrices, a materialising
- * traversal, rdamd_pair_sums, rdamd_substitution_counts_from_pair_sums and -- unless change_out,
+ * traversal, rdamd_pair_sums, rdamd_pair_sum_adjoints (RDAMD_ADJOINTS_AUTO),
+ * rdamd_substitution_counts_from_adjoints and -- unless change_out,
  * count_out, top_pair_out and top_prob_out are all NULL -- rdamd_branch_substitutions.  With those
  * four NULL the call serves every shape rdamd_pair_sums takes, protein models among them: typed_out
  * then holds the expected i -> j counts over 20 x 20 amino-acid pairs and the dwell times.  The

@@ -316,6 +316,11 @@ _sig("rdamd_pair_sums", C.c_int, _vp, _pop, _u, _pu, C.c_size_t, _pd, _pd, _pd)
 _sig("rdamd_pair_sums_last_ms", C.c_double)
 _sig("rdamd_gradient_from_pair_sums", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pd, _pd, _pd, _pd,
      _pd, _pd)
+_sig("rdamd_pair_sum_adjoints", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pu, _pd, C.c_int, _pd)
+_sig("rdamd_pair_sum_adjoints_last_ms", C.c_double)
+_sig("rdamd_gradient_from_adjoints", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pd, _pd, _pu, _pu, _pd, _pd, _pd, _pd,
+     _pd, _pd)
+_sig("rdamd_substitution_counts_from_adjoints", C.c_int, _u, _u, _u, _u, _pd, _pd, _pd, _pd, _pu, _pd, _pd)
 _pub = C.POINTER(C.c_ubyte)
 _sig("rdamd_branch_substitutions", C.c_int, _vp, _pop, _u, _pu, _pu, _pd, _pd, _pd, _pub, _pd, _pd)
 _sig("rdamd_branch_substitutions_last_ms", C.c_double)
@@ -1273,10 +1278,7 @@ def pair_sums_last_ms():
     return float(lib.rdamd_pair_sums_last_ms())
 
 
-def gradient_from_pair_sums(pair, root, cat, lengths, subst, freqs, params_indices, freqs_indices, rates, weights):
-    """(d_subst[m][K K - K], d_freqs[m][K], d_rates[R], d_weights[R]): the exact gradient of lnL from the
-    pair sums of branch_pair_sums (rdamd_gradient_from_pair_sums; host only).  subst[m], freqs[m]: the
-    rate-matrix sets; frequencies enter exactly as given."""
+def _gradient_assembly(who, entry, pair, root, cat, lengths, subst, freqs, params_indices, freqs_indices, rates, weights):
     pair = np.ascontiguousarray(pair, dtype=np.float64)
     n, _, R, K, _ = pair.shape
     root, cat, lengths, rates, weights = (np.ascontiguousarray(v, dtype=np.float64) for v in (root, cat, lengths, rates, weights))
@@ -1284,29 +1286,33 @@ def gradient_from_pair_sums(pair, root, cat, lengths, subst, freqs, params_indic
     freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1, K)
     sets = subst.shape[0]
     if freqs.shape[0] != sets or lengths.shape != (n, 2) or root.shape != (R, K) or any(v.shape != (R,) for v in (cat, rates, weights)):
-        raise ValueError("gradient_from_pair_sums: shapes do not fit the pair sums")
+        raise ValueError(who + ": shapes do not fit the pair sums")
     pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
     fi = np.ascontiguousarray(freqs_indices, dtype=np.uint32)
     if pi.shape != (R,) or fi.shape != (R,):
-        raise ValueError("gradient_from_pair_sums: one index per rate category")
+        raise ValueError(who + ": one index per rate category")
     d_subst, d_freqs, d_rates, d_weights = np.zeros_like(subst), np.zeros_like(freqs), np.zeros(R), np.zeros(R)
-    if lib.rdamd_gradient_from_pair_sums(K, R, sets, n, _dptr(pair), _dptr(root), _dptr(cat), _dptr(lengths), _dptr(subst),
-                                         _dptr(freqs), _uptr(pi), _uptr(fi), _dptr(rates), _dptr(weights), _dptr(d_subst),
-                                         _dptr(d_freqs), _dptr(d_rates), _dptr(d_weights)) != 1:
-        _fail("gradient_from_pair_sums")
+    if entry(K, R, sets, n, _dptr(pair), _dptr(root), _dptr(cat), _dptr(lengths), _dptr(subst), _dptr(freqs), _uptr(pi),
+             _uptr(fi), _dptr(rates), _dptr(weights), _dptr(d_subst), _dptr(d_freqs), _dptr(d_rates), _dptr(d_weights)) != 1:
+        _fail(who)
     return d_subst, d_freqs, d_rates, d_weights
 
 
-def branch_substitutions_last_ms():
-    """device milliseconds of the launch of this thread's last branch_substitutions call"""
-    return float(lib.rdamd_branch_substitutions_last_ms())
-
-
-def substitution_counts(pair, lengths, subst, freqs, params_indices, rates):
-    """typed[n][2][K][K] from the pair sums of branch_pair_sums (rdamd_substitution_counts_from_pair_sums;
-    host only): off the diagonal the expected number of i -> j substitutions on branch (k, c) over the
-    whole alignment, on the diagonal the expected time spent in state i.  subst[m], freqs[m]: the
+def gradient_from_pair_sums(pair, root, cat, lengths, subst, freqs, params_indices, freqs_indices, rates, weights):
+    """(d_subst[m][K K - K], d_freqs[m][K], d_rates[R], d_weights[R]): the exact gradient of lnL from the
+    pair sums of branch_pair_sums (rdamd_gradient_from_pair_sums; host only).  subst[m], freqs[m]: the
     rate-matrix sets; frequencies enter exactly as given."""
+    return _gradient_assembly("gradient_from_pair_sums", lib.rdamd_gradient_from_pair_sums, pair, root, cat, lengths, subst,
+                              freqs, params_indices, freqs_indices, rates, weights)
+
+
+ADJOINTS_WHERE = {"auto": 0, "host": 1, "device": 2}
+
+
+def pair_sum_adjoints(pair, lengths, subst, freqs, params_indices, rates, where="auto"):
+    """adjoint[n][2][R][K][K] = F((rho_r tau Q)^T, pair[n][c][r]): the block exponentials that the gradient
+    and the typed counts share (rdamd_pair_sum_adjoints).  where: "auto" (the device for 20 states when
+    one is present, else the host), "host" (2 .. 64 states) or "device" (20 states only)."""
     pair = np.ascontiguousarray(pair, dtype=np.float64)
     n, _, R, K, _ = pair.shape
     lengths, rates = (np.ascontiguousarray(v, dtype=np.float64) for v in (lengths, rates))
@@ -1314,15 +1320,69 @@ def substitution_counts(pair, lengths, subst, freqs, params_indices, rates):
     freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1, K)
     sets = subst.shape[0]
     if freqs.shape[0] != sets or lengths.shape != (n, 2) or rates.shape != (R,):
-        raise ValueError("substitution_counts: shapes do not fit the pair sums")
+        raise ValueError("pair_sum_adjoints: shapes do not fit the pair sums")
     pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
     if pi.shape != (R,):
-        raise ValueError("substitution_counts: one index per rate category")
+        raise ValueError("pair_sum_adjoints: one index per rate category")
+    if where not in ADJOINTS_WHERE:
+        raise ValueError("pair_sum_adjoints: where is one of " + ", ".join(ADJOINTS_WHERE))
+    adjoint = np.zeros_like(pair)
+    if lib.rdamd_pair_sum_adjoints(K, R, sets, n, _dptr(pair), _dptr(lengths), _dptr(subst), _dptr(freqs), _uptr(pi),
+                                   _dptr(rates), ADJOINTS_WHERE[where], _dptr(adjoint)) != 1:
+        _fail("pair_sum_adjoints")
+    return adjoint
+
+
+def pair_sum_adjoints_last_ms():
+    """device milliseconds of the kernel of this thread's last pair_sum_adjoints call (0 on the host route)"""
+    return float(lib.rdamd_pair_sum_adjoints_last_ms())
+
+
+def gradient_from_adjoints(adjoint, root, cat, lengths, subst, freqs, params_indices, freqs_indices, rates, weights):
+    """gradient_from_pair_sums' assembly alone, from the adjoints of pair_sum_adjoints
+    (rdamd_gradient_from_adjoints; host only)."""
+    return _gradient_assembly("gradient_from_adjoints", lib.rdamd_gradient_from_adjoints, adjoint, root, cat, lengths, subst,
+                              freqs, params_indices, freqs_indices, rates, weights)
+
+
+def branch_substitutions_last_ms():
+    """device milliseconds of the launch of this thread's last branch_substitutions call"""
+    return float(lib.rdamd_branch_substitutions_last_ms())
+
+
+def _counts_assembly(who, entry, pair, lengths, subst, freqs, params_indices, rates):
+    pair = np.ascontiguousarray(pair, dtype=np.float64)
+    n, _, R, K, _ = pair.shape
+    lengths, rates = (np.ascontiguousarray(v, dtype=np.float64) for v in (lengths, rates))
+    subst = np.ascontiguousarray(subst, dtype=np.float64).reshape(-1, K * K - K)
+    freqs = np.ascontiguousarray(freqs, dtype=np.float64).reshape(-1, K)
+    sets = subst.shape[0]
+    if freqs.shape[0] != sets or lengths.shape != (n, 2) or rates.shape != (R,):
+        raise ValueError(who + ": shapes do not fit the pair sums")
+    pi = np.ascontiguousarray(params_indices, dtype=np.uint32)
+    if pi.shape != (R,):
+        raise ValueError(who + ": one index per rate category")
     typed = np.zeros((n, 2, K, K), dtype=np.float64)
-    if lib.rdamd_substitution_counts_from_pair_sums(K, R, sets, n, _dptr(pair), _dptr(lengths), _dptr(subst), _dptr(freqs),
-                                                    _uptr(pi), _dptr(rates), _dptr(typed)) != 1:
-        _fail("substitution_counts")
+    if entry(K, R, sets, n, _dptr(pair), _dptr(lengths), _dptr(subst), _dptr(freqs), _uptr(pi), _dptr(rates),
+             _dptr(typed)) != 1:
+        _fail(who)
     return typed
+
+
+def substitution_counts(pair, lengths, subst, freqs, params_indices, rates):
+    """typed[n][2][K][K] from the pair sums of branch_pair_sums (rdamd_substitution_counts_from_pair_sums;
+    host only): off the diagonal the expected number of i -> j substitutions on branch (k, c) over the
+    whole alignment, on the diagonal the expected time spent in state i.  subst[m], freqs[m]: the
+    rate-matrix sets; frequencies enter exactly as given."""
+    return _counts_assembly("substitution_counts", lib.rdamd_substitution_counts_from_pair_sums, pair, lengths, subst, freqs,
+                            params_indices, rates)
+
+
+def substitution_counts_from_adjoints(adjoint, lengths, subst, freqs, params_indices, rates):
+    """substitution_counts' assembly alone, from the adjoints of pair_sum_adjoints
+    (rdamd_substitution_counts_from_adjoints; host only)."""
+    return _counts_assembly("substitution_counts_from_adjoints", lib.rdamd_substitution_counts_from_adjoints, adjoint, lengths,
+                            subst, freqs, params_indices, rates)
 
 
 def rell_last_resample_ms():

@@ -671,7 +671,8 @@ model_t::branch_lengths_t model_t::branch_lengths(const root_location_t &rl, con
 }
 
 // The exact gradient at one root in the optimiser's variables (model.hpp).  The pair sums give
-// d lnL / d (subst, pi, rho, w) with pi and w as the partition holds them (rdamd_gradient_from_pair_sums);
+// d lnL / d (subst, pi, rho, w) with pi and w as the partition holds them (rdamd_pair_sum_adjoints, then
+// rdamd_gradient_from_adjoints: the two halves of rdamd_gradient_from_pair_sums);
 // the chain rule to the optimiser's variables is closed-form for pi = x / sum x and w = u / sum u,
 // and a central difference of the host's own rdamd_compute_gamma_cats (step 1e-6 max(1, alpha))
 // for rho(alpha).  (No node arrays: nothing here is per node.)
@@ -700,9 +701,14 @@ std::vector<partition_parameters_t> model_t::gradient(const root_location_t &rl,
       g.gamma_alpha.assign(pp.gamma_alpha.size(), 0.0);
       g.gamma_weights.assign(pp.gamma_weights.size(), 0.0);
       const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
-      if (rdamd_gradient_from_pair_sums(K, R, 1, n_ops, pair.data(), root.data(), cat.data(), r.frame.lengths.data(),
-                                        pp.subst_rates.data(), pi.data(), zeros.data(), zeros.data(), _rate_rates[p].data(),
-                                        w.data(), g.subst_rates.data(), d_pi.data(), d_rho.data(), d_w.data()) != RDAMD_SUCCESS)
+      // the adjoints where they are cheapest (a protein partition's on the device), then the assembly
+      std::vector<double> adjoint(pair.size());
+      if (rdamd_pair_sum_adjoints(K, R, 1, n_ops, pair.data(), r.frame.lengths.data(), pp.subst_rates.data(), pi.data(),
+                                  zeros.data(), _rate_rates[p].data(), RDAMD_ADJOINTS_AUTO, adjoint.data()) != RDAMD_SUCCESS)
+        return RDAMD_FAILURE;
+      if (rdamd_gradient_from_adjoints(K, R, 1, n_ops, adjoint.data(), root.data(), cat.data(), r.frame.lengths.data(),
+                                       pp.subst_rates.data(), pi.data(), zeros.data(), zeros.data(), _rate_rates[p].data(),
+                                       w.data(), g.subst_rates.data(), d_pi.data(), d_rho.data(), d_w.data()) != RDAMD_SUCCESS)
         return RDAMD_FAILURE;
       double mean = 0.0;
       for (unsigned i = 0; i < K; ++i) mean += pi[i] * d_pi[i];
@@ -743,7 +749,7 @@ model_t::substitutions_t model_t::substitutions(const root_location_t &rl, const
       out.top_prob.assign(branches * total, 0.0);
       out.top_pair.assign(branches * total, 0);
     }
-    std::vector<double> pair, change, count, top_prob;
+    std::vector<double> pair, adjoint, change, count, top_prob;
     std::vector<unsigned char> top_pair;
     out.lnl = evaluate_partitions(r.ops, r.pmi, r.brl, true, [&](size_t p, size_t at) {
       rdamd_partition_t *part = _partitions[p];
@@ -756,9 +762,14 @@ model_t::substitutions_t model_t::substitutions(const root_location_t &rl, const
       const std::vector<unsigned> zeros(R, 0u);   // (a model's partition has one rate matrix)
       const size_t typed_at = out.typed.size();
       out.typed.resize(typed_at + branches * K * K);
-      if (rdamd_substitution_counts_from_pair_sums((unsigned)K, (unsigned)R, 1, n_ops, pair.data(), out.lengths.data(),
-                                                   params[p].subst_rates.data(), pi.data(), zeros.data(),
-                                                   _rate_rates[p].data(), out.typed.data() + typed_at) != RDAMD_SUCCESS)
+      adjoint.resize(pair.size());
+      if (rdamd_pair_sum_adjoints((unsigned)K, (unsigned)R, 1, n_ops, pair.data(), out.lengths.data(),
+                                  params[p].subst_rates.data(), pi.data(), zeros.data(), _rate_rates[p].data(),
+                                  RDAMD_ADJOINTS_AUTO, adjoint.data()) != RDAMD_SUCCESS)
+        return RDAMD_FAILURE;
+      if (rdamd_substitution_counts_from_adjoints((unsigned)K, (unsigned)R, 1, n_ops, adjoint.data(), out.lengths.data(),
+                                                  params[p].subst_rates.data(), pi.data(), zeros.data(),
+                                                  _rate_rates[p].data(), out.typed.data() + typed_at) != RDAMD_SUCCESS)
         return RDAMD_FAILURE;
       if (!per_site) return RDAMD_SUCCESS;
       change.resize(branches * sites); count.resize(branches * sites);

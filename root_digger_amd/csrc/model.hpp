@@ -178,8 +178,9 @@ public:
   // substitution rates as given, the unnormalised frequency vector, alpha through the MEDIAN gamma
   // rates, the unnormalised weights of a FREE partition (whose alpha entry is 0: its rates are
   // inert).  grad has the layout of params; *lnl: the log-likelihood there.  One materialising
-  // traversal, the root lnL, rdamd_pair_sums per partition and the host assembly of
-  // param_gradient.hpp.  Saves and restores what branch_lengths does.
+  // traversal, the root lnL, rdamd_pair_sums per partition, rdamd_pair_sum_adjoints (a protein
+  // partition's on the device) and the host assembly of param_gradient.hpp.  Saves and restores
+  // what branch_lengths does.
   std::vector<partition_parameters_t> gradient(const root_location_t &rl, const std::vector<partition_parameters_t> &params,
                                                double *lnl);
   // Substitutions mapped onto the branches at root rl (include/root_digger_amd.h,
